@@ -19,22 +19,37 @@ PCM and metadata are already resident in HBM when the timed region starts:
      (seld_graph.py; trainer.train_model's own path).  N > 1: the backward pass is cut into stages, one graph each, and
      the gradient buckets a stage completes are all-reduced over RCCL asynchronously while the next stages replay.
 clips/s = N * 32 * K / (max-over-ranks wall time); weak scaling (every rank has its own 32 clips).
+ms_per_step = that wall time / K.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs DIR) and prints the line.  The JSON
+line always carries
   roofline      : the hand-written log-mel kernel against the HBM roofline -- algorithmic bytes
                   (26.11 MB per 60 s clip: 23.04 MB fp32 PCM in + 3.07 MB log-mel out) x 32
                   clips per launch / average launch duration measured with HIP events on the launch stream;
                   `traffic` = HBM bytes per launch from the committed rocprofv3 --pmc passes (profiles/);
   roofline_model: the optimiser iterations against the dense bf16 MFMA peak (39.4 GFLOP/window for the CRNN);
+  allreduce_overlap : N > 1: true / false for the run, with `gradient_buckets`;
+and with --full, after the timed region (--no-kernel-rooflines / --no-other-workloads / --no-cpu-baseline drop parts):
   kernels       : every other hand-written kernel (conv tail, loss, window gather, BiGRU recurrence) at the
                   workload's shapes against the roofline that bounds it, timed after the timed region;
   allreduce_overlap : N = 1: the data-parallel step's stage graphs replayed on this GPU without collectives, HIP events
                   between the replays (duration of every stage, bytes of every gradient bucket, the window that hides its
-                  all-reduce); N > 1: true / false for the run, with `gradient_buckets`;
+                  all-reduce);
   other_workloads : 2 warm-up + 3 timed steps each of the other BASELINE.json workloads (configs[2], configs[4] on one GPU,
                   configs[3]'s per-GPU shard) in the same process, after the timed region -- never part of `value`;
   cpu_baseline  : the oracle (torch CPU restatement of the reference path) timed on this host's
-                  cores on a bounded sample -- a reported, non-target number.
+                  cores on a bounded sample -- a reported, non-target number;
+  config.replicas_in_sync : N > 1: every replica holds the same weights after the timed steps.
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0's) as float32 .npy files, about 23 MB:
+  loss.npy        the loss of its last optimiser iteration;
+  features.npy    the feature tensor [clips, frames, feature channels, 64 mel] at a seeded sample of frames;
+  labels.npy      the compact label masks [clips, frames, 648] (bit c <=> class c, 18 x 36 grid) at the same frames;
+  frames.npy      those frame indices (float64).
+The inputs are seeded: the same arguments give the same inputs, features and label masks in every run, and the same loss
+up to the rounding of the bf16 path.  The weights are not dumped: the library's convolution weight gradients add with
+atomics and MIOpen's find picks among near-equal kernels by timing, so after 60 x (W + K) Adam updates two runs hold
+visibly different weights (the deterministic convolution mode of MIOpen leaves only its naive kernels).
 
 Launching N > 1 ranks.  Under torchrun (RANK / WORLD_SIZE set, the driver's form) this process IS one rank.  Started
 plainly as ``python bench.py --gpus N`` it has not touched the GPU yet (``torch.cuda.device_count()`` does not initialise
@@ -63,6 +78,11 @@ PKG = ROOT / "sound-event-localization-detection_amd"
 for p in (str(ROOT), str(PKG)):
     if p not in sys.path:
         sys.path.insert(0, p)
+# MIOpen's find (cudnn.benchmark) also compiles and times its naive reference convolutions, 60 - 270 ms per run against
+# 0.03 - 0.17 ms for the solvers it selects at these shapes: 13 of the 25 s the first step takes with an empty kernel
+# cache.  They never win, so leaving them out changes no selection, only the start-up time.
+for _v in ("FWD", "BWD", "WRW"):
+    os.environ.setdefault(f"MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_{_v}", "0")
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -89,6 +109,11 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure `kernels`, `allreduce_overlap` (one GPU), `other_workloads` "
+                         "and `cpu_baseline`, and check that the replicas agree (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-rooflines", action="store_true",
                     help="skip the post-timing micro-benchmarks of the hand-written kernels (profiled runs: the kernel "
@@ -262,6 +287,33 @@ class HotPath:
             m1.record()
             self.model_events.append((m0, m1))
         return last
+
+
+DUMP_BYTES = 16 << 20             # bytes of features.npy and of labels.npy at most
+
+
+def _seeded_sample(n, k, seed):
+    """k sorted indices out of range(n), the same for every run (all of them when k >= n)."""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(hot, loss, out_dir):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files under ``out_dir`` (bench.py docstring)."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    with torch.no_grad():
+        np.save(out / "loss.npy", loss.detach().float().reshape(1).cpu().numpy())
+        clips, channels = hot.spec_full.shape[0], hot.spec_full.shape[2]
+        per_frame = clips * max(channels * 64, hot.mask_tm.shape[1]) * 4
+        frames = _seeded_sample(FRAMES_PER_CLIP, max(1, DUMP_BYTES // per_frame), 1)
+        idx = torch.from_numpy(frames).to(hot.device)
+        np.save(out / "frames.npy", frames.astype(np.float64))
+        np.save(out / "features.npy", hot.spec_full.index_select(1, idx).float().cpu().numpy())
+        rows = (torch.arange(clips, device=hot.device)[:, None] * FRAMES_PER_CLIP + idx[None]).reshape(-1)
+        masks = hot.mask_tm.view(torch.int16).index_select(0, rows).cpu().numpy().view(np.uint16)
+        np.save(out / "labels.npy", masks.reshape(clips, len(frames), -1).astype(np.float32))
 
 
 def measured_traffic_per_clip():
@@ -537,6 +589,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "RANK" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args))          # BEFORE anything initialises the GPU in this process
     if world != args.gpus:
@@ -582,8 +636,11 @@ def main():
         per_rank = [float(t.item()) for t in every]
         elapsed = max(per_rank)                               # the job is as slow as its slowest rank
 
-    in_sync = None
-    if world > 1:       # every replica must hold the same weights after the timed steps (sum of all parameters)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(hot, loss, args.dump_outputs)
+
+    in_sync, out_of_sync = None, []
+    if world > 1 and args.full:       # every replica must hold the same weights after the timed steps (sum of all parameters)
         with torch.no_grad():
             total = sum(p.double().sum() for p in hot.model.parameters()).reshape(1)
         if backend != "nccl":
@@ -592,7 +649,6 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         in_sync = bool((hi - lo).abs().item() <= 1e-9 * max(1.0, abs(hi.item())))
-        out_of_sync = []
         if not in_sync:          # name the tensors that differ (a diagnostic: this never happens in a healthy run)
             with torch.no_grad():
                 each = torch.stack([p.double().sum() for p in hot.model.parameters()])
@@ -648,7 +704,8 @@ def main():
         }
         if world > 1:
             line["config"]["backend"] = "rccl (torch.distributed 'nccl')" if backend == "nccl" else backend
-            line["config"]["replicas_in_sync"] = in_sync
+            if args.full:
+                line["config"]["replicas_in_sync"] = in_sync
             if out_of_sync:
                 line["config"]["replicas_out_of_sync"] = out_of_sync
             line["config"]["per_rank_clips_per_s"] = [CLIPS_PER_STEP * args.steps / t for t in per_rank]
@@ -665,18 +722,18 @@ def main():
         if hasattr(hot.optimizer, "fused_casts"):
             line["config"]["master_weights"] = {"one_launch_gradient_casts": hot.optimizer.fused_casts,
                                                 "per_tensor_fallbacks": hot.optimizer.fallback_casts}
-        if world == 1 and not args.no_kernel_rooflines:
+        if world == 1 and args.full and not args.no_kernel_rooflines:
             line["kernels"] = kernel_rooflines(device)
             if hasattr(hot.stepper, "stats"):
                 line["allreduce_overlap"] = overlap_windows(hot, device)
-        if world == 1 and not args.no_other_workloads and args.model == "crnn" and args.features == "logmel" \
+        if world == 1 and args.full and not args.no_other_workloads and args.model == "crnn" and args.features == "logmel" \
                 and args.loss == "class" and not args.fp32:
             if hasattr(hot.stepper, "close"):
                 hot.stepper.close()
             hot.pcm = hot.spec_full = hot.mask_tm = None
             torch.cuda.empty_cache()
             line["other_workloads"] = other_workloads(args, device)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line))
     if world > 1:

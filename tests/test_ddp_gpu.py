@@ -25,11 +25,12 @@ def _rehearsal_line():
     """ONE two-rank rehearsal of bench.py per test session (a launch costs most of a minute on a fresh box and the driver
     gives the whole GPU suite 900 s): ``python bench.py --gpus 2 --rehearse-gloo`` starts its own ranks with exactly the
     command the driver uses for N > 1 (``python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr
-    127.0.0.1 --master-port P bench.py --gpus 2 ...``, bench.py::launch_ranks) and relays rank 0's line."""
+    127.0.0.1 --master-port P bench.py --gpus 2 ...``, bench.py::launch_ranks) and relays rank 0's line.  ``--full``: the
+    line then carries the replica agreement check."""
     if "line" not in _bench:
         out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                              "--rehearse-gloo", "--rehearsal-clips", "8"], env=_bench_env(), capture_output=True, text=True,
-                             timeout=900, cwd=str(ROOT))
+                              "--rehearse-gloo", "--rehearsal-clips", "8", "--full"], env=_bench_env(), capture_output=True,
+                             text=True, timeout=900, cwd=str(ROOT))
         assert out.returncode == 0, out.stderr[-2000:]
         _bench["line"] = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     return _bench["line"]
