@@ -273,6 +273,17 @@ int seld_gru_dwhh_finish(const void* p_gi, const void* p_n, int in_is_bf16, int6
  * forward convolution.  elem_bytes 2 (bf16) or 4. */
 int seld_conv_weight_flip_transpose(const void* w, int elem_bytes, int64_t O, int64_t I, void* wt, void* stream);
 
+/* Weight gradient of a 3x3 / stride 1 / pad 1 / bias-free convolution (model_crnn.py:5-17) on channels-last bf16
+ * tensors: x [B][T][F][Cin] (the saved input), dy [B][T][F][Cout] -> dw [Cout][3][3][Cin] (the weight's channels-last
+ * memory), bf16 when dw_is_bf16, else fp32.  F in {8, 16, 32}, Cin % 64 == 0, Cout % 64 == 0 (see _supported); all
+ * pointers 16-byte aligned.  Split over K slabs that each write an fp32 partial into `workspace`
+ * (seld_conv3x3_wgrad_workspace_floats floats, no initialisation needed), added in a fixed order by a second launch:
+ * deterministic, no atomics. */
+int seld_conv3x3_wgrad_supported(int64_t F, int64_t Cin, int64_t Cout);
+int64_t seld_conv3x3_wgrad_workspace_floats(int64_t B, int64_t T, int64_t F, int64_t Cin, int64_t Cout);
+int seld_conv3x3_wgrad(const void* x, const void* dy, int64_t B, int64_t T, int64_t F, int64_t Cin, int64_t Cout,
+                       void* dw, int dw_is_bf16, float* workspace, void* stream);
+
 /* ---- CNN block tail: BatchNorm2d -> ReLU -> MaxPool2d((1,2)) at model_crnn.py:5-17 (ConvBlock.forward) ---- */
 /* x: the convolution output in channels-last memory order = row-major [rows = B*T*F][C] (bf16 when is_bf16, else
  * fp32); the two frequency bins of a pooling pair are adjacent rows.  pool = 2: MaxPool2d((1,2)); pool = 1: no

@@ -92,6 +92,9 @@ class Config:
     FUSED_LOSS = True           # seld_softmax_mse instead of softmax + mse_loss + autograd
     FUSED_CONV_TAIL = True      # BatchNorm -> ReLU -> MaxPool of the CNN blocks in two HBM passes (csrc/convtail.hip)
     CONV_DGRAD_AS_FORWARD = True  # encoder 3x3 convs: data gradient as a forward conv with transposed, flipped weights
+    FUSED_CONV_WGRAD = True     # encoder 3x3 convs: weight gradient by the HIP split-K MFMA kernel (csrc/convwgrad.hip),
+                                # written straight into the parameter's gradient; shapes it does not cover: the library.
+                                # Part of the _Conv3x3 path: no effect when CONV_DGRAD_AS_FORWARD is off
     FUSED_DWCONV = "auto"       # channels-last Conformer conv module with the HIP depthwise Conv1d (csrc/dwconv.hip):
                                 # fewer GPU microseconds but more host work; "auto" = always under GRAPH_STEP (no host work
                                 # per iteration), else modules with d_model >= 512 (eager: +3 % on the ResNet50-Conformer,

@@ -1,0 +1,300 @@
+// Weight gradient of the encoder's 3x3 / stride 1 / pad 1 / bias-free convolutions (model_crnn.py:5-17, ConvBlock.conv;
+// the Conformer's encoder is the same code) on channels-last bf16 activations.
+//
+//   dW[co][r][s][ci] = sum over (b, t, f) of dy[b][t][f][co] * x[b][t + r - 1][f + s - 1][ci]   (zero outside the map)
+//
+// is a GEMM with M = Cout, N = 9 * Cin and a very long K = B * T * F.  The library's solvers reach 70-620 TFLOP/s on the
+// encoder's shapes and finish with a split-K that adds with atomics into a zero-filled fp32 workspace, then a cast and
+// a copy.  Here:
+//
+//   * a workgroup (4 waves, 2 x 2) owns a 64-co x 64-ci tile for all nine taps and a K slab: a run of chunks, a chunk
+//     being kWgKc positions = TC consecutive time rows of one clip.  Per chunk it stages dy [kWgKc][64 co] and the x
+//     rows t0-1 .. t0+TC with zero rows outside [0, T) and a zero column on each frequency edge, [TC+2][F+2][64 ci],
+//     in LDS once; the nine taps are nine shifted views of that x image (a constant row offset per tap).
+//   * both operands are position-major in memory (channels innermost), so the MFMA fragments, 8 positions of one
+//     channel, come from ds_read_b64_tr_b16.  A K-group of 32 positions is read as two 4-row halves; the MFMA's k
+//     numbering is a free relabelling of positions as long as both operands use the same one, so lanes 16g..16g+15
+//     take positions 4g..4g+3 and 16+4g..16+4g+3: a 32-lane half then reads 8 consecutive LDS rows, which the 160-byte
+//     row pitch spreads over all 64 banks (conflict-free).
+//   * v_mfma_f32_16x16x32_bf16, fp32 accumulators for 9 taps x 2 x 2 tiles per wave (144 registers).
+//   * two workgroups per CU (at most 254 of the 256 registers, no scratch): one stages while the other multiplies.  A
+//     register prefetch of the next chunk does not fit beside the 144 accumulators (it spills).
+//   * each K slab writes its fp32 partial tile to its own workspace slot once (no atomics, no memset); a second launch
+//     adds the slots in a fixed order (conv3x3_wgrad_sum_kernel) and rounds once into dW in the parameter's own layout
+//     ([Cout][3][3][Cin]) and dtype.  Deterministic: the same inputs give the same bits on every call.
+#include <hip/hip_bf16.h>
+
+#include "seld_common.h"
+
+namespace seld {
+
+namespace {
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(8))) short s16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+
+constexpr int kWgThreads = 256;
+constexpr int kWgTile = 64;          // output channels and input channels per workgroup
+constexpr int kWgKc = 128;           // positions per staged chunk
+constexpr int kWgPitch = 80;         // LDS row pitch in bf16: 64 channels + 16 pad = 160 B
+constexpr int kWgSumThreads = 256;
+constexpr int kWgSumRows = 8;        // slab subsets per element of the fixed-order sum
+
+template <int F>
+struct WgradGeom {
+  static_assert(F == 8 || F == 16 || F == 32, "frequency bins: 8, 16 or 32");
+  static constexpr int TC = kWgKc / F;                       // time rows per chunk
+  static constexpr int XR = (TC + 2) * (F + 2);              // x image rows (with halo rows and edge columns)
+  static constexpr int kDyLoads = kWgKc * 8 / kWgThreads;    // 16-byte pieces per thread
+  static constexpr int kXLoads = (XR * 8 + kWgThreads - 1) / kWgThreads;
+  static constexpr int kLdsShorts = (kWgKc + XR) * kWgPitch;
+  static_assert(kLdsShorts * 2 <= 64 * 1024, "LDS image larger than the default limit");
+};
+
+// x image row of position `pos` of the chunk (tap (1, 1), i.e. no shift)
+template <int F>
+__device__ __forceinline__ int x_row(int pos) {
+  return (pos / F + 1) * (F + 2) + pos % F + 1;
+}
+
+__device__ __forceinline__ s16x4 tr_read(const unsigned short* base, int offset_shorts) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + offset_shorts));
+}
+
+__device__ __forceinline__ bf16x8 join(s16x4 lo, s16x4 hi) {
+  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+template <int F>
+__global__ __launch_bounds__(kWgThreads, 2) void conv3x3_wgrad_kernel(
+    const unsigned short* __restrict__ x, const unsigned short* __restrict__ dy, int T, int Cin, int Cout,
+    int chunks_per_clip, int chunks, int per_slab, float* __restrict__ ws) {
+  using G = WgradGeom<F>;
+  __shared__ __attribute__((aligned(16))) unsigned short lds[G::kLdsShorts];
+  unsigned short* const ldy = lds;
+  unsigned short* const lx = lds + kWgKc * kWgPitch;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int ci0 = blockIdx.x * kWgTile, co0 = blockIdx.y * kWgTile;
+  const int c_begin = blockIdx.z * per_slab;
+  const int c_end = min(c_begin + per_slab, chunks);
+
+  f32x4 acc[9][2][2];
+#pragma unroll
+  for (int k = 0; k < 9; ++k)
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) acc[k][m][n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  // lane 4q+p of the 16-lane group g supplies row q, columns 4p..4p+3 of its 4-row block (ds_read_b64_tr_b16)
+  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+  const int lpos = 4 * g + q;                                   // position of the lane's row in the first half
+  const int a_col = wm * 32 + 4 * p, b_col = wn * 32 + 4 * p;
+
+  uint4 rdy[G::kDyLoads], rx[G::kXLoads];
+  auto load = [&](int c) {
+    const int b = c / chunks_per_clip, t0 = (c - b * chunks_per_clip) * G::TC;
+    const long clip_row = static_cast<long>(b) * T;
+#pragma unroll
+    for (int i = 0; i < G::kDyLoads; ++i) {
+      const int piece = tid + i * kWgThreads, pos = piece >> 3, ch = piece & 7;
+      const int t = t0 + pos / F;
+      rdy[i] = make_uint4(0u, 0u, 0u, 0u);
+      if (t < T)
+        rdy[i] = *reinterpret_cast<const uint4*>(dy + ((clip_row + t) * F + pos % F) * Cout + co0 + ch * 8);
+    }
+#pragma unroll
+    for (int i = 0; i < G::kXLoads; ++i) {
+      const int piece = tid + i * kWgThreads, r = piece >> 3, ch = piece & 7;
+      const int tr = r / (F + 2), f = r - tr * (F + 2) - 1, t = t0 - 1 + tr;
+      rx[i] = make_uint4(0u, 0u, 0u, 0u);
+      if (r < G::XR && t >= 0 && t < T && f >= 0 && f < F)
+        rx[i] = *reinterpret_cast<const uint4*>(x + ((clip_row + t) * F + f) * Cin + ci0 + ch * 8);
+    }
+  };
+
+  for (int c = c_begin; c < c_end; ++c) {
+    load(c);                                                    // in flight while the other waves finish chunk c-1
+    __syncthreads();                                            // the previous chunk's fragment reads are done
+#pragma unroll
+    for (int i = 0; i < G::kDyLoads; ++i) {
+      const int piece = tid + i * kWgThreads;
+      *reinterpret_cast<uint4*>(ldy + (piece >> 3) * kWgPitch + (piece & 7) * 8) = rdy[i];
+    }
+#pragma unroll
+    for (int i = 0; i < G::kXLoads; ++i) {
+      const int piece = tid + i * kWgThreads;
+      if (piece < G::XR * 8) *reinterpret_cast<uint4*>(lx + (piece >> 3) * kWgPitch + (piece & 7) * 8) = rx[i];
+    }
+    __syncthreads();
+
+#pragma unroll
+    for (int ks = 0; ks < kWgKc / 32; ++ks) {
+      const int pos_lo = ks * 32 + lpos, pos_hi = pos_lo + 16;
+      bf16x8 a[2];
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+        a[m] = join(tr_read(ldy, pos_lo * kWgPitch + a_col + m * 16), tr_read(ldy, pos_hi * kWgPitch + a_col + m * 16));
+      const int xr_lo = x_row<F>(pos_lo), xr_hi = x_row<F>(pos_hi);
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const int shift = (tap / 3 - 1) * (F + 2) + (tap % 3 - 1);
+        bf16x8 bfr[2];
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+          bfr[n] = join(tr_read(lx, (xr_lo + shift) * kWgPitch + b_col + n * 16),
+                        tr_read(lx, (xr_hi + shift) * kWgPitch + b_col + n * 16));
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int n = 0; n < 2; ++n)
+            acc[tap][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m], bfr[n], acc[tap][m][n], 0, 0, 0);
+      }
+    }
+  }
+
+  // C/D of the 16x16 tile: column (ci) = lane & 15, rows (co) = 4 * (lane >> 4) + j
+  float* const slot = ws + static_cast<long>(blockIdx.z) * Cout * 9 * Cin;
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int co = co0 + wm * 32 + m * 16 + 4 * (lane >> 4) + j;
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+          slot[(static_cast<long>(co) * 9 + tap) * Cin + ci0 + wn * 32 + n * 16 + (lane & 15)] = acc[tap][m][n][j];
+    }
+}
+
+// dw[i] = round(sum over s of ws[s][i]) in a fixed order: thread row r of the workgroup adds slabs r, r + 8, r + 16, ...
+// of 4 consecutive elements (count % 4 == 0), then row 0 adds the 8 row sums in row order.  Eight rows in flight per
+// column: the small-tile shapes have up to 256 slabs over few elements (a single thread per element there is a
+// latency-bound walk: 68 us for 64->128 channels).
+template <bool kBf16>
+__global__ __launch_bounds__(kWgSumThreads) void conv3x3_wgrad_sum_kernel(const float* __restrict__ ws, int slabs,
+                                                                           long count, void* __restrict__ dw) {
+  constexpr int kCols = kWgSumThreads / kWgSumRows;
+  __shared__ float4 part[kWgSumRows][kCols];
+  const int col = threadIdx.x % kCols, row = threadIdx.x / kCols;
+  const long i = (static_cast<long>(blockIdx.x) * kCols + col) * 4;
+  float4 s = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (i < count)
+    for (int k = row; k < slabs; k += kWgSumRows) {
+      const float4 v = *reinterpret_cast<const float4*>(ws + static_cast<long>(k) * count + i);
+      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+  part[row][col] = s;
+  __syncthreads();
+  if (row != 0 || i >= count) return;
+#pragma unroll
+  for (int r = 1; r < kWgSumRows; ++r) {
+    const float4 v = part[r][col];
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  if (kBf16) {
+    const unsigned lo = static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(s.x))) |
+                        (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(s.y))) << 16);
+    const unsigned hi = static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(s.z))) |
+                        (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(s.w))) << 16);
+    *reinterpret_cast<uint2*>(static_cast<unsigned short*>(dw) + i) = make_uint2(lo, hi);
+  } else {
+    *reinterpret_cast<float4*>(static_cast<float*>(dw) + i) = s;
+  }
+}
+
+struct WgradPlan {
+  int chunks_per_clip = 0, chunks = 0, per_slab = 0, slabs = 0;
+};
+
+int time_rows_per_chunk(int64_t F) { return static_cast<int>(kWgKc / F); }
+
+bool wgrad_supported(int64_t F, int64_t Cin, int64_t Cout) {
+  return (F == 8 || F == 16 || F == 32) && Cin > 0 && Cout > 0 && Cin % kWgTile == 0 &&
+         Cout % kWgTile == 0;
+}
+
+// K slabs: enough workgroups for two per CU, each slab at least one chunk
+WgradPlan wgrad_plan(int64_t B, int64_t T, int64_t F, int64_t Cin, int64_t Cout, int num_cus) {
+  WgradPlan pl;
+  const int tc = time_rows_per_chunk(F);
+  pl.chunks_per_clip = static_cast<int>((T + tc - 1) / tc);
+  pl.chunks = static_cast<int>(B) * pl.chunks_per_clip;
+  const long tiles = (Cin / kWgTile) * (Cout / kWgTile);
+  const long want = (2L * (num_cus > 0 ? num_cus : 256) + tiles - 1) / tiles;
+  const long slabs = want < 1 ? 1 : (want > pl.chunks ? pl.chunks : want);
+  pl.per_slab = static_cast<int>((pl.chunks + slabs - 1) / slabs);
+  pl.slabs = (pl.chunks + pl.per_slab - 1) / pl.per_slab;
+  return pl;
+}
+
+template <int F>
+void launch_wgrad(const unsigned short* x, const unsigned short* dy, int T, int Cin, int Cout, const WgradPlan& pl,
+                  float* ws, hipStream_t stream) {
+  const dim3 grid(static_cast<unsigned>(Cin / kWgTile), static_cast<unsigned>(Cout / kWgTile),
+                  static_cast<unsigned>(pl.slabs));
+  hipLaunchKernelGGL(conv3x3_wgrad_kernel<F>, grid, dim3(kWgThreads), 0, stream, x, dy, T, Cin, Cout,
+                     pl.chunks_per_clip, pl.chunks, pl.per_slab, ws);
+}
+
+}  // namespace
+
+}  // namespace seld
+
+extern "C" {
+
+int seld_conv3x3_wgrad_supported(int64_t F, int64_t Cin, int64_t Cout) {
+  return seld::wgrad_supported(F, Cin, Cout) ? 1 : 0;
+}
+
+int64_t seld_conv3x3_wgrad_workspace_floats(int64_t B, int64_t T, int64_t F, int64_t Cin, int64_t Cout) {
+  using namespace seld;
+  const DeviceState* st = current_state();
+  if (!st || B <= 0 || T <= 0 || !wgrad_supported(F, Cin, Cout)) return 0;
+  return static_cast<int64_t>(wgrad_plan(B, T, F, Cin, Cout, st->num_cus).slabs) * Cout * 9 * Cin;
+}
+
+int seld_conv3x3_wgrad(const void* x, const void* dy, int64_t B, int64_t T, int64_t F, int64_t Cin, int64_t Cout,
+                       void* dw, int dw_is_bf16, float* workspace, void* stream_) {
+  using namespace seld;
+  const DeviceState* st = current_state();
+  if (!st) return kErrNotInitialised;
+  if (!x || !dy || !dw || !workspace || B <= 0 || T <= 0)
+    return fail(kErrInvalidArgument, "seld_conv3x3_wgrad: bad argument");
+  if (!wgrad_supported(F, Cin, Cout))
+    return fail(kErrUnsupported, "seld_conv3x3_wgrad: F in {8, 16, 32} and channel counts % 64 == 0 required");
+  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dw) |
+        reinterpret_cast<uintptr_t>(workspace)) & 15) != 0)
+    return fail(kErrInvalidArgument, "seld_conv3x3_wgrad: 16-byte aligned tensors required");
+  const WgradPlan pl = wgrad_plan(B, T, F, Cin, Cout, st->num_cus);
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const unsigned short* xs = static_cast<const unsigned short*>(x);
+  const unsigned short* ds = static_cast<const unsigned short*>(dy);
+  const int t = static_cast<int>(T), ci = static_cast<int>(Cin), co = static_cast<int>(Cout);
+  switch (F) {
+    case 8: launch_wgrad<8>(xs, ds, t, ci, co, pl, workspace, stream); break;
+    case 16: launch_wgrad<16>(xs, ds, t, ci, co, pl, workspace, stream); break;
+    default: launch_wgrad<32>(xs, ds, t, ci, co, pl, workspace, stream); break;
+  }
+  SELD_HIP_TRY(hipGetLastError());
+  const long count = static_cast<long>(Cout) * 9 * Cin;
+  const long cols = kWgSumThreads / kWgSumRows;
+  const dim3 grid(static_cast<unsigned>((count / 4 + cols - 1) / cols));
+  if (dw_is_bf16)
+    hipLaunchKernelGGL(conv3x3_wgrad_sum_kernel<true>, grid, dim3(kWgSumThreads), 0, stream, workspace, pl.slabs,
+                       count, dw);
+  else
+    hipLaunchKernelGGL(conv3x3_wgrad_sum_kernel<false>, grid, dim3(kWgSumThreads), 0, stream, workspace, pl.slabs,
+                       count, dw);
+  SELD_HIP_TRY(hipGetLastError());
+  return kOk;
+}
+
+}  // extern "C"

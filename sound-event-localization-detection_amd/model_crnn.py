@@ -25,6 +25,7 @@ class _Conv3x3(torch.autograd.Function):
     256->512 channels 219 -> 170 us, 128->256 130 -> 115 us, 64->128 100 -> 87 us including the weight transform)."""
 
     enabled = True
+    fused_wgrad = True          # weight gradient by csrc/convwgrad.hip where it applies (config.FUSED_CONV_WGRAD)
 
     @staticmethod
     def forward(ctx, x, weight):
@@ -57,15 +58,23 @@ class _Conv3x3(torch.autograd.Function):
                 if dx.dtype != x_dtype:
                     dx = dx.to(x_dtype)
             import seld_overlap
+            import seld_native
+            # the HIP kernel writes dW straight into the gradient's layout and dtype (no cast, no copy, no atomics)
+            fused = _Conv3x3.fused_wgrad and seld_native.conv3x3_wgrad_applicable(xc, dy, wc)
             if seld_overlap.conv_wgrad_side and seld_overlap.enabled:
                 # side stream, beside the rest of the data-gradient chain (seld_overlap.launch_now); the stepper joins
                 dw = torch.empty_like(wc, dtype=w_dtype)
 
                 def job():
+                    if fused:
+                        seld_native.conv3x3_wgrad(xc, dy, dw)     # its workspace: the caching allocator, side stream
+                        return
                     dw.copy_(torch.ops.aten.convolution_backward(dy, xc, wc, None, (1, 1), (1, 1), (1, 1), False, (0, 0),
                                                                  1, (False, True, False))[1])
                 seld_overlap.launch_now(dy.device, [dy, xc, wc, dw], job, last_of_stage=ctx.after_cut, outputs=[dw], hold=True)
                 return dx, dw.view_as(dw)          # a fresh alias: autograd takes it over instead of cloning (seld_overlap)
+            if fused:
+                return dx, seld_native.conv3x3_wgrad(xc, dy, torch.empty_like(wc, dtype=w_dtype))
             dw = torch.ops.aten.convolution_backward(dy, xc, wc, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
                                                      (False, True, False))[1]
         return dx, dw if dw.dtype == w_dtype else dw.to(w_dtype)

@@ -94,6 +94,10 @@ def _declare(lib):
     lib.seld_column_sums_blocks.argtypes = [_i64, _i64]
     lib.seld_column_sums_blocks.restype = ctypes.c_int64
     lib.seld_conv_weight_flip_transpose.argtypes = [_ptr, _int, _i64, _i64, _ptr, _ptr]
+    lib.seld_conv3x3_wgrad_supported.argtypes = [_i64, _i64, _i64]
+    lib.seld_conv3x3_wgrad_workspace_floats.restype = _i64
+    lib.seld_conv3x3_wgrad_workspace_floats.argtypes = [_i64, _i64, _i64, _i64, _i64]
+    lib.seld_conv3x3_wgrad.argtypes = [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _int, _ptr, _ptr]
     lib.seld_layernorm_supported.argtypes = [_i64]
     lib.seld_layernorm_workspace_floats.restype = _i64
     lib.seld_layernorm_workspace_floats.argtypes = [_i64, _i64]
@@ -998,6 +1002,40 @@ def conv_weight_flip_transpose(w: torch.Tensor) -> torch.Tensor:
         check(load_library().seld_conv_weight_flip_transpose(_p(w), w.element_size(), o, i, _p(wt),
                                                              _stream_ptr(w.device)), "seld_conv_weight_flip_transpose")
     return wt
+
+
+def conv3x3_wgrad_applicable(x: torch.Tensor, dy: torch.Tensor, w: torch.Tensor) -> bool:
+    """True when ``conv3x3_wgrad`` covers this 3x3 / stride 1 / pad 1 convolution: bf16 x [B, Cin, T, F] and
+    dy [B, Cout, T, F] in channels-last memory, F in {8, 16, 32}, channel counts multiples of 64, and weights
+    [Cout, Cin, 3, 3] in channels-last memory (the gradient is written in that layout)."""
+    if not (x.is_cuda and x.dim() == 4 and dy.dim() == 4 and w.dim() == 4 and x.dtype == torch.bfloat16
+            and dy.dtype == torch.bfloat16 and tuple(w.shape[2:]) == (3, 3)):
+        return False
+    b, cin, t, f = x.shape
+    if tuple(dy.shape) != (b, w.shape[0], t, f) or w.shape[1] != cin:
+        return False
+    if not (x.is_contiguous(memory_format=torch.channels_last) and dy.is_contiguous(memory_format=torch.channels_last)
+            and w.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    return bool(load_library().seld_conv3x3_wgrad_supported(f, cin, w.shape[0]))
+
+
+def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor) -> torch.Tensor:
+    """dw [Cout, Cin, 3, 3] (channels-last memory, bf16 or fp32) = the weight gradient of a 3x3 / stride 1 / pad 1
+    bias-free convolution with input x and output gradient dy (both bf16, channels-last; ``conv3x3_wgrad_applicable``).
+    fp32 accumulation, one rounding; deterministic.  The fp32 workspace comes from the caching allocator on the
+    current stream."""
+    if not conv3x3_wgrad_applicable(x, dy, dw) or dw.dtype not in (torch.float32, torch.bfloat16):
+        raise SeldNativeError("conv3x3_wgrad: unsupported shapes, dtypes or layouts")
+    b, cin, t, f = x.shape
+    cout = dy.shape[1]
+    with _device_guard(ensure_init(x.device)):
+        lib = load_library()
+        ws = torch.empty(int(lib.seld_conv3x3_wgrad_workspace_floats(b, t, f, cin, cout)), dtype=torch.float32,
+                         device=x.device)
+        check(lib.seld_conv3x3_wgrad(_p(x), _p(dy), b, t, f, cin, cout, _p(dw), _is_bf16(dw), _p(ws),
+                                     _stream_ptr(x.device)), "seld_conv3x3_wgrad")
+    return dw
 
 
 # --------------------------------------------------------------------------- STFT / spatial features
