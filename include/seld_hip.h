@@ -372,6 +372,38 @@ int seld_gru_from_pair_tile(const void* dg_tile, int elem_bytes, int64_t B, int6
  * accumulates step by step). */
 int seld_gru_previous_state(const void* y, int elem_bytes, int64_t B, int64_t T, void* h_prev, void* stream);
 
+/* ---- evaluation: spatial grid maps -> DOA events, location-aware matching (csrc/seld_eval.hip) -----------------
+ * No reference counterpart (its test_model, trainer.py:394-711, reports argmax accuracy per cell); the definitions are
+ * this project's, DESIGN.md section 10.  Grid 18 x 36 (cell = i*36 + j), 14 classes (13 = background), windows of 250
+ * frames with hop 50 over a timeline of `total` frames: W = ceil(total / 50) windows, window w starts at frame 50 w.
+ *
+ * seld_grid_decode: logits [nw][250][648][14] (bf16 when is_bf16, else fp32; 16-byte aligned) hold windows
+ * [w0, w0+nw).  meta_first int64 / meta_len int32 [Q] (device) give the first global frame and the frame count (1..5)
+ * of every meta-frame of the timeline.  Meta-frames [q0, q0+nq) are decoded:
+ *   P_q[cell][c] = mean over the frames f of q (ascending) of the mean over the windows covering f (ascending w) of
+ *   softmax(logits[w][f - 50 w][cell][:])[c], fp32;  a detection is a cell whose P_q >= threshold and that beats its
+ *   8 neighbours (azimuth wraps, no wrap over the poles; equal scores: the lower cell wins), the first K (1..8) of them
+ *   by (score descending, cell ascending).
+ * Outputs, row qi = q - q0:  det_cell int32 [nq][13][K] (-1 past the count), det_score f32 [nq][13][K] (0 past the
+ * count), det_count int32 [nq][13]; probs_out f32 [nq][648][13] = P_q, or NULL.  One workgroup per meta-frame, fixed
+ * summation order: bit-identical however the meta-frames are split across calls.
+ * Every window that covers a requested meta-frame must be in the call: the check needs the tables' values, so the
+ * host does it on its own copy (seld_native.grid_decode raises before launching); the kernel itself writes nothing
+ * for a meta-frame whose windows are not all present. */
+int seld_grid_decode(const void* logits, int is_bf16, int64_t w0, int64_t nw, int64_t W, int64_t total,
+                     const int64_t* meta_first, const int32_t* meta_len, int64_t q0, int64_t nq, float threshold, int K,
+                     int32_t* det_cell, float* det_score, int32_t* det_count, float* probs_out, void* stream);
+
+/* seld_doa_match: one thread per (q, c) of nq meta-frames x 13 classes.  Detections as seld_grid_decode writes them
+ * (det_cell [nq][13][K], det_count [nq][13]; DOA = the cell centre az = -180 + (j + 1/2) 360/J,
+ * el = -90 + (i + 1/2) 180/I); references: CSR ref_offsets int32 [nq*13 + 1] over ref_dirs int32 [R][2] = (azimuth,
+ * elevation) degrees, at most 8 per (q, c) (the host checks).  With d the float64 great-circle angle in degrees:
+ *   stats int32 [nq][13][4] = (R, P, k = min(R, P), tp = size of a maximum matching among pairs with d <= thr_deg),
+ *   cost f64 [nq][13] = minimum total d over injective assignments of size k (0 when k = 0). */
+int seld_doa_match(const int32_t* det_cell, const int32_t* det_count, int K, const int32_t* ref_offsets,
+                   const int32_t* ref_dirs, int64_t nq, int I, int J, double thr_deg, int32_t* stats, double* cost,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,10 @@ class Config:
     GAUSSIAN_AUGMENT = False    # smrl_seld_gaussian.py:397-534 label augmentation (+-2 sigma box per source)
     GAUSSIAN_SIGMA_AZIMUTH = 5.0
     GAUSSIAN_SIGMA_ELEVATION = 5.0
+    # SELD evaluation (seld_eval.py, trainer.evaluate_seld, infer.py)
+    SELD_THRESHOLD = 0.5        # a grid cell is a detection when its meta-frame probability reaches this and beats its 8 neighbours
+    SELD_MAX_PEAKS = 4          # detections kept per (100 ms meta-frame, class), 1..8
+    SELD_DOA_THRESHOLD_DEG = 20  # a detection matches a reference within this great-circle angle (F20 / ER20)
 
     def __init__(self):
         for folder in (self.OUTPUT_PATH, self.CHECKPOINT_PATH):

@@ -316,7 +316,7 @@ class SELDDataset(Dataset):
         return spec[:frames], mask[:frames]
 
     def _build_timeline(self):
-        specs, masks = [], []
+        specs, masks, rows = [], [], []
         for idx, (audio_path, metadata_path) in enumerate(zip(self.audio_files, self.metadata_files)):
             try:
                 spec, mask = self._file_features(audio_path, metadata_path)
@@ -325,7 +325,18 @@ class SELDDataset(Dataset):
                 raise
             specs.append(spec)
             masks.append(mask)
+            rows.append(_read_metadata_rows(metadata_path))
+        self._set_segments([int(s.shape[0]) for s in specs], rows)
         self._set_timeline(torch.cat(specs, dim=0), torch.cat(masks, dim=0))
+
+    def _set_segments(self, frame_counts, rows):
+        """Evaluation bookkeeping (seld_eval.py): ``segments`` int64 [n_files, 2] = (first frame, cropped frame count) of
+        every file on the timeline; ``metadata_rows`` the files' CSV rows as read, int64 [R, 5] each (not the
+        Gaussian-augmented labels)."""
+        counts = np.asarray(frame_counts, dtype=np.int64)
+        self.segments = np.stack([np.cumsum(counts) - counts, counts], axis=1).reshape(-1, 2)
+        self.metadata_rows = [np.asarray(r, dtype=np.int64).reshape(len(r), -1)[:, :5].copy() if len(r)
+                              else np.zeros((0, 5), dtype=np.int64) for r in rows]
 
     def _set_timeline(self, spec_tm, mask_tm):
         self.spec_tm = spec_tm.contiguous()            # [total, C, 64] float32 (device)
@@ -354,11 +365,13 @@ class SELDDataset(Dataset):
         SELDDataset._init_fields(self, num_classes, device)
         if use_gaussian_augmentation is not None:
             self.use_gaussian_augmentation = bool(use_gaussian_augmentation)
-        specs, masks = [], []
+        specs, masks, kept = [], [], []
         for pcm, rows in zip(clips, metadata_rows):
             spec, mask = self._features_from_pcm(pcm.to(self.device), sample_rate, np.asarray(rows))
             specs.append(spec)
             masks.append(mask)
+            kept.append(np.asarray(rows))
+        self._set_segments([int(s.shape[0]) for s in specs], kept)
         self._set_timeline(torch.cat(specs, dim=0), torch.cat(masks, dim=0))
         self._build_window_table()
         return self

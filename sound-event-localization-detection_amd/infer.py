@@ -1,0 +1,75 @@
+"""Inference CLI: recordings -> SELD event CSVs, one per recording (no reference counterpart).
+
+    python infer.py --checkpoint best_model.pth --out-dir DIR a.wav [b.wav ...]
+
+Each recording becomes a one-segment timeline (features through the dataset's own path, no metadata rows), its 5 s
+windows run through the checkpoint's model in timeline order, and the decoded events are written to DIR/<stem>.csv as
+``meta_frame,class,rank,azimuth,elevation`` rows -- the metadata format the dataset reads.
+"""
+import argparse
+import logging
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+
+import dataset  # noqa: E402
+import seld_eval  # noqa: E402
+import trainer  # noqa: E402
+from utils import safe_torch_load  # noqa: E402
+
+
+def parse_args(argv=None):
+    cfg = trainer.config
+    p = argparse.ArgumentParser(description="Decode SELD events from WAV recordings with a trained checkpoint.")
+    p.add_argument("--checkpoint", required=True, help="checkpoint written by train_model (e.g. best_model.pth)")
+    p.add_argument("--out-dir", required=True, help="directory for the event CSVs")
+    p.add_argument("--model-type", default=None, help="model kind; default: the checkpoint's Config, else Config.MODEL_TYPE")
+    p.add_argument("--batch-size", type=int, default=cfg.BATCH_SIZE)
+    p.add_argument("--threshold", type=float, default=cfg.SELD_THRESHOLD)
+    p.add_argument("--max-peaks", type=int, default=cfg.SELD_MAX_PEAKS)
+    p.add_argument("--device", default=None, help="default: the current ROCm device")
+    p.add_argument("wavs", nargs="+", help="PCM WAV recordings (24 kHz)")
+    return p.parse_args(argv)
+
+
+def _pcm(path):
+    data, rate, bits = dataset._read_wav(path)
+    if bits == 16:
+        return torch.from_numpy(data), rate                     # int16 straight into the feature kernel
+    return torch.from_numpy(data.astype(np.float32) / float(1 << (bits - 1))), rate
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    device = torch.device(args.device) if args.device else dataset._compute_device()
+    checkpoint = safe_torch_load(args.checkpoint, map_location=device)
+    model_type = args.model_type or getattr(checkpoint.get("config"), "MODEL_TYPE", None)
+    if model_type:
+        trainer.config.MODEL_TYPE = model_type
+    model = None
+    written = []
+    for wav in args.wavs:
+        pcm, rate = _pcm(wav)
+        ds = dataset.SELDDataset.from_pcm([pcm], [np.zeros((0, 5), dtype=np.int64)], sample_rate=rate, device=device,
+                                          use_gaussian_augmentation=False)
+        if model is None:
+            model = trainer.prepare_model_for_device(trainer.build_model((ds.I, ds.J), True, n_channels=ds.n_channels),
+                                                     device)
+            model.load_state_dict(checkpoint["model_state_dict"])
+            model.eval()
+        result = seld_eval.evaluate_logits(trainer.timeline_logits(model, ds, args.batch_size, device), ds,
+                                           threshold=args.threshold, max_peaks=args.max_peaks, events_dir=args.out_dir,
+                                           names=[Path(wav).stem])
+        path = result["event_files"][0]
+        written.append(path)
+        print(f"{wav}: {result['FP']} events -> {path}")
+    return written
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,324 @@
+"""SELD evaluation: the model's spatial grid maps -> DOA events, and the location-aware metrics F20 / ER20 / LE_CD / LR_CD.
+
+The reference has no such code (its test_model, trainer.py:394-711, reports argmax accuracy per grid cell); the
+definitions are this project's, DESIGN.md section 10.  The hot paths are two HIP kernels (csrc/seld_eval.hip):
+
+  seld_grid_decode   one streaming pass over the logits: softmax per cell, mean over the overlapping windows and over
+                     the frames of each 100 ms meta-frame, 3x3 peak test per class, top-K per (meta-frame, class)
+  seld_doa_match     per (meta-frame, class): minimum-cost assignment and maximum matching within the DOA threshold
+
+The host side here builds the tables (meta-frames, reference CSR), drives the decode batch by batch as the windows are
+computed, reduces the match counts on the device and writes event CSVs.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from seld_native import SeldNativeError, _device_guard, _p, _stream_ptr, check, ensure_init, load_library
+
+WIN = 250                  # frames per window (config.WINDOW_LENGTH / SPECTROGRAM_HOP_LENGTH)
+HOP = 50                   # frames between window starts (config.HOP_LENGTH / SPECTROGRAM_HOP_LENGTH)
+FRAMES_PER_META = 5        # 100 ms meta-frame / 20 ms label frame (dataset.py:100-103)
+NUM_EVENT_CLASSES = 13     # class 13 is the background
+GRID_I, GRID_J = 18, 36
+MAX_PEAKS = 8              # K limit of the decode kernel
+MAX_REFS = 8               # references per (meta-frame, class) the match kernel enumerates
+DOA_MARGIN_DEG = 1e-6      # a pair counts within the threshold when d <= threshold + 1e-6 degrees
+# Windows kept from one decode call to the next.  A meta-frame needs every window that covers one of its frames: up to
+# five per frame, and six when its frames straddle a window start (frames 50 k - 1 and 50 k).  Its last covering window
+# is in the current batch, so the five before the batch are enough.
+KEEP_WINDOWS = 5
+
+
+# ------------------------------------------------------------------------------------------------------ meta-frames
+
+class MetaFrameTable:
+    """Every meta-frame of a timeline, in timeline order.  Host arrays (int64 unless noted), length Q:
+    ``first`` global first frame, ``length`` frame count (int32, 1..5), ``segment`` segment index (int32), ``index`` the
+    meta-frame number m within its segment, ``first_window`` / ``last_window`` the windows covering its first / last
+    frame; ``seg_offsets`` [S + 1]: the meta-frames of segment s are ``seg_offsets[s]:seg_offsets[s + 1]``.
+    ``total`` frames on the timeline, ``windows`` = ceil(total / 50)."""
+
+    def __init__(self, segments, total=None):
+        seg = np.asarray(segments, dtype=np.int64).reshape(-1, 2)
+        if (seg < 0).any():
+            raise ValueError("segments must be (first_frame >= 0, n_frames >= 0)")
+        counts = (seg[:, 1] + FRAMES_PER_META - 1) // FRAMES_PER_META          # ceil(n / 5) meta-frames per segment
+        self.seg_offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        self.segment = np.repeat(np.arange(len(seg), dtype=np.int32), counts)
+        self.index = np.arange(int(self.seg_offsets[-1]), dtype=np.int64) - self.seg_offsets[:-1][self.segment]
+        starts = FRAMES_PER_META * self.index
+        self.first = seg[self.segment, 0] + starts
+        self.length = np.minimum(FRAMES_PER_META, seg[self.segment, 1] - starts).astype(np.int32)
+        self.segments = seg
+        end = int((seg[:, 0] + seg[:, 1]).max()) if len(seg) else 0
+        self.total = end if total is None else int(total)
+        if self.total < end:
+            raise ValueError(f"segments reach frame {end}, beyond the timeline's {self.total}")
+        self.windows = (self.total + HOP - 1) // HOP
+        last = self.first + self.length - 1
+        self.first_window = np.where(self.first < WIN, 0, (self.first - WIN) // HOP + 1)
+        self.last_window = np.minimum(last // HOP, self.windows - 1)
+        if (np.diff(self.last_window) < 0).any():
+            raise ValueError("segments must be in timeline order")
+        self._device = {}
+
+    def __len__(self):
+        return int(self.first.shape[0])
+
+    def device(self, device):
+        """(first int64 [Q], length int32 [Q]) on ``device``, uploaded once."""
+        key = str(device)
+        if key not in self._device:
+            self._device[key] = (torch.from_numpy(self.first.copy()).to(device),
+                                 torch.from_numpy(self.length.copy()).to(device))
+        return self._device[key]
+
+
+def meta_frame_table(segments, total=None) -> MetaFrameTable:
+    """Segments (first_frame, n_frames) int [S, 2] -> the timeline's meta-frames: meta-frame m of segment s covers frames
+    first + 5m .. first + min(5m + 5, n) - 1, m < ceil(n / 5) (the label rule of dataset.py:100-103)."""
+    return MetaFrameTable(segments, total)
+
+
+# ------------------------------------------------------------------------------------------------------ kernels
+
+def grid_decode(logits: torch.Tensor, w0: int, table: MetaFrameTable, q0: int, nq: int, threshold: float, max_peaks: int,
+                out=None, probs: torch.Tensor | None = None):
+    """seld_grid_decode over meta-frames [q0, q0 + nq) from ``logits`` [nw, 250, 648, 14] (bf16 or fp32, GPU) holding
+    windows [w0, w0 + nw).  ``out``: contiguous (det_cell int32 [nq, 13, K], det_score f32 [nq, 13, K], det_count int32
+    [nq, 13]) to write, else allocated.  ``probs``: f32 [nq, 648, 13] to receive P_q, or None.
+    Raises SeldNativeError, launching nothing, when a window that covers one of the meta-frames is not in ``logits``."""
+    if not logits.is_cuda:
+        raise SeldNativeError("grid_decode: logits must live on the GPU (no CPU fallback)")
+    if logits.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("grid_decode: logits must be bfloat16 or float32")
+    if logits.dim() != 4 or tuple(logits.shape[1:]) != (WIN, GRID_I * GRID_J, NUM_EVENT_CLASSES + 1):
+        raise ValueError(f"grid_decode: logits must be [nw, {WIN}, 648, 14], got {tuple(logits.shape)}")
+    logits = logits.contiguous()
+    nw = int(logits.shape[0])
+    if not (q0 >= 0 and nq >= 0 and q0 + nq <= len(table)):
+        raise ValueError("grid_decode: meta-frame range outside the table")
+    if nq:
+        lo, hi = int(table.first_window[q0:q0 + nq].min()), int(table.last_window[q0:q0 + nq].max())
+        if lo < w0 or hi >= w0 + nw:
+            raise SeldNativeError(f"grid_decode: meta-frames {q0}..{q0 + nq - 1} need windows {lo}..{hi}, the call "
+                                  f"holds {w0}..{w0 + nw - 1}")
+    device = logits.device
+    index = ensure_init(device)
+    k = int(max_peaks)
+    if out is None:
+        out = (torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.int32, device=device),
+               torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.float32, device=device),
+               torch.empty((nq, NUM_EVENT_CLASSES), dtype=torch.int32, device=device))
+    first, length = table.device(device)
+    with _device_guard(index):
+        check(load_library().seld_grid_decode(_p(logits), int(logits.dtype == torch.bfloat16), int(w0), nw,
+                                              table.windows, table.total, _p(first), _p(length), int(q0), int(nq),
+                                              float(threshold), k, _p(out[0]), _p(out[1]), _p(out[2]), _p(probs),
+                                              _stream_ptr(device)), "seld_grid_decode")
+    return out
+
+
+def doa_match(det_cell: torch.Tensor, det_count: torch.Tensor, ref_offsets: torch.Tensor, ref_dirs: torch.Tensor,
+              doa_threshold_deg: float, I: int = GRID_I, J: int = GRID_J):
+    """seld_doa_match: (stats int32 [Q, 13, 4] = (R, P, k, tp), cost f64 [Q, 13]) on the detections' device.  A pair is
+    within the threshold when d <= doa_threshold_deg + DOA_MARGIN_DEG."""
+    device = det_cell.device
+    if not det_cell.is_cuda:
+        raise SeldNativeError("doa_match: detections must live on the GPU (no CPU fallback)")
+    q = int(det_count.shape[0])
+    if ref_offsets.numel() != q * NUM_EVENT_CLASSES + 1:
+        raise ValueError("doa_match: ref_offsets must have Q * 13 + 1 entries")
+    index = ensure_init(device)
+    stats = torch.empty((q, NUM_EVENT_CLASSES, 4), dtype=torch.int32, device=device)
+    cost = torch.empty((q, NUM_EVENT_CLASSES), dtype=torch.float64, device=device)
+    dirs = ref_dirs if ref_dirs.numel() else torch.zeros((1, 2), dtype=torch.int32, device=device)
+    det_cell, det_count = det_cell.contiguous(), det_count.contiguous()
+    ref_offsets, dirs = ref_offsets.to(torch.int32).contiguous(), dirs.to(torch.int32).contiguous()
+    with _device_guard(index):
+        check(load_library().seld_doa_match(_p(det_cell), _p(det_count), int(det_cell.shape[-1]), _p(ref_offsets),
+                                            _p(dirs), q, int(I), int(J), float(doa_threshold_deg) + DOA_MARGIN_DEG,
+                                            _p(stats), _p(cost), _stream_ptr(device)), "seld_doa_match")
+    return stats, cost
+
+
+# ------------------------------------------------------------------------------------------------------ decode driver
+
+def decode(batches, table: MetaFrameTable, threshold: float, max_peaks: int, device=None, keep_probs: bool = False):
+    """Streaming decode of a whole timeline.  ``batches`` yields logit tensors [B, 250, 648, 14] of consecutive windows
+    in timeline order (window 0 first, ``table.windows`` in all).  After each batch every meta-frame whose last
+    covering window has been seen is decoded; the last KEEP_WINDOWS windows stay on the device for the next call.
+    Returns (det_cell int32 [Q, 13, K], det_score f32 [Q, 13, K], det_count int32 [Q, 13], probs f32 [Q, 648, 13] or
+    None) on the device."""
+    k = int(max_peaks)
+    if not 1 <= k <= MAX_PEAKS:
+        raise ValueError(f"max_peaks must be in 1..{MAX_PEAKS}, got {max_peaks}")
+    n_q = len(table)
+    det = probs = carry = None
+    seen = 0                    # windows received so far
+    done = 0                    # meta-frames decoded so far
+    for batch in batches:
+        if device is None:
+            device = batch.device
+        if det is None:
+            det = (torch.empty((n_q, NUM_EVENT_CLASSES, k), dtype=torch.int32, device=device),
+                   torch.empty((n_q, NUM_EVENT_CLASSES, k), dtype=torch.float32, device=device),
+                   torch.empty((n_q, NUM_EVENT_CLASSES), dtype=torch.int32, device=device))
+            if keep_probs:
+                probs = torch.empty((n_q, GRID_I * GRID_J, NUM_EVENT_CLASSES), dtype=torch.float32, device=device)
+        if batch.dtype not in (torch.bfloat16, torch.float32):
+            batch = batch.float()
+        held = batch if carry is None else torch.cat([carry, batch.to(carry.dtype)], dim=0)
+        w0 = seen - (0 if carry is None else int(carry.shape[0]))
+        seen += int(batch.shape[0])
+        end = int(np.searchsorted(table.last_window, seen - 1, side="right"))
+        if end > done:
+            grid_decode(held, w0, table, done, end - done, threshold, k,
+                        out=(det[0][done:end], det[1][done:end], det[2][done:end]),
+                        probs=probs[done:end] if probs is not None else None)
+            done = end
+        carry = held[-KEEP_WINDOWS:]
+    if seen != table.windows or done != n_q:
+        raise ValueError(f"decode: the timeline has {table.windows} windows, got {seen}")
+    if det is None:             # an empty timeline
+        device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        det = (torch.zeros((0, NUM_EVENT_CLASSES, k), dtype=torch.int32, device=device),
+               torch.zeros((0, NUM_EVENT_CLASSES, k), dtype=torch.float32, device=device),
+               torch.zeros((0, NUM_EVENT_CLASSES), dtype=torch.int32, device=device))
+    return det[0], det[1], det[2], probs
+
+
+# ------------------------------------------------------------------------------------------------------ references
+
+def reference_table(table: MetaFrameTable, metadata_rows):
+    """CSR of the references per (meta-frame, class): (offsets int32 [Q * 13 + 1], dirs int32 [R, 2] = (az, el)).
+    Rows of segment s with meta-frame m and class c < 13 land at q = seg_offsets[s] + m; rows with 5 m >= n (outside the
+    cropped segment, as the rasteriser drops them) or negative m are dropped; rows keep their file order inside a (q, c).
+    Raises ValueError when a (q, c) has more than MAX_REFS references."""
+    keys, dirs = [np.zeros(0, np.int64)], [np.zeros((0, 2), np.int64)]
+    for s, rows in enumerate(metadata_rows):
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1, 5) if len(rows) else np.zeros((0, 5), np.int64)
+        n = int(table.segments[s, 1])
+        m, c = rows[:, 0], rows[:, 1]
+        rows = rows[(m >= 0) & (FRAMES_PER_META * m < n) & (c >= 0) & (c < NUM_EVENT_CLASSES)]
+        keys.append((table.seg_offsets[s] + rows[:, 0]) * NUM_EVENT_CLASSES + rows[:, 1])
+        dirs.append(rows[:, 3:5])
+    n_qc = len(table) * NUM_EVENT_CLASSES
+    key, dirs = np.concatenate(keys), np.concatenate(dirs)
+    counts = np.bincount(key, minlength=n_qc)
+    if counts.size and counts.max() > MAX_REFS:
+        bad = int(np.argmax(counts))
+        raise ValueError(f"meta-frame {bad // NUM_EVENT_CLASSES}, class {bad % NUM_EVENT_CLASSES} has {int(counts.max())} "
+                         f"references; the matcher takes at most {MAX_REFS}")
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    order = np.argsort(key, kind="stable")
+    return offsets, np.ascontiguousarray(dirs[order].astype(np.int32)).reshape(-1, 2)
+
+
+# ------------------------------------------------------------------------------------------------------ metrics
+
+def score(stats: torch.Tensor, cost: torch.Tensor) -> dict:
+    """Micro-averaged metrics from the per-(q, c) match results: stats int [Q, 13, 4] = (R, P, k, tp), cost float [Q, 13].
+    Counts are reduced in int64 and the cost in float64 where the tensors live; only the totals and the per-class
+    vectors are copied to the host.  Empty denominators give nan."""
+    st = stats.to(torch.int64)
+    r, p, k, tp = st[..., 0], st[..., 1], st[..., 2], st[..., 3]
+    fn_qc, fp_qc = r - tp, p - tp
+    fn_q, fp_q = fn_qc.sum(1), fp_qc.sum(1)
+    totals = torch.stack([torch.minimum(fn_q, fp_q).sum(), torch.clamp(fn_q - fp_q, min=0).sum(),
+                          torch.clamp(fp_q - fn_q, min=0).sum()])                                  # S, D, I
+    counts = torch.stack([tp.sum(0), fp_qc.sum(0), fn_qc.sum(0), r.sum(0), k.sum(0)])            # [5, 13]
+    cost_c = cost.to(torch.float64).sum(0)
+    counts, totals, cost_c = counts.cpu().numpy(), totals.cpu().numpy(), cost_c.cpu().numpy()
+
+    def div(a, b):
+        return float(a) / float(b) if b else math.nan
+
+    TP, FP, FN, N, K = (int(v) for v in counts.sum(1))
+    S, D, I = (int(v) for v in totals)
+    per_class = {"TP": counts[0].tolist(), "FP": counts[1].tolist(), "FN": counts[2].tolist(), "N": counts[3].tolist(),
+                 "F20": [div(2 * t, 2 * t + f + n) for t, f, n in zip(counts[0], counts[1], counts[2])],
+                 "LE_CD": [div(c, kk) for c, kk in zip(cost_c, counts[4])],
+                 "LR_CD": [div(kk, n) for kk, n in zip(counts[4], counts[3])]}
+    return {"F20": div(2 * TP, 2 * TP + FP + FN), "ER20": div(S + D + I, N), "LE_CD": div(float(cost_c.sum()), K),
+            "LR_CD": div(K, N), "TP": TP, "FP": FP, "FN": FN, "N": N, "S": S, "D": D, "I": I, "matched": K,
+            "per_class": per_class}
+
+
+def match_and_score(det_cell: torch.Tensor, det_count: torch.Tensor, table: MetaFrameTable, metadata_rows,
+                    doa_threshold_deg: float, I: int = GRID_I, J: int = GRID_J) -> dict:
+    """References (numpy CSR) -> seld_doa_match on the detections' device -> score()."""
+    offsets, dirs = reference_table(table, metadata_rows)
+    device = det_cell.device
+    stats, cost = doa_match(det_cell, det_count, torch.from_numpy(offsets).to(device), torch.from_numpy(dirs).to(device),
+                            doa_threshold_deg, I, J)
+    return score(stats, cost)
+
+
+# ------------------------------------------------------------------------------------------------------ events
+
+def events_for_segment(det_cell, det_count, table: MetaFrameTable, segment: int, I: int = GRID_I, J: int = GRID_J):
+    """Event rows of one segment: int32 [R, 5] = (meta_frame, class, rank, azimuth, elevation) in (m, c, rank) order,
+    the DOA being the detection's cell centre (integer degrees on the 10-degree grid)."""
+    lo, hi = int(table.seg_offsets[segment]), int(table.seg_offsets[segment + 1])
+    cells = det_cell[lo:hi].cpu().numpy() if torch.is_tensor(det_cell) else np.asarray(det_cell)[lo:hi]
+    count = det_count[lo:hi].cpu().numpy() if torch.is_tensor(det_count) else np.asarray(det_count)[lo:hi]
+    m, c, rank = np.meshgrid(np.arange(hi - lo), np.arange(NUM_EVENT_CLASSES), np.arange(cells.shape[-1]), indexing="ij")
+    sel = rank < count[..., None]
+    cell = cells[sel].astype(np.int64)
+    az = np.rint(-180.0 + (cell % J + 0.5) * (360.0 / J))
+    el = np.rint(-90.0 + (cell // J + 0.5) * (180.0 / I))
+    return np.stack([m[sel], c[sel], rank[sel], az, el], axis=1).astype(np.int32).reshape(-1, 5)
+
+
+def write_events_csv(path, rows) -> Path:
+    """One ``m,c,rank,az,el`` line per event, the reference's 5-column metadata format (dataset._read_metadata_rows reads
+    it back unchanged)."""
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 5)
+    with open(path, "w", newline="") as fh:
+        fh.writelines(",".join(str(int(v)) for v in row) + "\n" for row in rows)
+    return path
+
+
+def segment_names(dataset):
+    """The audio stems of the dataset's files, or segment0000, segment0001, ... for an in-memory timeline."""
+    files = list(getattr(dataset, "audio_files", None) or [])
+    n = len(dataset.segments)
+    return [Path(f).stem for f in files] if len(files) == n else [f"segment{s:04d}" for s in range(n)]
+
+
+# ------------------------------------------------------------------------------------------------------ entry point
+
+def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_threshold_deg=None, events_dir=None,
+                    names=None) -> dict:
+    """Decode + score for any iterator of logit batches [B, 250, 648, 14] that covers ``dataset``'s windows in order.
+    ``dataset``: an SELDDataset (``segments``, ``metadata_rows``, ``total_frames``, ``I``, ``J``, ``device``).  Defaults
+    come from Config (SELD_THRESHOLD, SELD_MAX_PEAKS, SELD_DOA_THRESHOLD_DEG).  Returns F20, ER20, LE_CD, LR_CD, TP, FP,
+    FN, N, per_class (plus S, D, I, matched and the settings); with ``events_dir`` one CSV per segment, named after
+    ``names`` or the audio stems, listed under "event_files"."""
+    from config import Config
+    threshold = Config.SELD_THRESHOLD if threshold is None else threshold
+    max_peaks = Config.SELD_MAX_PEAKS if max_peaks is None else max_peaks
+    doa_threshold_deg = Config.SELD_DOA_THRESHOLD_DEG if doa_threshold_deg is None else doa_threshold_deg
+    if (dataset.I, dataset.J) != (GRID_I, GRID_J):
+        raise NotImplementedError(f"the decode kernel is built for the {GRID_I} x {GRID_J} grid, got "
+                                  f"{dataset.I} x {dataset.J}")
+    table = meta_frame_table(dataset.segments, dataset.total_frames)
+    det_cell, _, det_count, _ = decode(batches, table, threshold, max_peaks, device=dataset.device)
+    result = match_and_score(det_cell, det_count, table, dataset.metadata_rows, doa_threshold_deg, dataset.I, dataset.J)
+    result.update(threshold=float(threshold), max_peaks=int(max_peaks), doa_threshold_deg=float(doa_threshold_deg))
+    if events_dir is not None:
+        names = segment_names(dataset) if names is None else list(names)
+        cells, counts = det_cell.cpu().numpy(), det_count.cpu().numpy()
+        result["event_files"] = [str(write_events_csv(Path(events_dir) / f"{name}.csv",
+                                                      events_for_segment(cells, counts, table, s, dataset.I, dataset.J)))
+                                 for s, name in enumerate(names)]
+    return result

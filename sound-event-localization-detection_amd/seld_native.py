@@ -121,6 +121,9 @@ def _declare(lib):
     lib.seld_gru_tile_rows.argtypes = []
     lib.seld_gru_forward.argtypes = [_ptr, _int, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr]
     lib.seld_gru_backward.argtypes = [_ptr, _ptr, _ptr, _int, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr]
+    lib.seld_grid_decode.argtypes = [_ptr, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, ctypes.c_float, _int,
+                                     _ptr, _ptr, _ptr, _ptr, _ptr]
+    lib.seld_doa_match.argtypes = [_ptr, _ptr, _int, _ptr, _ptr, _i64, _int, _int, ctypes.c_double, _ptr, _ptr, _ptr]
     return lib
 
 

@@ -856,6 +856,61 @@ def test_model(test_loader, model_path=None, batch_size=None, device=None, num_v
     return results
 
 
+# ------------------------------------------------------------------------------------------------
+# evaluate_seld: detections and SELD metrics (no reference counterpart; seld_eval.py)
+# ------------------------------------------------------------------------------------------------
+
+def timeline_logits(model, dataset, batch_size, device):
+    """The model's logits [B, 250, 648, 14] for every window of ``dataset`` in timeline order, one batch at a time (eval
+    mode is the caller's; autocast as in training).  Windows come from the device timeline when the dataset keeps one."""
+    n = len(dataset)
+    on_device = device.type == "cuda" and getattr(dataset, "spec_tm", None) is not None
+    for lo in range(0, n, batch_size):
+        idx = list(range(lo, min(lo + batch_size, n)))
+        if on_device:
+            spec, _ = dataset.device_batch(idx)
+        else:
+            spec = torch.stack([dataset[i][0] for i in idx]).to(device)
+        with torch.no_grad(), autocast_context(device):
+            logits = model(spec)
+        yield logits
+
+
+def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, threshold=None, max_peaks=None,
+                  doa_threshold_deg=None, events_dir=None):
+    """Evaluate a checkpoint on what it detects: the windows of ``test_loader.dataset`` (an SELDDataset) run through the
+    model in timeline order, the overlapping grid maps are decoded into DOA events on the GPU and scored against the
+    dataset's CSV rows.  Returns F20, ER20, LE_CD, LR_CD, TP, FP, FN, N, per_class (seld_eval.evaluate_logits); with
+    ``events_dir`` one event CSV per file, named after its audio stem.  The checkpoint is loaded as test_model loads it;
+    runs on rank 0 only."""
+    import seld_eval
+    test_dataset = test_loader.dataset
+    batch_size = batch_size or getattr(test_loader, "batch_size", None) or config.BATCH_SIZE
+    model_path = Path(model_path or (config.CHECKPOINT_PATH / "best_model.pth"))
+    device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if not model_path.exists():
+        raise FileNotFoundError(f"Model checkpoint not found: {model_path}")
+    if get_rank() != 0:
+        logger.info("evaluate_seld runs on rank 0 only")
+        return {}
+    checkpoint = safe_torch_load(model_path, map_location=device)
+    model = prepare_model_for_device(build_model((test_dataset.I, test_dataset.J), True,
+                                                 n_channels=getattr(test_dataset, "n_channels", None)), device)
+    model.load_state_dict(checkpoint["model_state_dict"])
+    model.eval()
+    logger.info(f"SELD evaluation: {len(test_dataset)} windows, checkpoint epoch {checkpoint['epoch']}")
+    results = seld_eval.evaluate_logits(timeline_logits(model, test_dataset, batch_size, device), test_dataset,
+                                        threshold=threshold, max_peaks=max_peaks, doa_threshold_deg=doa_threshold_deg,
+                                        events_dir=events_dir)
+    results["checkpoint_epoch"] = checkpoint["epoch"]
+    logger.info(f"F20 {results['F20']:.4f}  ER20 {results['ER20']:.4f}  LE_CD {results['LE_CD']:.2f} deg  "
+                f"LR_CD {results['LR_CD']:.4f}  (TP {results['TP']}, FP {results['FP']}, FN {results['FN']}, "
+                f"N {results['N']})")
+    return results
+
+
 def _label_classes(labels, num_classes):
     """argmax over classes of the labels, for dense float labels or the compact uint16 mask
     (lowest set bit = first maximal class, as torch.argmax picks the first maximum; mask 0 = background)."""
