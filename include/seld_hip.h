@@ -284,6 +284,34 @@ int64_t seld_conv3x3_wgrad_workspace_floats(int64_t B, int64_t T, int64_t F, int
 int seld_conv3x3_wgrad(const void* x, const void* dy, int64_t B, int64_t T, int64_t F, int64_t Cin, int64_t Cout,
                        void* dw, int dw_is_bf16, float* workspace, void* stream);
 
+/* ---- First encoder block with the convolution recomputed in place (csrc/convfirst.hip) --------------------- */
+/* Conv3x3(4 -> 64, stride 1, pad 1, no bias) -> BatchNorm2d (training mode, affine, running statistics) -> ReLU ->
+ * MaxPool2d((1,2)) of model_crnn.py:5-17 without ever writing the convolution output or its gradient.
+ *   in  [B][T][F][4] bf16 (channels-last memory of the [B, 4, T, F] input; it needs no gradient), 8-byte aligned
+ *   w   [64][4][3][3] bf16 (w_is_bf16) or fp32 (rounded to bf16 as autocast would) with element strides
+ *       w_sco, w_sci, w_sr, w_ss (output channel, input channel, kernel row, kernel column)
+ *   F in {16, 32, 64, 128, 256} (see _supported)
+ * forward : y [B][T][F/2][64] bf16; mean_invstd [2][64], scale_shift [2][64] fp32 (kept for backward); the running
+ *   statistics are updated like nn.BatchNorm2d.  Same expressions and roundings as seld_conv_tail_forward on the
+ *   bf16 convolution output (fp32 accumulation, one rounding).
+ * backward: from dy [B][T][F/2][64] bf16: dw (the convolution's weight gradient, bf16 when dw_is_bf16 else fp32, written
+ *   with element strides dw_s*), dgamma [64], dbeta [64] fp32.
+ * workspace: seld_convfirst_workspace_floats(backward) floats, no initialisation needed.  phases: 3 in normal use;
+ *   1 launches only the first kernel (statistics / reduction), 2 only what follows it (finalise + apply / finalise +
+ *   weight gradient + sum), for timing.
+ * Deterministic: no atomics, every sum in a fixed order. */
+int seld_convfirst_supported(int64_t F, int64_t Cin, int64_t Cout);
+int64_t seld_convfirst_workspace_floats(int backward);
+int seld_convfirst_forward(const void* in, const void* w, int w_is_bf16, int64_t w_sco, int64_t w_sci, int64_t w_sr,
+                           int64_t w_ss, int64_t B, int64_t T, int64_t F, const float* bn_weight, const float* bn_bias,
+                           float* running_mean, float* running_var, float momentum, float eps, void* y,
+                           float* mean_invstd, float* scale_shift, float* workspace, int phases, void* stream);
+int seld_convfirst_backward(const void* in, const void* w, int w_is_bf16, int64_t w_sco, int64_t w_sci, int64_t w_sr,
+                            int64_t w_ss, const void* dy, int64_t B, int64_t T, int64_t F, const float* mean_invstd,
+                            const float* scale_shift, void* dw, int dw_is_bf16, int64_t dw_sco, int64_t dw_sci,
+                            int64_t dw_sr, int64_t dw_ss, float* dgamma, float* dbeta, float* workspace, int phases,
+                            void* stream);
+
 /* ---- CNN block tail: BatchNorm2d -> ReLU -> MaxPool2d((1,2)) at model_crnn.py:5-17 (ConvBlock.forward) ---- */
 /* x: the convolution output in channels-last memory order = row-major [rows = B*T*F][C] (bf16 when is_bf16, else
  * fp32); the two frequency bins of a pooling pair are adjacent rows.  pool = 2: MaxPool2d((1,2)); pool = 1: no

@@ -103,6 +103,10 @@ class ConvBlock(nn.Module):
         self.pool = nn.MaxPool2d(pool_size) if pool_size else None
 
     def forward(self, x):
+        if x.is_cuda and self.conv.in_channels <= 8:
+            import seld_convfirst
+            if seld_convfirst.applicable(self, x):          # first block: convolution recomputed (csrc/convfirst.hip)
+                return seld_convfirst.first_block(self, x)
         x = conv3x3(self.conv, x)
         if x.is_cuda:
             import seld_convtail

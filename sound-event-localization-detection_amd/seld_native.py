@@ -98,6 +98,13 @@ def _declare(lib):
     lib.seld_conv3x3_wgrad_workspace_floats.restype = _i64
     lib.seld_conv3x3_wgrad_workspace_floats.argtypes = [_i64, _i64, _i64, _i64, _i64]
     lib.seld_conv3x3_wgrad.argtypes = [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _int, _ptr, _ptr]
+    lib.seld_convfirst_supported.argtypes = [_i64, _i64, _i64]
+    lib.seld_convfirst_workspace_floats.restype = _i64
+    lib.seld_convfirst_workspace_floats.argtypes = [_int]
+    lib.seld_convfirst_forward.argtypes = [_ptr, _ptr, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr,
+                                           ctypes.c_float, ctypes.c_float, _ptr, _ptr, _ptr, _ptr, _int, _ptr]
+    lib.seld_convfirst_backward.argtypes = [_ptr, _ptr, _int, _i64, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr,
+                                            _ptr, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _int, _ptr]
     lib.seld_layernorm_supported.argtypes = [_i64]
     lib.seld_layernorm_workspace_floats.restype = _i64
     lib.seld_layernorm_workspace_floats.argtypes = [_i64, _i64]
@@ -1039,6 +1046,59 @@ def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor) -> torch.
         check(lib.seld_conv3x3_wgrad(_p(x), _p(dy), b, t, f, cin, cout, _p(dw), _is_bf16(dw), _p(ws),
                                      _stream_ptr(x.device)), "seld_conv3x3_wgrad")
     return dw
+
+
+# --------------------------------------------------------------------------- first encoder block (conv recomputed)
+
+def convfirst_applicable(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """True when ``convfirst_forward`` covers this block input: bf16 x [B, 4, T, F] in channels-last memory,
+    w [64, 4, 3, 3] (bf16 or fp32, any strides), F a power of two in 16 .. 256."""
+    if not (x.is_cuda and x.dim() == 4 and w.dim() == 4 and x.dtype == torch.bfloat16
+            and w.dtype in (torch.float32, torch.bfloat16) and tuple(w.shape[2:]) == (3, 3) and w.shape[1] == x.shape[1]
+            and x.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    return bool(load_library().seld_convfirst_supported(x.shape[3], x.shape[1], w.shape[0]))
+
+
+def convfirst_forward(x, w, bn_weight, bn_bias, running_mean, running_var, momentum, eps, phases=3):
+    """Conv3x3(4 -> 64) -> BatchNorm2d (training) -> ReLU -> MaxPool2d((1, 2)) with the convolution recomputed in both
+    passes (csrc/convfirst.hip).  Returns (y [B, 64, T, F // 2] bf16 channels-last, mean_invstd [2, 64], scale_shift
+    [2, 64]); the running statistics are updated in place."""
+    if not convfirst_applicable(x, w):
+        raise SeldNativeError("convfirst: unsupported shapes, dtypes or layouts")
+    b, _, t, f = x.shape
+    index = ensure_init(x.device)
+    y = torch.empty((b, w.shape[0], t, f // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    stats = torch.empty((2, 2, w.shape[0]), dtype=torch.float32, device=x.device)
+    lib = load_library()
+    ws = torch.empty(int(lib.seld_convfirst_workspace_floats(0)), dtype=torch.float32, device=x.device)
+    with _device_guard(index):
+        check(lib.seld_convfirst_forward(_p(x), _p(w), _is_bf16(w), *w.stride(), b, t, f, _p(bn_weight), _p(bn_bias),
+                                         _p(running_mean), _p(running_var), float(momentum), float(eps), _p(y),
+                                         _p(stats[0]), _p(stats[1]), _p(ws), int(phases), _stream_ptr(x.device)),
+              "seld_convfirst_forward")
+    return y, stats[0], stats[1]
+
+
+def convfirst_backward(x, w, dy, mean_invstd, scale_shift, dw, phases=3):
+    """-> (dw, dgamma [64] fp32, dbeta [64] fp32): the convolution's weight gradient written into ``dw`` (shape of w,
+    bf16 or fp32, any strides) and the BatchNorm parameter gradients, from dy [B, 64, T, F // 2]."""
+    if not convfirst_applicable(x, w) or dw.shape != w.shape or dw.dtype not in (torch.float32, torch.bfloat16):
+        raise SeldNativeError("convfirst: unsupported shapes, dtypes or layouts")
+    b, _, t, f = x.shape
+    if tuple(dy.shape) != (b, w.shape[0], t, f // 2):
+        raise SeldNativeError("convfirst: dy does not match the block's output")
+    if dy.dtype != x.dtype or not dy.is_contiguous(memory_format=torch.channels_last):
+        dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
+    index = ensure_init(x.device)
+    dgb = torch.empty((2, w.shape[0]), dtype=torch.float32, device=x.device)
+    lib = load_library()
+    ws = torch.empty(int(lib.seld_convfirst_workspace_floats(1)), dtype=torch.float32, device=x.device)
+    with _device_guard(index):
+        check(lib.seld_convfirst_backward(_p(x), _p(w), _is_bf16(w), *w.stride(), _p(dy), b, t, f, _p(mean_invstd),
+                                          _p(scale_shift), _p(dw), _is_bf16(dw), *dw.stride(), _p(dgb[0]), _p(dgb[1]),
+                                          _p(ws), int(phases), _stream_ptr(x.device)), "seld_convfirst_backward")
+    return dw, dgb[0], dgb[1]
 
 
 # --------------------------------------------------------------------------- STFT / spatial features
