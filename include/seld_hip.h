@@ -154,6 +154,37 @@ int seld_labels_expand(const uint16_t* mask, int64_t n_cells, int num_classes, f
 int seld_window_gather(const void* src, int64_t total_rows, int64_t row_bytes, const int64_t* starts, int64_t B,
                        int64_t window, void* dst, void* stream);
 
+/* ---- windows with training augmentation (no upstream counterpart) -------------------------- */
+/* The same gather with one transform per window, read from row b of `params`: int32 [B][SELD_AUGMENT_PARAM_INTS] on the
+ * device =
+ *   [0] spatial pattern p, 0..15, 0 = identity: mirror m = p >> 3 (az -> -az), then k = (p >> 1) & 3 quarter turns
+ *       (az -> az + 90 k), then elevation flip e = p & 1 (el -> -el)
+ *   [1] [2] time mask 0 (first frame of the window, length)      [3] [4] time mask 1
+ *   [5] [6] frequency mask 0 (first of the 64 bins, length)      [7] [8] frequency mask 1
+ *   [9] .. [11] padding.
+ * The kernels reduce p modulo 16 and only compare the mask fields with coordinates they generate themselves: no row can
+ * make them read or write out of bounds.  Neither entry point allocates or synchronises (graph-capture safe); a window's
+ * output depends on (source, starts[b], params[b]) only. */
+#define SELD_AUGMENT_PARAM_INTS 12
+#define SELD_AUGMENT_PATTERNS 16
+#define SELD_AUGMENT_MAX_CHANNELS 64
+
+/* Features: src float32 [total_rows][channels][64] -> dst float32 [B][window][channels][64],
+ *   dst[b][w][c][f] = sign * src[starts[b] + w][source channel of c][f]   (sign flip = XOR of the sign bit: exact),
+ * then elements inside a time mask (every channel) or a frequency mask (channels < freq_channels: the log-mel and
+ * intensity-vector channels, not GCC-PHAT lags) are set to mask_value.  Rows outside [0, total_rows) stay zero.
+ * channel_table: HOST pointer, uint8 [SELD_AUGMENT_PATTERNS][channels], entry = source channel | 0x80 when negated
+ * (copied into the kernel's arguments; NULL = every pattern leaves the channels alone). */
+int seld_window_gather_augment(const float* src, int64_t total_rows, int channels, int freq_channels, const int64_t* starts,
+                               const int32_t* params, int64_t B, int64_t window, const uint8_t* channel_table,
+                               float mask_value, float* dst, void* stream);
+
+/* Labels: src uint16 [total_rows][I*J] -> dst uint16 [B][window][I*J], the cell (i, j) of a source row moved to
+ *   i' = e ? I-1-i : i,   j' = ((m ? J-1-j : j) + k J/4) mod J;   rows outside [0, total_rows) are zero (background).
+ * Labels are never masked.  J % 4 != 0 (a quarter turn is not a whole number of cells) or I*J % 8 != 0: -4. */
+int seld_window_permute_mask(const uint16_t* src, int64_t total_rows, int I, int J, const int64_t* starts,
+                             const int32_t* params, int64_t B, int64_t window, uint16_t* dst, void* stream);
+
 /* ---- loss: loss.py:43-54 class_mse_loss (+ its backward) ---------------------------------- */
 /* logits [n_cells][14] (fp32, or bf16 when logits_is_bf16), labels as EITHER the compact mask
  * (uint16 [n_cells]) OR dense float32 [n_cells][14] (exactly one non-NULL).  Writes

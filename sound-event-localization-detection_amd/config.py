@@ -149,6 +149,17 @@ class Config:
     GAUSSIAN_AUGMENT = False    # smrl_seld_gaussian.py:397-534 label augmentation (+-2 sigma box per source)
     GAUSSIAN_SIGMA_AZIMUTH = 5.0
     GAUSSIAN_SIGMA_ELEVATION = 5.0
+    # Training augmentation inside the device window gather (seld_augment.py, csrc/augment.hip).  All
+    # off by default; applied to the training feed only, never to evaluation / inference.  Needs DEVICE_FEED (the host
+    # DataLoader path refuses to run with a switch on: there is no CPU fallback)
+    AUGMENT_SPATIAL = False     # FOA audio channel swapping: one of the 16 sign-and-swap transforms per window and epoch, DOA
+                                # labels moved to match ('logmel' with 4 channels and 'logmel_iv' only)
+    AUGMENT_TIME_MASKS = 0      # SpecAugment: time masks per window, 0..2, every channel
+    AUGMENT_TIME_MASK_MAX = 0   # longest time mask in frames (a length is uniform in [0, max])
+    AUGMENT_FREQ_MASKS = 0      # frequency masks per window, 0..2, log-mel and intensity-vector channels (not GCC-PHAT lags)
+    AUGMENT_FREQ_MASK_MAX = 0   # widest frequency mask in mel bins
+    AUGMENT_MASK_VALUE = 0.0    # what masked elements are set to (0.0 = what tail windows are padded with)
+    FOA_CHANNEL_ORDER = "WYZX"  # which input channel is which: 'WYZX' (STARSS / DCASE FOA recordings) or 'WXYZ'
     # SELD evaluation (seld_eval.py, trainer.evaluate_seld, infer.py)
     SELD_THRESHOLD = 0.5        # a grid cell is a detection when its meta-frame probability reaches this and beats its 8 neighbours
     SELD_MAX_PEAKS = 4          # detections kept per (100 ms meta-frame, class), 1..8

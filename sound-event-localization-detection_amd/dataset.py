@@ -28,6 +28,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
+import seld_augment
 import seld_native
 from config import Config
 from utils import polar_to_grid  # noqa: F401  (re-exported like the reference module)
@@ -422,11 +423,13 @@ class SELDDataset(Dataset):
         return spec, torch.from_numpy(_expand_mask_host(mask, self.num_classes))
 
     # -- device feed (used by trainer when DEVICE_FEED is on) -----------------------------------
-    def device_batch(self, indices, out=None):
+    def device_batch(self, indices, out=None, augment=None):
         """Window indices -> (spec [B, 250, C, 64] f32, mask [B, 250, 648] u16) on the device, gathered
         by seld_window_gather straight from the device timeline (no host round trip, no dense labels).
         ``out``: callable (spec_shape, spec_dtype, mask_shape, mask_dtype) -> (spec_buffer, mask_buffer) or None --
-        the static input buffers of a captured training step (seld_graph.GraphedTrainStep.static_inputs)."""
+        the static input buffers of a captured training step (seld_graph.GraphedTrainStep.static_inputs).
+        ``augment``: None, or the windows' parameter table (int32 [B, 12], ``seld_augment.draw``): the batch is then
+        produced by the augmenting gathers (csrc/augment.hip) -- channel swap + label cell permutation + masks."""
         if self.spec_tm is None:
             raise RuntimeError("device_batch needs keep_on_device=True")
         starts = torch.as_tensor(self.window_starts[np.asarray(indices, dtype=np.int64)])
@@ -435,9 +438,30 @@ class SELDDataset(Dataset):
         if out is not None:
             bufs = out((len(starts), w) + tuple(self.spec_tm.shape[1:]), self.spec_tm.dtype,
                        (len(starts), w) + tuple(self.mask_tm.shape[1:]), self.mask_tm.dtype)
+        if augment is not None:
+            table, freq_channels, mask_value = self._augment_tables()
+            starts = starts.to(self.device, non_blocking=True)
+            params = seld_native.augment_params(augment, len(starts), w, self.device)     # one more small async copy
+            spec = seld_native.gather_windows_augment(self.spec_tm, starts, w, params, table, freq_channels, mask_value,
+                                                      out=bufs[0] if bufs else None)
+            mask = seld_native.gather_windows_permute(self.mask_tm, starts, w, params, self.I, self.J,
+                                                      out=bufs[1] if bufs else None)
+            return spec, mask
         spec = seld_native.gather_windows(self.spec_tm, starts, w, out=bufs[0] if bufs else None)
         mask = seld_native.gather_windows(self.mask_tm, starts, w, out=bufs[1] if bufs else None)
         return spec, mask
+
+    def _augment_tables(self):
+        """(channel table uint8 [16, C], channels that take frequency masks, mask value) for this dataset's feature set and
+        Config.FOA_CHANNEL_ORDER; a feature set without a defined channel swap gets identity rows."""
+        feature_set = getattr(config, "FEATURE_SET", "logmel")
+        order = getattr(config, "FOA_CHANNEL_ORDER", "WYZX")
+        key = (feature_set, order, self.n_channels)
+        if getattr(self, "_augment_key", None) != key:
+            self._augment_key = key
+            self._augment_table = (seld_augment.channel_table(feature_set, self.n_channels, order),
+                                   seld_augment.freq_mask_channels(feature_set, self.n_channels))
+        return self._augment_table + (float(getattr(config, "AUGMENT_MASK_VALUE", 0.0)),)
 
 
 def _expand_mask_host(mask, num_classes):

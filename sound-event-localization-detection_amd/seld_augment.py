@@ -1,0 +1,172 @@
+"""Training augmentation of the device feed: the tables and the per-window draw behind ``csrc/augment.hip``
+(DESIGN.md section 11).  Host-side integer work only; the batches themselves are transformed by the gather kernels.
+
+Spatial pattern ``p`` in 0..15, applied to a whole window (``p = 0`` is the identity):
+
+    mirror first     m = p >> 3         az -> -az                 Y -> -Y
+    then rotate      k = (p >> 1) & 3   az -> az + 90 k           k = 1: X' = -Y, Y' = X;  2: X' = -X, Y' = -Y;  3: X' = Y, Y' = -X
+    then flip        e = p & 1          el -> -el                 Z -> -Z
+
+with X = cos az cos el, Y = sin az cos el, Z = sin el; W never changes.  These are the 16 sign-and-swap transforms of the
+first-order-Ambisonics channels ("audio channel swapping"); on the 10-degree grid each one is an exact permutation of the
+cells, so features AND labels of the transformed sound field are gathers of the stored ones.
+
+Parameter row of one window (int32 x 12, ``include/seld_hip.h``):
+    [0] pattern   [1] [2] [3] [4] two time masks (first frame, length)   [5] [6] [7] [8] two frequency masks   [9..11] 0
+"""
+from __future__ import annotations
+
+import numpy as np
+
+PARAM_INTS = 12
+PATTERNS = 16
+N_BINS = 64
+NEGATE = 0x80                     # channel-table flag: the output channel is MINUS its source channel
+
+SWITCHES = ("AUGMENT_SPATIAL", "AUGMENT_TIME_MASKS", "AUGMENT_FREQ_MASKS")
+
+
+def decode(p: int):
+    """pattern -> (mirror, quarter turns, elevation flip)."""
+    if not 0 <= int(p) < PATTERNS:
+        raise ValueError(f"spatial pattern {p} outside 0..15")
+    return (int(p) >> 3) & 1, (int(p) >> 1) & 3, int(p) & 1
+
+
+def axis_map(p: int):
+    """{'X' | 'Y' | 'Z': (source axis, sign)}: the transformed field's axis is sign * the original field's source axis."""
+    m, k, e = decode(p)
+    x, y = ("X", 1), ("Y", -1 if m else 1)
+    neg = lambda a: (a[0], -a[1])
+    x, y = ((x, y), (neg(y), x), (neg(x), neg(y)), (y, neg(x)))[k]
+    return {"X": x, "Y": y, "Z": ("Z", -1 if e else 1)}
+
+
+def check_channel_order(order: str) -> str:
+    order = str(order).upper()
+    if len(order) != 4 or order[0] != "W" or sorted(order[1:]) != ["X", "Y", "Z"]:
+        raise ValueError(f"FOA_CHANNEL_ORDER must be 'WYZX' (STARSS / DCASE recordings) or 'WXYZ', got {order!r}")
+    return order
+
+
+def spatial_supported(feature_set: str, n_channels: int) -> bool:
+    """Channel swapping is defined for 4-channel FOA input only: 'logmel' with 4 channels and 'logmel_iv' (4 + 3)."""
+    return (feature_set == "logmel" and n_channels == 4) or (feature_set == "logmel_iv" and n_channels == 7)
+
+
+def channel_table(feature_set: str, n_channels: int, order: str = "WYZX") -> np.ndarray:
+    """uint8 [16, n_channels]: entry [p, c] = source channel of output channel c under pattern p, | NEGATE when the output is
+    minus the source.  A log-mel channel takes the log-mel of its source channel (a power: the sign drops out); an
+    intensity-vector channel (4 + n pairs W with input channel 1 + n) takes the SIGNED channel of its source axis.  Feature
+    sets without a defined swap get identity rows (the masks still apply)."""
+    table = np.tile(np.arange(n_channels, dtype=np.uint8), (PATTERNS, 1))
+    if not spatial_supported(feature_set, n_channels):
+        return table
+    order = check_channel_order(order)
+    for p in range(PATTERNS):
+        mp = axis_map(p)
+        for c in range(1, 4):
+            src_axis, sign = mp[order[c]]
+            sc = order.index(src_axis)
+            table[p, c] = sc
+            if n_channels == 7:
+                table[p, 3 + c] = (3 + sc) | (NEGATE if sign < 0 else 0)
+    return table
+
+
+def freq_mask_channels(feature_set: str, n_channels: int) -> int:
+    """Frequency masks apply to channels [0, this): log-mel and intensity vectors have a 64-bin FREQUENCY axis, the 64-wide
+    axis of a GCC-PHAT channel is lags."""
+    if feature_set == "logmel_gcc":                     # C + C(C-1)/2 channels: the first C are log-mel
+        c = int(round((np.sqrt(8 * n_channels + 1) - 1) / 2))
+        return c if c * (c + 1) // 2 == n_channels else 0
+    return n_channels
+
+
+def cell_dest(p: int, I: int = 18, J: int = 36) -> np.ndarray:
+    """int64 [I*J]: the cell a set cell moves TO: (i, j) -> (e ? I-1-i : i, ((m ? J-1-j : j) + k J/4) mod J)."""
+    if J % 4:
+        raise ValueError("a quarter turn is a whole number of cells only when J % 4 == 0")
+    m, k, e = decode(p)
+    i, j = np.divmod(np.arange(I * J, dtype=np.int64), J)
+    i2 = I - 1 - i if e else i
+    j2 = ((J - 1 - j if m else j) + k * (J // 4)) % J
+    return i2 * J + j2
+
+
+def cell_source(p: int, I: int = 18, J: int = 36) -> np.ndarray:
+    """int64 [I*J]: the gather form, out[..., c] = in[..., cell_source[c]] (the inverse permutation of ``cell_dest``)."""
+    dest = cell_dest(p, I, J)
+    src = np.empty_like(dest)
+    src[dest] = np.arange(I * J, dtype=np.int64)
+    return src
+
+
+# ------------------------------------------------------------------------------------------ configuration
+
+def settings(cfg):
+    """The augmentation switches of a Config as a plain dict (missing attributes = off)."""
+    return {
+        "spatial": bool(getattr(cfg, "AUGMENT_SPATIAL", False)),
+        "time_masks": int(getattr(cfg, "AUGMENT_TIME_MASKS", 0)),
+        "time_max": int(getattr(cfg, "AUGMENT_TIME_MASK_MAX", 0)),
+        "freq_masks": int(getattr(cfg, "AUGMENT_FREQ_MASKS", 0)),
+        "freq_max": int(getattr(cfg, "AUGMENT_FREQ_MASK_MAX", 0)),
+        "mask_value": float(getattr(cfg, "AUGMENT_MASK_VALUE", 0.0)),
+        "order": str(getattr(cfg, "FOA_CHANNEL_ORDER", "WYZX")),
+    }
+
+
+def enabled(cfg) -> bool:
+    s = settings(cfg)
+    return s["spatial"] or s["time_masks"] > 0 or s["freq_masks"] > 0
+
+
+def check_settings(cfg, feature_set: str | None = None, n_channels: int | None = None):
+    """Raise ValueError for switches outside their range or a spatial swap the feature set does not define."""
+    s = settings(cfg)
+    for key in ("time_masks", "freq_masks"):
+        if not 0 <= s[key] <= 2:
+            raise ValueError(f"AUGMENT_{key.upper()} must be 0, 1 or 2, got {s[key]}")
+    if s["time_max"] < 0 or s["freq_max"] < 0:
+        raise ValueError("AUGMENT_TIME_MASK_MAX / AUGMENT_FREQ_MASK_MAX must not be negative")
+    if not np.isfinite(s["mask_value"]):
+        raise ValueError("AUGMENT_MASK_VALUE must be finite")
+    check_channel_order(s["order"])
+    if s["spatial"] and feature_set is not None and not spatial_supported(feature_set, int(n_channels)):
+        raise ValueError(
+            f"AUGMENT_SPATIAL is defined for 4-channel FOA features ('logmel' with 4 channels, 'logmel_iv'), not for "
+            f"FEATURE_SET={feature_set!r} with {n_channels} feature channels: a microphone array's geometry is unknown here, "
+            f"so no channel swap is defined (time / frequency masks work for every feature set)")
+    return s
+
+
+def identity_rows(n: int) -> np.ndarray:
+    return np.zeros((int(n), PARAM_INTS), dtype=np.int32)
+
+
+def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, bins: int = N_BINS) -> np.ndarray:
+    """int32 [B, 12] parameter rows for the windows ``window_indices`` (dataset window indices) of ``epoch``.
+
+    A window's row is a function of (seed, epoch, window index) and the switches ONLY -- not of the rank, the batch size
+    or the position in the batch -- so N-rank training sees the same augmented windows as one rank, and a window repeated
+    by the data-parallel wrap padding gets the same transform both times.  The pattern is uniform over the 16; a mask
+    length is a uniform integer in [0, max] (max clipped to the axis), its start uniform over the positions that fit."""
+    s = check_settings(cfg)
+    if window is None:
+        window = int(int(cfg.WINDOW_LENGTH) / int(cfg.SPECTROGRAM_HOP_LENGTH))
+    idx = np.asarray(window_indices, dtype=np.int64).reshape(-1)
+    rows = identity_rows(len(idx))
+    if not (s["spatial"] or s["time_masks"] or s["freq_masks"]):
+        return rows
+    for r, i in enumerate(idx):
+        rng = np.random.default_rng([int(seed), int(epoch), int(i)])
+        if s["spatial"]:
+            rows[r, 0] = rng.integers(0, PATTERNS)
+        for first, count, longest, axis in ((1, s["time_masks"], s["time_max"], int(window)),
+                                            (5, s["freq_masks"], s["freq_max"], int(bins))):
+            for n in range(count):
+                length = int(rng.integers(0, min(longest, axis) + 1))
+                rows[r, first + 2 * n] = rng.integers(0, axis - length + 1)
+                rows[r, first + 2 * n + 1] = length
+    return rows

@@ -70,6 +70,8 @@ def _declare(lib):
     lib.seld_labels_rasterise_box.argtypes = [_ptr, _ptr, _i64, _i64, _int, _int, ctypes.c_double, ctypes.c_double, _ptr,
                                               _ptr]
     lib.seld_window_gather.argtypes = [_ptr, _i64, _i64, _ptr, _i64, _i64, _ptr, _ptr]
+    lib.seld_window_gather_augment.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _i64, _i64, _ptr, ctypes.c_float, _ptr, _ptr]
+    lib.seld_window_permute_mask.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _i64, _i64, _ptr, _ptr]
     lib.seld_softmax_mse_workspace_bytes.restype = _i64
     lib.seld_softmax_mse_workspace_bytes.argtypes = []
     lib.seld_softmax_mse.argtypes = [_ptr, _int, _ptr, _ptr, _i64, _int, ctypes.c_float, _ptr, _ptr, _ptr, _ptr]
@@ -374,6 +376,95 @@ def gather_windows(src: torch.Tensor, starts: torch.Tensor, window: int, out: to
     with _device_guard(index):
         check(load_library().seld_window_gather(_p(src), src.shape[0], row_bytes, _p(starts), starts.numel(),
                                                 window, _p(out), _stream_ptr(src.device)), "seld_window_gather")
+    return out
+
+
+AUGMENT_PARAM_INTS = 12      # SELD_AUGMENT_PARAM_INTS: (pattern, 2 x (time start, length), 2 x (frequency start, length), padding)
+AUGMENT_PATTERNS = 16
+
+
+def augment_params(params, batch: int, window: int, device) -> torch.Tensor:
+    """The per-window parameter table of the augmenting gathers as an int32 [batch, 12] device tensor.  A host table
+    (numpy array / CPU tensor) is validated here -- pattern in 0..15, every mask inside its axis -- and uploaded with one
+    asynchronous copy; a device tensor is trusted (no synchronise; the kernels clamp whatever they are given)."""
+    t = torch.as_tensor(params)
+    if tuple(t.shape) != (batch, AUGMENT_PARAM_INTS):
+        raise ValueError(f"augment parameters must be [{batch}, {AUGMENT_PARAM_INTS}], got {tuple(t.shape)}")
+    if t.is_cuda:
+        if t.dtype != torch.int32:
+            raise TypeError("augment parameters on the device must be int32")
+        return t.contiguous()
+    t = t.to(torch.int32).contiguous()
+    if batch:
+        if int(t[:, 0].min()) < 0 or int(t[:, 0].max()) >= AUGMENT_PATTERNS:
+            raise ValueError("augment parameters: spatial pattern outside 0..15")
+        for first, axis, what in ((1, window, "time"), (3, window, "time"), (5, N_MELS, "frequency"), (7, N_MELS, "frequency")):
+            start, length = t[:, first], t[:, first + 1]
+            if int(start.min()) < 0 or int(length.min()) < 0 or int((start + length).max()) > axis:
+                raise ValueError(f"augment parameters: {what} mask outside [0, {axis})")
+    return t.to(device, non_blocking=True)
+
+
+def gather_windows_augment(src: torch.Tensor, starts: torch.Tensor, window: int, params: torch.Tensor, channel_table=None,
+                           freq_channels: int | None = None, mask_value: float = 0.0,
+                           out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gather_windows`` of the feature timeline src [T, C, 64] (float32) with one augmentation per window
+    (csrc/augment.hip): a signed channel permutation chosen by the window's spatial pattern, then time / frequency masks.
+    ``params``: int32 [B, 12] on the device (``augment_params``); ``channel_table``: uint8 [16, C] host array, entry =
+    source channel | 0x80 when negated (None: channels stay put); frequency masks touch channels < ``freq_channels``."""
+    if not src.is_cuda or src.dtype != torch.float32 or src.dim() != 3 or src.shape[2] != N_MELS:
+        raise SeldNativeError("gather_windows_augment: src must be a float32 GPU tensor [T, C, 64]")
+    src = src.contiguous()
+    channels = int(src.shape[1])
+    if src.shape[0] == 0:
+        raise ValueError("gather_windows_augment: empty source")
+    freq_channels = channels if freq_channels is None else int(freq_channels)
+    index = ensure_init(src.device)
+    starts = starts.to(device=src.device, dtype=torch.int64).contiguous()
+    if not params.is_cuda or params.dtype != torch.int32 or tuple(params.shape) != (starts.numel(), AUGMENT_PARAM_INTS) \
+            or not params.is_contiguous():
+        raise ValueError("gather_windows_augment: params must be a contiguous int32 [B, 12] GPU tensor (augment_params)")
+    table = None
+    if channel_table is not None:
+        import numpy as np
+        table = np.ascontiguousarray(channel_table, dtype=np.uint8)
+        if table.shape != (AUGMENT_PATTERNS, channels):
+            raise ValueError(f"gather_windows_augment: channel_table must be [16, {channels}]")
+    shape = (starts.numel(), window, channels, N_MELS)
+    if out is None:
+        out = torch.empty(shape, dtype=src.dtype, device=src.device)
+    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
+        raise ValueError(f"gather_windows_augment: out must be a contiguous float32 tensor of shape {shape} on {src.device}")
+    with _device_guard(index):
+        check(load_library().seld_window_gather_augment(
+            _p(src), src.shape[0], channels, freq_channels, _p(starts), _p(params), starts.numel(), window,
+            ctypes.c_void_p(table.ctypes.data) if table is not None else None, float(mask_value), _p(out),
+            _stream_ptr(src.device)), "seld_window_gather_augment")
+    return out
+
+
+def gather_windows_permute(src: torch.Tensor, starts: torch.Tensor, window: int, params: torch.Tensor, I: int = GRID_I,
+                           J: int = GRID_J, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gather_windows`` of the label timeline src [T, I*J] (uint16 class masks) with the grid cells moved by each
+    window's spatial pattern (csrc/augment.hip); labels are never masked."""
+    if not src.is_cuda or src.dtype != torch.uint16 or src.dim() != 2 or src.shape[1] != I * J:
+        raise SeldNativeError("gather_windows_permute: src must be a uint16 GPU tensor [T, I*J]")
+    src = src.contiguous()
+    if src.shape[0] == 0:
+        raise ValueError("gather_windows_permute: empty source")
+    index = ensure_init(src.device)
+    starts = starts.to(device=src.device, dtype=torch.int64).contiguous()
+    if not params.is_cuda or params.dtype != torch.int32 or tuple(params.shape) != (starts.numel(), AUGMENT_PARAM_INTS) \
+            or not params.is_contiguous():
+        raise ValueError("gather_windows_permute: params must be a contiguous int32 [B, 12] GPU tensor (augment_params)")
+    shape = (starts.numel(), window, I * J)
+    if out is None:
+        out = torch.empty(shape, dtype=src.dtype, device=src.device)
+    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
+        raise ValueError(f"gather_windows_permute: out must be a contiguous uint16 tensor of shape {shape} on {src.device}")
+    with _device_guard(index):
+        check(load_library().seld_window_permute_mask(_p(src), src.shape[0], I, J, _p(starts), _p(params), starts.numel(),
+                                                      window, _p(out), _stream_ptr(src.device)), "seld_window_permute_mask")
     return out
 
 

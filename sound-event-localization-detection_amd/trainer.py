@@ -35,6 +35,7 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader, RandomSampler, SequentialSampler  # noqa: F401
 from tqdm import tqdm
 
+import seld_augment
 from config import Config
 from dataset import SELDDataset
 from loss import SMRSELDLoss
@@ -243,6 +244,12 @@ class LoaderFeed:
     batch size, workers, collate function and pinning is driven by an explicit batch sampler."""
 
     def __init__(self, loader, device, rank=0, world=1, seed=0):
+        if seld_augment.enabled(config):
+            # the augmentation lives in the device gather kernels (csrc/augment.hip); the product path has no CPU fallback
+            on = [name for name in seld_augment.SWITCHES if getattr(config, name, 0)]
+            raise RuntimeError(f"{', '.join(on)}: training augmentation is applied by the device window gather and needs the "
+                               f"device feed (DEVICE_FEED = True, a ROCm GPU, a SELDDataset kept on the device); the host "
+                               f"DataLoader path has no CPU implementation of it.  Switch the augmentation off to use it")
         self.loader, self.device = loader, device
         self.rank, self.world, self.seed = rank, world, seed
         sampler = getattr(loader, "sampler", None)
@@ -294,6 +301,9 @@ class DeviceFeed:
         self.drop_last = bool(loader.drop_last)
         self.shuffle = isinstance(loader.sampler, RandomSampler)
         self.device, self.rank, self.world, self.seed = device, rank, world, seed
+        # a spatial swap the feature set does not define is refused when the feed is built, not at the first batch
+        if seld_augment.enabled(config):
+            seld_augment.check_settings(config, getattr(config, "FEATURE_SET", "logmel"), self.dataset.n_channels)
 
     def _order(self, epoch):
         return shard_indices(epoch_order(len(self.dataset), self.shuffle, self.seed, epoch), self.rank, self.world)
@@ -302,10 +312,16 @@ class DeviceFeed:
         n = len(shard_indices(range(len(self.dataset)), self.rank, self.world))
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
-    def batches(self, epoch, out=None):
-        """``out``: see SELDDataset.device_batch (gather straight into a captured step's input buffers)."""
+    def batches(self, epoch, out=None, augment=False):
+        """``out``: see SELDDataset.device_batch (gather straight into a captured step's input buffers).
+        ``augment``: apply the Config.AUGMENT_* switches (seld_augment.draw: a window's transform depends on the seed, the
+        epoch and the window's dataset index only).  Only the training loop passes True; with every switch off it is the
+        plain gather."""
+        augment = bool(augment) and seld_augment.enabled(config)
         for idx in batched(self._order(epoch), self.batch_size, self.drop_last):
-            yield self.dataset.device_batch(idx, out=out)
+            params = seld_augment.draw(self.seed, epoch, idx, config, window=self.dataset.window_length_frames) \
+                if augment else None
+            yield self.dataset.device_batch(idx, out=out, augment=params)
 
 
 def make_feed(loader, device, rank, world):
@@ -646,7 +662,10 @@ def train_model(train_loader, test_loader, num_epochs=None, batch_size=None, lea
         term_sum = torch.zeros((), dtype=torch.float64, device=device)
         steps = 0
         static = getattr(stepper, "static_inputs", None) if isinstance(train_feed, DeviceFeed) else None
-        source = train_feed.batches(epoch, out=static) if static is not None else train_feed.batches(epoch)
+        if isinstance(train_feed, DeviceFeed):               # the training feed is the only one that augments
+            source = train_feed.batches(epoch, out=static, augment=True)
+        else:
+            source = train_feed.batches(epoch)
         bar = tqdm(source, total=len(train_feed), desc=f"Epoch {epoch}/{num_epochs} [Train]",
                    leave=False, disable=not is_main)
         for spectrograms, labels in bar:
