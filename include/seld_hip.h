@@ -215,6 +215,43 @@ int seld_multi_adam(const void* const* grad, const int32_t* grad_is_bf16, float*
                     const float* step, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                     void* stream);
 
+/* ---- guarded update: global gradient-norm clipping, non-finite step skip, weight EMA (csrc/guard.hip, csrc/adam.hip) ----
+ * The device-side record the norm pass writes and the guarded Adam reads: 8 words, 32 bytes, 16-byte aligned, zeroed by
+ * the caller once before the first call (the two counters are cumulative).  The flags are floats so that framework ops can
+ * use them as they are (`skipped` is what torch's fused Adam takes as found_inf). */
+typedef struct seld_guard_record {
+  float grad_norm;        /* sqrt(sum over all tensors of (g * grad_scale)^2); inf / NaN when an element is not finite */
+  float clip_coef;        /* min(1, max_norm / (grad_norm + 1e-6)) evaluated in fp32; exactly 1.0f when max_norm <= 0 */
+  float apply;            /* 1.0f: update; 0.0f: skip (only when grad_norm is not finite AND skip_nonfinite was set) */
+  float skipped;          /* 1.0f - apply */
+  int32_t steps_skipped;  /* cumulative: calls that ended with apply == 0 */
+  int32_t steps_clipped;  /* cumulative: applied calls with clip_coef < 1 */
+  int32_t reserved[2];
+} seld_guard_record;
+
+/* Global L2 norm of a LIST of gradient tensors and the guard record, one launch per 48 tensors plus one single-workgroup
+ * launch, deterministic (fixed-order sums, no atomics): pass 1 writes one fp32 partial per 4096-element chunk of every
+ * tensor (at most 25 fp32 additions per partial), pass 2 sums the partials in double.  grad / grad_is_bf16 / lengths as
+ * for seld_multi_adam (HOST arrays; tensors walked as storage).  partial: device scratch of at least
+ * *partial_floats = seld_multi_grad_norm_scratch(lengths, count) floats, rewritten by every call.  A finite gradient
+ * whose squares overflow fp32 inside one chunk (|g * grad_scale| above ~1e17) reads as non-finite. */
+int seld_multi_grad_norm_scratch(const int64_t* lengths, int count, int64_t* partial_floats);
+int seld_multi_grad_norm(const void* const* grad, const int32_t* grad_is_bf16, const int64_t* lengths, int count,
+                         float grad_scale, float max_norm, int skip_nonfinite, float* partial, int64_t partial_floats,
+                         seld_guard_record* guard, void* stream);
+
+/* seld_multi_adam with a guard: every workgroup returns before its first store when guard->apply == 0 (param, exp_avg,
+ * exp_avg_sq, the bf16 working copies and ema untouched); otherwise the gradient is grad * grad_scale * guard->clip_coef
+ * (in that order: a coefficient of exactly 1 gives seld_multi_adam's bits; weight decay is added after clipping) and, where
+ * ema[k] != NULL and ema_decay != 0, ema[k] += (1 - ema_decay) * (p_new - ema[k]) from the fp32 value just computed (fp32,
+ * the master's layout) in the same pass.  ema == NULL: no EMA at all; guard == NULL: always apply, coefficient 1.  The
+ * caller advances `step` only for applied updates (e.g. step += 1 before the call, step -= guard->skipped after it). */
+int seld_multi_adam_guarded(const void* const* grad, const int32_t* grad_is_bf16, float* const* param,
+                            float* const* exp_avg, float* const* exp_avg_sq, void* const* low_bf16, const int64_t* lengths,
+                            int count, const float* lr, const float* step, float beta1, float beta2, float eps,
+                            float weight_decay, float grad_scale, float* const* ema, float ema_decay,
+                            const seld_guard_record* guard, void* stream);
+
 /* One launch per 96 tensors casts a list of tensors (the fp32-master / bf16-working-weight mode of the trainer):
  * src / dst are HOST arrays of `count` device addresses, lengths a HOST array of element counts (the descriptors are
  * passed to the kernel by value).  bf16_to_fp32 != 0: bf16 sources -> fp32 destinations (gradients); 0: fp32 -> bf16

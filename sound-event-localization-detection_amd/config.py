@@ -160,6 +160,13 @@ class Config:
     AUGMENT_FREQ_MASK_MAX = 0   # widest frequency mask in mel bins
     AUGMENT_MASK_VALUE = 0.0    # what masked elements are set to (0.0 = what tail windows are padded with)
     FOA_CHANNEL_ORDER = "WYZX"  # which input channel is which: 'WYZX' (STARSS / DCASE FOA recordings) or 'WXYZ'
+    # Guarded optimiser update (csrc/guard.hip, csrc/adam.hip).  All off by default; device-side, inside
+    # the one-launch update, so they need the master-weight path (bf16 autocast on a ROCm device): make_optimizer refuses
+    # a switched-on guard anywhere else
+    GRAD_CLIP_NORM = 0.0        # > 0: scale the gradients so that their global L2 norm is at most this (clip_grad_norm_)
+    SKIP_NONFINITE_STEPS = False  # skip an update whose gradient norm is inf / NaN (weights, Adam state, EMA, step counts kept)
+    EMA_DECAY = 0.0             # > 0: keep an exponential moving average of the weights (ema += (1 - decay)(w - ema) per update)
+    EVAL_USE_EMA = False        # test_model / evaluate_seld / infer.py load the checkpoint's ema_state_dict (an error if absent)
     # SELD evaluation (seld_eval.py, trainer.evaluate_seld, infer.py)
     SELD_THRESHOLD = 0.5        # a grid cell is a detection when its meta-frame probability reaches this and beats its 8 neighbours
     SELD_MAX_PEAKS = 4          # detections kept per (100 ms meta-frame, class), 1..8

@@ -13,9 +13,15 @@
 //            p -= (lr / (1 - beta1^step)) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
 // with lr and step read from DEVICE scalars (graph replay: a ReduceLROnPlateau change needs no re-capture; the caller
 // increments step before the launch).
+//
+// multi_adam_guarded_kernel is the same body with three additions (seld_multi_adam_guarded): it reads
+// the guard record of csrc/guard.hip and returns before its first store when the step is skipped, multiplies the gradient
+// by the clip coefficient after grad_scale (a coefficient of exactly 1 gives the plain kernel's bits), and keeps an fp32
+// exponential moving average of the new masters in the same pass: + 8 B per parameter (ema read and written) on the 28 B.
 #include <hip/hip_bf16.h>
 
 #include "seld_common.h"
+#include "seld_hip.h"
 
 namespace seld {
 
@@ -47,7 +53,19 @@ __device__ __forceinline__ unsigned adam_pack_bf16x2(float lo, float hi) {
          (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(hi))) << 16);
 }
 
-__global__ __launch_bounds__(kAdamThreads) void multi_adam_kernel(const AdamBatch b, const AdamScalars s) {
+struct AdamGuard {
+  unsigned long long ema[kAdamBatch];                    // fp32 moving average of the master, or 0
+  const seld_guard_record* guard;                        // or nullptr: always apply, coefficient 1
+  float ema_rate;                                        // 1 - decay
+};
+
+template <bool kGuarded>
+__device__ __forceinline__ void multi_adam_body(const AdamBatch& b, const AdamScalars& s, const AdamGuard* x) {
+  float coef = 1.0f;
+  if (kGuarded && x->guard) {
+    if (x->guard->apply == 0.0f) return;                 // uniform: the whole grid leaves before any store
+    coef = x->guard->clip_coef;
+  }
   int t = 0;
   while (t + 1 < b.count && static_cast<int>(blockIdx.x) >= b.first_block[t + 1]) ++t;      // uniform
   const long n = b.n[t];
@@ -59,15 +77,16 @@ __global__ __launch_bounds__(kAdamThreads) void multi_adam_kernel(const AdamBatc
   float* m = reinterpret_cast<float*>(b.m[t]);
   float* v = reinterpret_cast<float*>(b.v[t]);
   unsigned short* low = reinterpret_cast<unsigned short*>(b.low[t]);
+  float* ema = kGuarded ? reinterpret_cast<float*>(x->ema[t]) : nullptr;
   const float lr = *s.lr, step = *s.step;
   const float bc1 = 1.0f - __powf(s.beta1, step), bc2 = 1.0f - __powf(s.beta2, step);
   const float step_size = lr / bc1, bc2_sqrt = sqrtf(bc2);
-  const bool aligned = ((b.grad[t] | b.param[t] | b.m[t] | b.v[t] | b.low[t]) & 15ull) == 0;
+  const bool aligned = ((b.grad[t] | b.param[t] | b.m[t] | b.v[t] | b.low[t] | (kGuarded ? x->ema[t] : 0ull)) & 15ull) == 0;
 #pragma unroll
   for (int k = 0; k < kAdamPerThread / 8; ++k) {
     const long i = base + (static_cast<long>(k) * kAdamThreads + threadIdx.x) * 8;
     if (i >= n) break;
-    float g[8], pp[8], mm[8], vv[8];
+    float g[8], pp[8], mm[8], vv[8], ee[8];
     const bool full = aligned && i + 8 <= n;
     if (full) {
       if (grad_bf16) {
@@ -88,6 +107,10 @@ __global__ __launch_bounds__(kAdamThreads) void multi_adam_kernel(const AdamBatc
       pp[0] = p0.x; pp[1] = p0.y; pp[2] = p0.z; pp[3] = p0.w; pp[4] = p1.x; pp[5] = p1.y; pp[6] = p1.z; pp[7] = p1.w;
       mm[0] = m0.x; mm[1] = m0.y; mm[2] = m0.z; mm[3] = m0.w; mm[4] = m1.x; mm[5] = m1.y; mm[6] = m1.z; mm[7] = m1.w;
       vv[0] = v0.x; vv[1] = v0.y; vv[2] = v0.z; vv[3] = v0.w; vv[4] = v1.x; vv[5] = v1.y; vv[6] = v1.z; vv[7] = v1.w;
+      if (kGuarded && ema) {
+        const float4 e0 = *reinterpret_cast<const float4*>(ema + i), e1 = *reinterpret_cast<const float4*>(ema + i + 4);
+        ee[0] = e0.x; ee[1] = e0.y; ee[2] = e0.z; ee[3] = e0.w; ee[4] = e1.x; ee[5] = e1.y; ee[6] = e1.z; ee[7] = e1.w;
+      }
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -96,16 +119,19 @@ __global__ __launch_bounds__(kAdamThreads) void multi_adam_kernel(const AdamBatc
         pp[j] = p[e];
         mm[j] = m[e];
         vv[j] = v[e];
+        if (kGuarded && ema) ee[j] = ema[e];
       }
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float gj = g[j] * s.grad_scale;
+      if (kGuarded) gj *= coef;
       gj = fmaf(s.weight_decay, pp[j], gj);
       mm[j] = fmaf(1.0f - s.beta1, gj - mm[j], mm[j]);
       vv[j] = fmaf(s.beta2, vv[j], (1.0f - s.beta2) * gj * gj);
       const float denom = sqrtf(vv[j]) / bc2_sqrt + s.eps;
       pp[j] -= step_size * mm[j] / denom;
+      if (kGuarded && ema) ee[j] = fmaf(x->ema_rate, pp[j] - ee[j], ee[j]);
     }
     if (full) {
       *reinterpret_cast<float4*>(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
@@ -122,6 +148,10 @@ __global__ __launch_bounds__(kAdamThreads) void multi_adam_kernel(const AdamBatc
         w.w = adam_pack_bf16x2(pp[6], pp[7]);
         *reinterpret_cast<uint4*>(low + i) = w;
       }
+      if (kGuarded && ema) {
+        *reinterpret_cast<float4*>(ema + i) = make_float4(ee[0], ee[1], ee[2], ee[3]);
+        *reinterpret_cast<float4*>(ema + i + 4) = make_float4(ee[4], ee[5], ee[6], ee[7]);
+      }
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -130,10 +160,20 @@ __global__ __launch_bounds__(kAdamThreads) void multi_adam_kernel(const AdamBatc
           m[i + j] = mm[j];
           v[i + j] = vv[j];
           if (low) low[i + j] = __bfloat16_as_ushort(__float2bfloat16(pp[j]));
+          if (kGuarded && ema) ema[i + j] = ee[j];
         }
       }
     }
   }
+}
+
+__global__ __launch_bounds__(kAdamThreads) void multi_adam_kernel(const AdamBatch b, const AdamScalars s) {
+  multi_adam_body<false>(b, s, nullptr);
+}
+
+__global__ __launch_bounds__(kAdamThreads) void multi_adam_guarded_kernel(const AdamBatch b, const AdamScalars s,
+                                                                          const AdamGuard x) {
+  multi_adam_body<true>(b, s, &x);
 }
 
 }  // namespace seld
@@ -173,6 +213,51 @@ int seld_multi_adam(const void* const* grad, const int32_t* grad_is_bf16, float*
     }
     b.count = here;
     hipLaunchKernelGGL(multi_adam_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kAdamThreads), 0, stream, b, s);
+  }
+  SELD_HIP_TRY(hipGetLastError());
+  return kOk;
+}
+
+int seld_multi_adam_guarded(const void* const* grad, const int32_t* grad_is_bf16, float* const* param,
+                            float* const* exp_avg, float* const* exp_avg_sq, void* const* low_bf16, const int64_t* lengths,
+                            int count, const float* lr, const float* step, float beta1, float beta2, float eps,
+                            float weight_decay, float grad_scale, float* const* ema, float ema_decay,
+                            const seld_guard_record* guard, void* stream_) {
+  using namespace seld;
+  if (!current_state()) return kErrNotInitialised;
+  if (count < 0) return fail(kErrInvalidArgument, "seld_multi_adam_guarded: negative count");
+  if (count == 0) return kOk;
+  if (!grad || !grad_is_bf16 || !param || !exp_avg || !exp_avg_sq || !low_bf16 || !lengths || !lr || !step)
+    return fail(kErrInvalidArgument, "seld_multi_adam_guarded: null pointer");
+  if (!(ema_decay >= 0.0f && ema_decay < 1.0f)) return fail(kErrInvalidArgument, "seld_multi_adam_guarded: ema_decay not in [0, 1)");
+  const bool with_ema = ema != nullptr && ema_decay != 0.0f;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const AdamScalars s{lr, step, beta1, beta2, eps, weight_decay, grad_scale};
+  for (int first = 0; first < count; first += kAdamBatch) {
+    AdamBatch b;
+    AdamGuard x;
+    const int here = count - first < kAdamBatch ? count - first : kAdamBatch;
+    long blocks = 0;
+    for (int i = 0; i < here; ++i) {
+      const int k = first + i;
+      if (lengths[k] <= 0 || !grad[k] || !param[k] || !exp_avg[k] || !exp_avg_sq[k])
+        return fail(kErrInvalidArgument, "seld_multi_adam_guarded: bad tensor descriptor");
+      b.grad[i] = reinterpret_cast<unsigned long long>(grad[k]);
+      b.param[i] = reinterpret_cast<unsigned long long>(param[k]);
+      b.m[i] = reinterpret_cast<unsigned long long>(exp_avg[k]);
+      b.v[i] = reinterpret_cast<unsigned long long>(exp_avg_sq[k]);
+      b.low[i] = reinterpret_cast<unsigned long long>(low_bf16[k]);
+      x.ema[i] = with_ema ? reinterpret_cast<unsigned long long>(ema[k]) : 0ull;
+      b.n[i] = lengths[k];
+      b.flags[i] = grad_is_bf16[k] ? 1 : 0;
+      b.first_block[i] = static_cast<int>(blocks);
+      blocks += (lengths[k] + kAdamChunk - 1) / kAdamChunk;
+      if (blocks >= (1L << 31)) return fail(kErrUnsupported, "seld_multi_adam_guarded: too many elements for one launch");
+    }
+    b.count = here;
+    x.guard = guard;
+    x.ema_rate = 1.0f - ema_decay;
+    hipLaunchKernelGGL(multi_adam_guarded_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kAdamThreads), 0, stream, b, s, x);
   }
   SELD_HIP_TRY(hipGetLastError());
   return kOk;

@@ -32,6 +32,8 @@ def parse_args(argv=None):
     p.add_argument("--threshold", type=float, default=cfg.SELD_THRESHOLD)
     p.add_argument("--max-peaks", type=int, default=cfg.SELD_MAX_PEAKS)
     p.add_argument("--device", default=None, help="default: the current ROCm device")
+    p.add_argument("--use-ema", action="store_true",
+                   help="load the checkpoint's ema_state_dict (default: Config.EVAL_USE_EMA); an error when it has none")
     p.add_argument("wavs", nargs="+", help="PCM WAV recordings (24 kHz)")
     return p.parse_args(argv)
 
@@ -60,7 +62,7 @@ def main(argv=None):
         if model is None:
             model = trainer.prepare_model_for_device(trainer.build_model((ds.I, ds.J), True, n_channels=ds.n_channels),
                                                      device)
-            model.load_state_dict(checkpoint["model_state_dict"])
+            model.load_state_dict(trainer.select_state_dict(checkpoint, True if args.use_ema else None))
             model.eval()
         result = seld_eval.evaluate_logits(trainer.timeline_logits(model, ds, args.batch_size, device), ds,
                                            threshold=args.threshold, max_peaks=args.max_peaks, events_dir=args.out_dir,

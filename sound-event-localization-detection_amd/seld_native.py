@@ -90,6 +90,10 @@ def _declare(lib):
     _pp, _pi64, _pi32 = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
     _f = ctypes.c_float
     lib.seld_multi_adam.argtypes = [_pp, _pi32, _pp, _pp, _pp, _pp, _pi64, _int, _ptr, _ptr, _f, _f, _f, _f, _f, _ptr]
+    lib.seld_multi_grad_norm_scratch.argtypes = [_pi64, _int, _pi64]
+    lib.seld_multi_grad_norm.argtypes = [_pp, _pi32, _pi64, _int, _f, _f, _int, _ptr, _i64, _ptr, _ptr]
+    lib.seld_multi_adam_guarded.argtypes = [_pp, _pi32, _pp, _pp, _pp, _pp, _pi64, _int, _ptr, _ptr, _f, _f, _f, _f, _f, _pp, _f,
+                                            _ptr, _ptr]
     lib.seld_multi_sum_chunks.argtypes = [_pp, _pp, _pi64, _pi32, _pi32, _int, _ptr]
     lib.seld_multi_column_sums_scratch.argtypes = [_pi64, _pi64, _int, _pi64]
     lib.seld_multi_column_sums.argtypes = [_pp, _pp, _pi64, _pi64, _pi32, _int, _ptr, _i64, _ptr]
@@ -708,6 +712,127 @@ def multi_adam(grads, params, exp_avgs, exp_avg_sqs, lows, lr: torch.Tensor, ste
     with _device_guard(ensure_init(device)):
         check(load_library().seld_multi_adam(*args, n, _p(lr), _p(step), float(beta1), float(beta2), float(eps),
                                              float(weight_decay), float(grad_scale), _stream_ptr(device)), "seld_multi_adam")
+    return True
+
+
+# --------------------------------------------------------------------------- guarded update (csrc/guard.hip, adam.hip)
+
+GUARD_WORDS = 8          # seld_guard_record (include/seld_hip.h): norm, coef, apply, skipped | steps_skipped, steps_clipped, 2 spare
+
+
+def new_guard_record(device) -> torch.Tensor:
+    """A zeroed seld_guard_record as a float32 tensor of 8 words (words 4 and 5 are int32 counters: ``read_guard``)."""
+    return torch.zeros(GUARD_WORDS, dtype=torch.float32, device=device)
+
+
+def read_guard(guard: torch.Tensor) -> dict:
+    """The record on the host (ONE device-to-host copy, synchronises)."""
+    host = guard.detach().cpu()
+    counters = host.view(torch.int32)
+    return {"grad_norm": float(host[0]), "clip_coef": float(host[1]), "apply": float(host[2]) != 0.0,
+            "steps_skipped": int(counters[4]), "steps_clipped": int(counters[5])}
+
+
+def grad_norm_scratch_floats(lengths) -> int:
+    """Floats of partial scratch ``multi_grad_norm`` needs for tensors of these element counts."""
+    lengths = [int(x) for x in lengths]
+    out = ctypes.c_int64(0)
+    check(load_library().seld_multi_grad_norm_scratch((ctypes.c_int64 * len(lengths))(*lengths), len(lengths),
+                                                      ctypes.byref(out)), "seld_multi_grad_norm_scratch")
+    return int(out.value)
+
+
+def _guard_ok(guard) -> bool:
+    return (guard.is_cuda and guard.dtype == torch.float32 and guard.is_contiguous() and guard.numel() >= GUARD_WORDS
+            and guard.data_ptr() % 16 == 0)
+
+
+def multi_grad_norm(grads, guard: torch.Tensor, partial: torch.Tensor, grad_scale: float = 1.0, max_norm: float = 0.0,
+                    skip_nonfinite: bool = False, cache=None) -> bool:
+    """Global L2 norm of ``grads`` (bf16 / fp32 GPU tensors, each dense in some memory format) times ``grad_scale``, the
+    clip coefficient for ``max_norm`` (<= 0: exactly 1) and the apply / skip decision, written to ``guard`` (a
+    ``new_guard_record``); ``partial``: fp32 scratch of ``grad_norm_scratch_floats`` elements.  Deterministic, no host
+    synchronisation.  Returns False -- having done nothing -- when a tensor does not qualify.  ``cache``: dict of a caller
+    that passes the same list every iteration (the key covers every address it caches)."""
+    grads = list(grads)
+    n = len(grads)
+    if not (_guard_ok(guard) and partial.is_cuda and partial.dtype == torch.float32 and partial.is_contiguous()):
+        return False
+    key = args = None
+    if cache is not None:
+        key = tuple(g.data_ptr() for g in grads)
+        if cache.get("key") == key:
+            args = cache["args"]
+    if args is None:
+        for g in grads:
+            if not (g.is_cuda and g.dtype in (torch.float32, torch.bfloat16) and g.numel() > 0 and _dense_like(g, g)):
+                return False
+        args = ((ctypes.c_void_p * n)(*[g.data_ptr() for g in grads]),
+                (ctypes.c_int32 * n)(*[int(g.dtype == torch.bfloat16) for g in grads]),
+                (ctypes.c_int64 * n)(*[g.numel() for g in grads]),
+                sum((g.numel() + 4095) // 4096 for g in grads))
+        if cache is not None:
+            cache["key"], cache["args"] = key, args
+    if args[3] > partial.numel():
+        return False
+    device = guard.device
+    with _device_guard(ensure_init(device)):
+        check(load_library().seld_multi_grad_norm(args[0], args[1], args[2], n, float(grad_scale), float(max_norm),
+                                                  int(bool(skip_nonfinite)), _p(partial), partial.numel(), _p(guard),
+                                                  _stream_ptr(device)), "seld_multi_grad_norm")
+    return True
+
+
+def multi_adam_guarded(grads, params, exp_avgs, exp_avg_sqs, lows, lr: torch.Tensor, step: torch.Tensor, beta1: float,
+                       beta2: float, eps: float, weight_decay: float, grad_scale: float = 1.0, emas=None,
+                       ema_decay: float = 0.0, guard=None, cache=None) -> bool:
+    """``multi_adam`` behind a guard record (``multi_grad_norm``): nothing is written when ``guard`` says skip, the
+    gradient is multiplied by its clip coefficient, and ``emas[i]`` (fp32, the parameter's layout; or None) follows the new
+    master as ``ema += (1 - ema_decay) * (p - ema)`` in the same pass.  ``guard`` None: always apply, coefficient 1
+    (EMA alone); ``emas`` None or ``ema_decay`` 0: no EMA.  Returns False -- having done nothing -- when a tensor does not
+    qualify.  ``cache``: as for ``multi_adam``; the key covers every cached address (grad, param, exp_avg, exp_avg_sq,
+    low, ema)."""
+    n = len(params)
+    if n == 0:
+        return True
+    if emas is None or float(ema_decay) == 0.0:
+        emas = None
+    if guard is not None and not _guard_ok(guard):
+        return False
+    key = args = None
+    if cache is not None:
+        key = tuple(t.data_ptr() for t in grads) + tuple(t.data_ptr() for t in params) + \
+            tuple(t.data_ptr() for t in exp_avgs) + tuple(t.data_ptr() for t in exp_avg_sqs) + \
+            tuple(0 if t is None else t.data_ptr() for t in lows) + \
+            (() if emas is None else tuple(0 if t is None else t.data_ptr() for t in emas))
+        if cache.get("key") == key:
+            args = cache["args"]
+    device = params[0].device
+    if args is None:
+        for i, (g, p, m, v, lo) in enumerate(zip(grads, params, exp_avgs, exp_avg_sqs, lows)):
+            e = None if emas is None else emas[i]
+            if not (p.is_cuda and p.dtype == torch.float32 and m.dtype == torch.float32 and v.dtype == torch.float32
+                    and g.dtype in (torch.float32, torch.bfloat16) and _dense_like(g, p) and _dense_like(m, p)
+                    and _dense_like(v, p) and (lo is None or (lo.dtype == torch.bfloat16 and _dense_like(lo, p)))
+                    and (e is None or (e.dtype == torch.float32 and _dense_like(e, p)))):
+                return False
+        args = ((ctypes.c_void_p * n)(*[g.data_ptr() for g in grads]),
+                (ctypes.c_int32 * n)(*[int(g.dtype == torch.bfloat16) for g in grads]),
+                (ctypes.c_void_p * n)(*[p.data_ptr() for p in params]),
+                (ctypes.c_void_p * n)(*[m.data_ptr() for m in exp_avgs]),
+                (ctypes.c_void_p * n)(*[v.data_ptr() for v in exp_avg_sqs]),
+                (ctypes.c_void_p * n)(*[0 if lo is None else lo.data_ptr() for lo in lows]),
+                (ctypes.c_int64 * n)(*[p.numel() for p in params]),
+                None if emas is None else (ctypes.c_void_p * n)(*[0 if e is None else e.data_ptr() for e in emas]))
+        if cache is not None:
+            cache["key"], cache["args"] = key, args
+    if not (lr.is_cuda and step.is_cuda and lr.dtype == torch.float32 and step.dtype == torch.float32):
+        return False
+    with _device_guard(ensure_init(device)):
+        check(load_library().seld_multi_adam_guarded(*args[:7], n, _p(lr), _p(step), float(beta1), float(beta2), float(eps),
+                                                     float(weight_decay), float(grad_scale), args[7], float(ema_decay),
+                                                     None if guard is None else _p(guard), _stream_ptr(device)),
+              "seld_multi_adam_guarded")
     return True
 
 

@@ -23,6 +23,7 @@ What is different underneath:
 """
 import gc
 import logging
+import math
 import os
 import random
 from contextlib import nullcontext
@@ -441,8 +442,70 @@ class MasterWeightAdam(torch.optim.Adam):
             m.grad = torch.zeros_like(m)
 
     own_kernel = True         # Config.FUSED_ADAM_KERNEL via make_optimizer; SELD_OWN_ADAM=0 switches it off (developer A/B)
+    # the guarded update, all off: configure_guard() switches them on and makes the device tensors
+    grad_clip_norm = 0.0      # Config.GRAD_CLIP_NORM
+    skip_nonfinite = False    # Config.SKIP_NONFINITE_STEPS
+    ema_decay = 0.0           # Config.EMA_DECAY
+    _guard = _partial = _ema = None
     seld_grad_scale = 1.0          # every gradient is multiplied by this on its way into the update (data parallel: 1 / world,
                               # set by seld_graph.GraphedTrainStep -- folded into the kernel instead of a pass over the buffers)
+
+    def configure_guard(self, grad_clip_norm=0.0, skip_nonfinite=False, ema_decay=0.0):
+        """Switch on gradient-norm clipping / the non-finite step skip / the weight EMA.  Allocates what the device side
+        needs ONCE, before any capture: the guard record, the norm's partial scratch and the EMA tensors (copies of the
+        masters and of the fp32 others, kept outside ``self.state``: ``state_dict()`` keeps the framework's format)."""
+        import seld_native
+        grad_clip_norm, ema_decay = float(grad_clip_norm), float(ema_decay)
+        if not (grad_clip_norm >= 0.0 and math.isfinite(grad_clip_norm)):
+            raise ValueError(f"GRAD_CLIP_NORM must be a finite number >= 0, got {grad_clip_norm}")
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"EMA_DECAY must be in [0, 1), got {ema_decay}")
+        self.grad_clip_norm, self.skip_nonfinite, self.ema_decay = grad_clip_norm, bool(skip_nonfinite), ema_decay
+        params = self._masters + self._others
+        if self._uses_norm and self._guard is None:
+            device = params[0].device
+            self._guard = seld_native.new_guard_record(device)
+            self._partial = torch.zeros(seld_native.grad_norm_scratch_floats([p.numel() for p in params]),
+                                        dtype=torch.float32, device=device)
+        if ema_decay > 0.0 and self._ema is None:
+            self._ema = [p.detach().clone(memory_format=torch.preserve_format) for p in params]
+        if ema_decay == 0.0:
+            self._ema = None
+        self._norm_cache, self._guarded_cache = {}, {}
+        return self
+
+    @property
+    def _uses_norm(self):
+        return self.grad_clip_norm > 0.0 or self.skip_nonfinite
+
+    @property
+    def guard_active(self):
+        return self._uses_norm or self.ema_decay > 0.0
+
+    def guard_report(self):
+        """{grad_norm, clip_coef, steps_skipped, steps_clipped} of the latest update / so far: one device-to-host copy
+        (synchronises; call it per epoch, not per step)."""
+        import seld_native
+        if self._guard is None:
+            return {"grad_norm": 0.0, "clip_coef": 1.0, "steps_skipped": 0, "steps_clipped": 0}
+        rec = seld_native.read_guard(self._guard)
+        return {k: rec[k] for k in ("grad_norm", "clip_coef", "steps_skipped", "steps_clipped")}
+
+    def ema_tensors(self):
+        """The EMA of every optimiser tensor, in the order masters + others (None when EMA_DECAY is 0)."""
+        return self._ema
+
+    def _torch_guard(self, grads):
+        """The guard record from framework ops (the fallback's fallback: a gradient multi_grad_norm does not take)."""
+        norms = torch._foreach_norm([g.float() for g in grads])
+        total = (torch.linalg.vector_norm(torch.stack(norms).double()) * float(self.seld_grad_scale)).float()
+        rec = self._guard
+        coef = torch.clamp(self.grad_clip_norm / (total + 1e-6), max=1.0) if self.grad_clip_norm > 0.0 else torch.ones_like(total)
+        apply = torch.isfinite(total).float() if self.skip_nonfinite else torch.ones_like(total)
+        rec[0], rec[1], rec[2], rec[3] = total, coef, apply, 1.0 - apply
+        counters = rec.view(torch.int32)
+        counters[4] += (1.0 - apply).to(torch.int32)
+        counters[5] += ((coef < 1.0) & (apply > 0)).to(torch.int32)
 
     def _own_step(self):
         """The whole update as ONE multi-tensor launch per 48 tensors (csrc/adam.hip): the bf16 gradients are read as they
@@ -478,10 +541,40 @@ class MasterWeightAdam(torch.optim.Adam):
         beta1, beta2 = group["betas"]
         if not self._adam_checked(grads, params, exp_avgs, exp_avg_sqs, lows):
             return False
+        if self.guard_active:
+            return self._own_guarded_step(group, grads, params, exp_avgs, exp_avg_sqs, lows, steps)
         torch._foreach_add_(steps, 1)                 # every parameter's own counter, as the framework keeps them
         ok = seld_native.multi_adam(grads, params, exp_avgs, exp_avg_sqs, lows, lr, steps[0], beta1, beta2, group["eps"],
                                     group["weight_decay"], float(self.seld_grad_scale), self._adam_cache)
         assert ok
+        self.fused_casts += 1
+        self.own_steps += 1
+        return True
+
+    def _own_guarded_step(self, group, grads, params, exp_avgs, exp_avg_sqs, lows, steps):
+        """The update with a switch on: [norm of all gradients -> guard record] + the guarded one-launch Adam (clip
+        coefficient, skip, EMA inside the same pass).  Device-side only: the step counts advance before the launch and
+        are taken back by the record's ``skipped`` flag (0.0 or 1.0) after it, as torch's fused Adam does for found_inf."""
+        import seld_native
+        emas = self._ema
+        if emas is not None and not all(e.dtype == torch.float32 and seld_native._dense_like(e, p)
+                                        for e, p in zip(emas, params)):
+            return False
+        beta1, beta2 = group["betas"]
+        scale = float(self.seld_grad_scale)
+        torch._foreach_add_(steps, 1)
+        guard = None
+        if self._uses_norm:
+            guard = self._guard
+            ok = seld_native.multi_grad_norm(grads, guard, self._partial, scale, self.grad_clip_norm, self.skip_nonfinite,
+                                             self._norm_cache)
+            assert ok
+        ok = seld_native.multi_adam_guarded(grads, params, exp_avgs, exp_avg_sqs, lows, group["lr"], steps[0], beta1, beta2,
+                                            group["eps"], group["weight_decay"], scale, emas, self.ema_decay, guard,
+                                            self._guarded_cache)
+        assert ok
+        if self.skip_nonfinite:
+            torch._foreach_add_(steps, guard[3], alpha=-1)
         self.fused_casts += 1
         self.own_steps += 1
         return True
@@ -503,6 +596,15 @@ class MasterWeightAdam(torch.optim.Adam):
         grads = [p.grad for p in self._low]
         if any(p.grad is None for p in self._low + self._others):
             self._uniform_steps = False           # the framework skips such parameters: their step counts fall behind
+        if self._uses_norm:
+            # the norm of the gradients as stored, times grad_scale (before the in-place scaling below rounds them)
+            external = getattr(self, "external_master_grads", False)
+            raw = [(m.grad if external else p.grad) for p, m in zip(self._low, self._masters)] + [p.grad for p in self._others]
+            if any(g is None for g in raw):
+                raise RuntimeError("the guarded update needs a gradient for every parameter")
+            if not seld_native.multi_grad_norm(raw, self._guard, self._partial, float(self.seld_grad_scale),
+                                               self.grad_clip_norm, self.skip_nonfinite, self._norm_cache):
+                self._torch_guard(raw)
         if self.seld_grad_scale != 1.0:
             external = getattr(self, "external_master_grads", False)
             scaled = [g for g in ([m.grad for m in self._masters] if external else grads) + [p.grad for p in self._others]
@@ -519,7 +621,22 @@ class MasterWeightAdam(torch.optim.Adam):
             self.fallback_casts += 1
             for m, g in zip(self._masters, grads):       # a parameter without a gradient, or a layout mismatch
                 m.grad.zero_() if g is None else m.grad.copy_(g)
-        out = super().step(closure)
+        if self.grad_clip_norm > 0.0:
+            torch._foreach_mul_([m.grad for m in self._masters] + [p.grad for p in self._others], self._guard[1])
+        if self.skip_nonfinite:
+            self.found_inf = self._guard[3]          # torch's fused Adam: no update and the step counts taken back, on the device
+        try:
+            out = super().step(closure)
+        finally:
+            if self.skip_nonfinite:
+                del self.found_inf
+        if self._ema is not None:
+            params = self._masters + [p.data for p in self._others]
+            if self._uses_norm:
+                weight = self._guard[2] * (1.0 - self.ema_decay)          # 0 on a skipped step
+                torch._foreach_lerp_(self._ema, params, [weight] * len(params))
+            else:
+                torch._foreach_lerp_(self._ema, params, 1.0 - self.ema_decay)
         working = [p.data for p in self._low]
         if not seld_native.multi_cast(self._masters, working, self._weight_cast_cache):
             torch._foreach_copy_(working, self._masters)
@@ -549,14 +666,58 @@ def make_optimizer(model, learning_rate, device, capturable=False):
             kwargs["capturable"] = True
             kwargs["lr"] = torch.tensor(float(learning_rate), dtype=torch.float32, device=device)
     state = getattr(unwrap(model), "_seld_master_weights", None)
+    clip, skip, decay = guard_settings()
     if state is not None:
         low_ids = {id(p) for p in state[0]}
         others = [p for p in model.parameters() if id(p) not in low_ids]
         opt = MasterWeightAdam(state[0], state[1], others, **kwargs)
         if not getattr(config, "FUSED_ADAM_KERNEL", True):
             opt.own_kernel = False
+        if clip > 0.0 or skip or decay > 0.0:
+            opt.configure_guard(clip, skip, decay)
         return opt
+    if clip > 0.0 or skip or decay > 0.0:
+        raise ValueError("GRAD_CLIP_NORM / SKIP_NONFINITE_STEPS / EMA_DECAY run inside the master-weight update on a ROCm "
+                         "device (AMP_DTYPE = 'bf16', MASTER_WEIGHTS = True): there is no CPU or fp32 fallback")
     return torch.optim.Adam(model.parameters(), **kwargs)
+
+
+def guard_settings():
+    """(GRAD_CLIP_NORM, SKIP_NONFINITE_STEPS, EMA_DECAY) of the config, validated."""
+    clip = float(getattr(config, "GRAD_CLIP_NORM", 0.0) or 0.0)
+    skip = bool(getattr(config, "SKIP_NONFINITE_STEPS", False))
+    decay = float(getattr(config, "EMA_DECAY", 0.0) or 0.0)
+    if not (clip >= 0.0 and math.isfinite(clip)):
+        raise ValueError(f"GRAD_CLIP_NORM must be a finite number >= 0, got {clip}")
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"EMA_DECAY must be in [0, 1), got {decay}")
+    return clip, skip, decay
+
+
+def ema_state_dict(model, optimizer):
+    """``model_state_dict`` with every parameter replaced by its exponential moving average (fp32, the reference's keys);
+    buffers (BatchNorm running statistics, ...) are the live model's.  None when the optimiser keeps no EMA."""
+    emas = optimizer.ema_tensors() if hasattr(optimizer, "ema_tensors") else None
+    if emas is None:
+        return None
+    ema_of = {id(p): e for p, e in zip(optimizer._low + optimizer._others, emas)}
+    sd = model_state_dict(model)
+    for name, p in unwrap(model).named_parameters():
+        if id(p) in ema_of:
+            sd[name] = ema_of[id(p)].detach().clone()
+    return sd
+
+
+def select_state_dict(checkpoint, use_ema=None):
+    """The weights evaluation loads from a checkpoint: ``ema_state_dict`` when ``use_ema`` (default: Config.EVAL_USE_EMA)
+    -- an error when the checkpoint has none, never a silent fallback -- else ``model_state_dict``."""
+    if use_ema is None:
+        use_ema = bool(getattr(config, "EVAL_USE_EMA", False))
+    if not use_ema:
+        return checkpoint["model_state_dict"]
+    if checkpoint.get("ema_state_dict") is None:
+        raise KeyError("EVAL_USE_EMA / use_ema is set but the checkpoint holds no 'ema_state_dict' (train with EMA_DECAY > 0)")
+    return checkpoint["ema_state_dict"]
 
 
 def make_stepper(model, criterion, optimizer, device, world=1):
@@ -588,9 +749,14 @@ def checkpoint_payload(epoch, model, optimizer, train_loss, test_loss):
     for entry in opt_state["state"].values():
         if isinstance(entry.get("step"), torch.Tensor):
             entry["step"] = entry["step"].detach().float().cpu()
-    return {"epoch": epoch, "model_state_dict": model_state_dict(model),
-            "optimizer_state_dict": opt_state, "train_loss": train_loss, "test_loss": test_loss,
-            "config": config}
+    payload = {"epoch": epoch, "model_state_dict": model_state_dict(model),
+               "optimizer_state_dict": opt_state, "train_loss": train_loss, "test_loss": test_loss,
+               "config": config}
+    if float(getattr(config, "EMA_DECAY", 0.0) or 0.0) > 0.0:
+        ema = ema_state_dict(model, optimizer)
+        if ema is not None:
+            payload["ema_state_dict"] = ema
+    return payload
 
 
 def unwrap(model):
@@ -653,6 +819,8 @@ def train_model(train_loader, test_loader, num_epochs=None, batch_size=None, lea
     stale_epochs = 0
     kept_checkpoints = []
     epoch = 0
+    guarded = getattr(optimizer, "guard_active", False)
+    skipped_so_far = 0
 
     for epoch in range(1, num_epochs + 1):
         started = datetime.now()
@@ -707,6 +875,14 @@ def train_model(train_loader, test_loader, num_epochs=None, batch_size=None, lea
         logger.info(f"  Train Loss: {avg_train_loss:.6f} ({config.LOSS_TYPE.upper()}: {avg_train_term:.6f})")
         logger.info(f"  Test Loss:  {avg_test_loss:.6f} ({config.LOSS_TYPE.upper()}: {avg_test_term:.6f})")
         logger.info(f"  Learning Rate: {new_lr:.6f}")
+        if guarded:                                   # one device-to-host copy per epoch (the loop above adds no sync)
+            report = optimizer.guard_report()
+            logger.info(f"  Update guard: grad norm {report['grad_norm']:.4g}, clip coefficient {report['clip_coef']:.4g}, "
+                        f"{report['steps_clipped']} clipped / {report['steps_skipped']} skipped updates so far")
+            if report["steps_skipped"] > skipped_so_far:
+                logger.warning(f"  {report['steps_skipped'] - skipped_so_far} update(s) of this epoch were skipped: "
+                               f"non-finite gradient norm")
+                skipped_so_far = report["steps_skipped"]
 
         # early stopping watches the TRAIN loss (trainer.py:262-270)
         if avg_train_loss < best_train_loss - config.MIN_DELTA:
@@ -784,7 +960,7 @@ def train_model(train_loader, test_loader, num_epochs=None, batch_size=None, lea
 # ------------------------------------------------------------------------------------------------
 
 def test_model(test_loader, model_path=None, batch_size=None, device=None, num_visualizations=5,
-               save_visualizations=True):
+               save_visualizations=True, use_ema=None):
     """Evaluate a checkpoint (trainer.py:394-711): loss, argmax accuracies, frames with events and a few
     ground-truth-vs-prediction plots.  Accuracies and event counts are reduced on the device batch by
     batch instead of collecting every logit on the host (N x 9 MB x 2 upstream); only the frames that
@@ -806,7 +982,7 @@ def test_model(test_loader, model_path=None, batch_size=None, device=None, num_v
     checkpoint = safe_torch_load(model_path, map_location=device)
     model = prepare_model_for_device(build_model(grid, True, n_channels=getattr(test_dataset, "n_channels", None)),
                                      device)
-    model.load_state_dict(checkpoint["model_state_dict"])
+    model.load_state_dict(select_state_dict(checkpoint, use_ema))
     model.eval()
     logger.info(f"Model loaded (epoch {checkpoint['epoch']}, test loss {checkpoint['test_loss']:.6f})")
     criterion = SMRSELDLoss(loss_type=config.LOSS_TYPE, w_class=config.W_CLASS, w_aiur=config.W_AIUR,
@@ -899,7 +1075,7 @@ def timeline_logits(model, dataset, batch_size, device):
 
 
 def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, threshold=None, max_peaks=None,
-                  doa_threshold_deg=None, events_dir=None):
+                  doa_threshold_deg=None, events_dir=None, use_ema=None):
     """Evaluate a checkpoint on what it detects: the windows of ``test_loader.dataset`` (an SELDDataset) run through the
     model in timeline order, the overlapping grid maps are decoded into DOA events on the GPU and scored against the
     dataset's CSV rows.  Returns F20, ER20, LE_CD, LR_CD, TP, FP, FN, N, per_class (seld_eval.evaluate_logits); with
@@ -920,7 +1096,7 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
     checkpoint = safe_torch_load(model_path, map_location=device)
     model = prepare_model_for_device(build_model((test_dataset.I, test_dataset.J), True,
                                                  n_channels=getattr(test_dataset, "n_channels", None)), device)
-    model.load_state_dict(checkpoint["model_state_dict"])
+    model.load_state_dict(select_state_dict(checkpoint, use_ema))
     model.eval()
     logger.info(f"SELD evaluation: {len(test_dataset)} windows, checkpoint epoch {checkpoint['epoch']}")
     results = seld_eval.evaluate_logits(timeline_logits(model, test_dataset, batch_size, device), test_dataset,
