@@ -302,6 +302,12 @@ int seld_smr_loss(const void* logits, int logits_is_bf16, const uint16_t* mask, 
 int seld_gru_fold_bias(const float* b_ih, const float* b_hh, int64_t H, void* gi_bias, int out_is_bf16, float* b_hn,
                        void* stream);
 
+/* seld_gru_fold_bias and, in the same launch, the parameter-only operand of the backward recurrence: w_hh_t_bf16
+ * [2][H][3H] bf16 = W_hh ([2][3H][H], fp32 or bf16 when w_is_bf16) rounded to bf16 (nearest even) and transposed per
+ * direction -- what seld_gru_backward / seld_gru_backward_direct take as w_hh_t.  H must be a multiple of 32. */
+int seld_gru_prepare(const float* b_ih, const float* b_hh, const void* w_hh, int w_is_bf16, int64_t H, void* gi_bias,
+                     int out_is_bf16, float* b_hn, void* w_hh_t_bf16, void* stream);
+
 /* seld_gru_backward's per-tile bias sums `partial` [tiles][2][4][H] -> nn.GRU's bias gradients db_ih [2][3H] =
  * (da_r, da_z, da_n) and db_hh [2][3H] = (da_r, da_z, da_n r), fp32, tiles added in a fixed order. */
 int seld_gru_bias_grads(const float* partial, int64_t tiles, int64_t H, float* db_ih, float* db_hh, void* stream);
@@ -454,7 +460,16 @@ int seld_gru_backward(const void* dy_tile, const void* saved_tile, const void* y
                       const void* w_hh_t_bf16, int64_t tiles, int64_t T, int64_t H, void* dg_tile, float* dbias,
                       void* stream);
 
-/* Layout converters for the two calls above (HBM-bound permutes; elem_bytes = 2 for bf16, 4 for fp32).
+/* The same backward recurrence on the caller's own layouts (bf16 and 4-sequence tiles only: kErrUnsupported otherwise): dy and y
+ * natural [B][T][2H] with exactly B rows (the last tile's padding sequences re-read row B-1 and contribute exact
+ * zeros), dgi [B][T][2][3][H] = (da_r, da_z, da_n) and dghn [B][T][2][H] = da_n*r written contiguously, rows >= B never
+ * touched; saved_tile, w_hh_t and dbias ([ceil(B/S)][2][4][H]) as above.  Bit-identical to seld_gru_to_tile ->
+ * seld_gru_backward -> seld_gru_from_pair_tile, without the two converter launches. */
+int seld_gru_backward_direct(const void* dy, const void* saved_tile, const void* y, int is_bf16,
+                             const void* w_hh_t_bf16, int64_t B, int64_t T, int64_t H, void* dgi, void* dghn,
+                             float* dbias, void* stream);
+
+/* Layout converters for seld_gru_backward (HBM-bound permutes; elem_bytes = 2 for bf16, 4 for fp32).
  * seld_gru_to_tile: natural src [B][T][2][ns][H] -> tile layout dst (B padded with zeros to whole tiles).
  * seld_gru_from_pair_tile: the backward kernel's dg_tile -> dgi [B][T][2][3][H] (da_r, da_z, da_n) and
  * dghn [B][T][2][H] (da_n*r), both contiguous -- what the caller's GEMMs read. */

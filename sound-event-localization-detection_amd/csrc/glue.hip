@@ -42,6 +42,41 @@ __global__ __launch_bounds__(kGlueThreads) void gru_fold_bias_kernel(const float
   if (g == 2) b_hn[d * h + u] = hh;
 }
 
+// gru_fold_bias_kernel's work plus the operand of the backward recurrence that depends on the parameters only:
+// w_t[d][k][g*h + u] = bf16(w_hh[d][g*h + u][k]), the [2][H][3H] transpose of W_hh (round to nearest even, what
+// ``w_hh.to(bf16).transpose(1, 2).contiguous()`` gives).  One launch per layer and forward pass instead of a cast and a
+// strided copy on the main stream right before every backward recurrence.  Block = one 32 x 32 tile through LDS (both
+// sides in 64-B / 128-B runs); the first ceil(6h / 256) blocks also fold the biases.  h is a multiple of 32.
+__global__ __launch_bounds__(kGlueThreads) void gru_prepare_kernel(const float* __restrict__ b_ih,
+                                                                   const float* __restrict__ b_hh, int h,
+                                                                   void* __restrict__ gi_bias, int out_bf16,
+                                                                   float* __restrict__ b_hn, const void* __restrict__ w_hh,
+                                                                   int w_bf16, unsigned short* __restrict__ w_t) {
+  __shared__ unsigned short tile[32][33];
+  const int i = blockIdx.x * kGlueThreads + threadIdx.x;            // over [2][3][h]
+  if (i < 2 * 3 * h) {
+    const int u = i % h, g = (i / h) % 3, d = i / (3 * h);
+    const float hh = b_hh[i];
+    store_from_float(gi_bias, i, out_bf16 != 0, b_ih[i] + (g < 2 ? hh : 0.0f));
+    if (g == 2) b_hn[d * h + u] = hh;
+  }
+  const int kt = h / 32, rt = 3 * h / 32;                           // tiles along k (columns of W_hh) and along its rows
+  const int blk = blockIdx.x;
+  const int d = blk / (rt * kt), r0 = 32 * ((blk / kt) % rt), k0 = 32 * (blk % kt);
+  const int x = threadIdx.x & 31, y0 = threadIdx.x >> 5;
+  const long in0 = static_cast<long>(d) * 3 * h * h, out0 = in0;
+#pragma unroll
+  for (int y = y0; y < 32; y += kGlueThreads / 32) {
+    const long src = in0 + static_cast<long>(r0 + y) * h + k0 + x;
+    tile[y][x] = w_bf16 ? static_cast<const unsigned short*>(w_hh)[src]
+                        : __bfloat16_as_ushort(__float2bfloat16(static_cast<const float*>(w_hh)[src]));
+  }
+  __syncthreads();
+#pragma unroll
+  for (int y = y0; y < 32; y += kGlueThreads / 32)
+    w_t[out0 + static_cast<long>(k0 + y) * 3 * h + r0 + x] = tile[x][y];
+}
+
 // The backward recurrence leaves per-tile sums of (da_r, da_z, da_n, da_n r) over (sequence, time):
 // partial[tile][d][4][h].  db_ih[d] = (r, z, n) ; db_hh[d] = (r, z, n r): nn.GRU's bias gradients, in a fixed order.
 __global__ __launch_bounds__(kGlueThreads) void gru_bias_grads_kernel(const float* __restrict__ partial, int tiles, int h,
@@ -371,6 +406,21 @@ int seld_gru_fold_bias(const float* b_ih, const float* b_hh, int64_t H, void* gi
   const int n = static_cast<int>(6 * H);
   hipLaunchKernelGGL(gru_fold_bias_kernel, dim3((n + kGlueThreads - 1) / kGlueThreads), dim3(kGlueThreads), 0,
                      static_cast<hipStream_t>(stream_), b_ih, b_hh, static_cast<int>(H), gi_bias, out_is_bf16, b_hn);
+  SELD_HIP_TRY(hipGetLastError());
+  return kOk;
+}
+
+int seld_gru_prepare(const float* b_ih, const float* b_hh, const void* w_hh, int w_is_bf16, int64_t H, void* gi_bias,
+                     int out_is_bf16, float* b_hn, void* w_hh_t_bf16, void* stream_) {
+  using namespace seld;
+  if (!current_state()) return kErrNotInitialised;
+  if (H <= 0 || !b_ih || !b_hh || !w_hh || !gi_bias || !b_hn || !w_hh_t_bf16)
+    return fail(kErrInvalidArgument, "seld_gru_prepare: bad argument");
+  if (H % 32 != 0) return fail(kErrUnsupported, "seld_gru_prepare: H must be a multiple of 32");
+  const int blocks = static_cast<int>(2 * (3 * H / 32) * (H / 32));   // >= ceil(6H / 256): 6 H^2 / 1024 >= 6 H / 256 for H >= 4
+  hipLaunchKernelGGL(gru_prepare_kernel, dim3(blocks), dim3(kGlueThreads), 0, static_cast<hipStream_t>(stream_), b_ih,
+                     b_hh, static_cast<int>(H), gi_bias, out_is_bf16, b_hn, w_hh, w_is_bf16,
+                     static_cast<unsigned short*>(w_hh_t_bf16));
   SELD_HIP_TRY(hipGetLastError());
   return kOk;
 }

@@ -66,6 +66,7 @@ enum LdsAttrBit : unsigned {
   kAttrGccMfmaQ15 = 1u << 12,
   kAttrLogmelIvF32 = 1u << 13,
   kAttrLogmelIvI16 = 1u << 14,
+  kAttrGruBackwardDirect = 1u << 15,
 };
 
 // true when `bit` still has to be set up on this device (the caller then sets its attributes and calls lds_attr_set)

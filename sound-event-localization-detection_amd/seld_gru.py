@@ -3,7 +3,7 @@ parameters (model_crnn.py:65-72: GRU(2048, 256, num_layers=2, batch_first, bidir
 
 Per layer:   gi = x [W_ih ; W_ih_reverse]^T + [b_ih ; b_ih_reverse]         one GEMM (hipBLASLt / MFMA)
              y  = recurrence(gi, W_hh, b_hh)                                 one launch, both directions
-backward:    dg = recurrence_backward(dy, saved gates)                       one launch
+backward:    dg = recurrence_backward(dy, saved gates)                       one launch (bf16: on the GEMMs' own layouts)
              dx, dW_ih, db_ih, dW_hh, db_hh                                   five GEMMs / reductions
 Inter-layer dropout as in nn.GRU (training only).  Gate order r | z | n (PyTorch).
 """
@@ -15,6 +15,9 @@ import seld_overlap
 from seld_linear import chunk_count, tall_chunks, tall_product
 
 HIDDEN = 256
+# Developer A/B switch: False sends the bf16 backward recurrence through the layout converters and the tile kernel, and
+# forms W_hh^T right before it, as before the direct-layout kernel existed (same bits; tests compare the two).
+direct_backward = True
 
 
 def applicable(module, x):
@@ -44,25 +47,32 @@ class _BiGRULayer(torch.autograd.Function):
         cdt = torch.bfloat16 if low else torch.float32
         with torch.autocast(device_type="cuda", enabled=False):
             xc = x.to(cdt)
+            need = x.requires_grad or w_ih.requires_grad or w_hh.requires_grad
             # the r / z recurrent biases commute with the sigmoid argument: they ride on the GEMM's bias
+            w_hh_t = None
             if b_ih.dtype == torch.float32 and b_hh.dtype == torch.float32 and b_ih.is_contiguous() and b_hh.is_contiguous():
-                gi_bias, b_hn = seld_native.gru_fold_bias(b_ih, b_hh.reshape(-1), cdt)        # one launch
+                if (direct_backward and need and w_hh.is_contiguous()
+                        and w_hh.dtype in (torch.float32, torch.bfloat16)):
+                    # the same launch also leaves W_hh^T (bf16) for the backward recurrence: parameters only
+                    gi_bias, b_hn, w_hh_t = seld_native.gru_prepare(b_ih, b_hh.reshape(-1), w_hh, cdt)
+                else:
+                    gi_bias, b_hn = seld_native.gru_fold_bias(b_ih, b_hh.reshape(-1), cdt)    # one launch
             else:
                 fold = b_hh.clone()
                 fold[:, 2 * HIDDEN:] = 0
                 gi_bias, b_hn = (b_ih + fold.reshape(-1)).to(cdt), b_hh[:, 2 * HIDDEN:]
             gi = F.linear(xc, w_ih.to(cdt), gi_bias)                               # [B, T, 6H]
             b, t, _ = gi.shape
-            need = x.requires_grad or w_ih.requires_grad or w_hh.requires_grad
             y, saved = seld_native.gru_forward(gi.view(b, t, 2, 3 * HIDDEN), w_hh, b_hn, need)
-        ctx.save_for_backward(xc, w_ih, w_hh, y, saved if saved is not None else torch.empty(0))
+        ctx.save_for_backward(xc, w_ih, w_hh, y, saved if saved is not None else torch.empty(0),
+                              w_hh_t if w_hh_t is not None else torch.empty(0))
         ctx.cdt = cdt
         ctx.dtypes = (w_ih.dtype, b_ih.dtype, w_hh.dtype, b_hh.dtype)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        xc, w_ih, w_hh, y, saved = ctx.saved_tensors
+        xc, w_ih, w_hh, y, saved, w_hh_t = ctx.saved_tensors
         cdt = ctx.cdt
         b, t, _ = y.shape
         h = HIDDEN
@@ -71,15 +81,26 @@ class _BiGRULayer(torch.autograd.Function):
             dyc = dy.to(y.dtype)
             # weight-gradient jobs queued by the layers above start now, beside this recurrence (seld_overlap)
             seld_overlap.launch_pending(dy.device)
-            dgi, dghn, dbias = seld_native.gru_backward(dyc, saved, y, w_hh, raw_bias=True)
+            dgi, dghn, dbias = seld_native.gru_backward(dyc, saved, y, w_hh, raw_bias=True,
+                                                        w_hh_t=w_hh_t if w_hh_t.numel() else None, direct=direct_backward)
             dgi2 = dgi.view(n, 6 * h)                                             # d/d(gi), both directions
             x2 = xc.reshape(n, -1)
             t_wih, t_bih, t_whh, t_bhh = ctx.dtypes
 
             dw_ih = torch.empty((6 * h, x2.shape[1]), dtype=t_wih, device=dy.device)
             dw_hh = torch.empty((2, 3 * h, h), dtype=t_whh, device=dy.device)
+            # the bias gradients are parameter gradients like dW: only the optimiser needs them, so the reduction of
+            # the recurrence's per-tile sums runs where the layer's other parameter gradients run, not on the chain
+            db_ih = torch.empty(6 * h, dtype=t_bih, device=dy.device)
+            db_hh = torch.empty(6 * h, dtype=t_bhh, device=dy.device)
 
             def weight_grads():
+                fp32 = [db if db.dtype == torch.float32 else torch.empty(6 * h, dtype=torch.float32, device=dy.device)
+                        for db in (db_ih, db_hh)]
+                seld_native.gru_bias_grads(dbias, out=fp32)                       # one launch
+                for db, full in zip((db_ih, db_hh), fp32):
+                    if db is not full:
+                        db.copy_(full)
                 if ctx.feature_cf is None:
                     tall_product(dgi2, x2, out=dw_ih)                            # [6H, In]
                 else:                                                            # columns back to (channel, frequency)
@@ -100,20 +121,18 @@ class _BiGRULayer(torch.autograd.Function):
             dx = (dgi2 @ w_ih.to(cdt)).view_as(xc)
             if ctx.overlap:
                 # on the side stream, beside the recurrence of the layer below (seld_overlap.launch_pending there)
-                seld_overlap.submit(dy.device, [dgi, dghn, y, xc, dw_ih, dw_hh], weight_grads)
+                seld_overlap.submit(dy.device, [dgi, dghn, y, xc, dbias, dw_ih, dw_hh, db_ih, db_hh], weight_grads)
             elif seld_overlap.conv_wgrad_side and seld_overlap.enabled and dy.is_cuda:
                 # layer 0 under the captured step: beside the convolution backward (joined by the stepper; carried over
                 # to the next backward stage when the data-parallel step cuts the pass below this layer)
-                seld_overlap.launch_now(dy.device, [dgi, dghn, y, xc, dw_ih, dw_hh], weight_grads, last_of_stage=True,
-                                        outputs=[dw_ih, dw_hh])
+                seld_overlap.launch_now(dy.device, [dgi, dghn, y, xc, dbias, dw_ih, dw_hh, db_ih, db_hh], weight_grads,
+                                        last_of_stage=True, outputs=[dw_ih, dw_hh, db_ih, db_hh])
             else:
                 weight_grads()
-            db_ih, db_hh = seld_native.gru_bias_grads(dbias)                       # [6H], [6H] fp32, one launch
-            db_hh = db_hh.view(2, 3 * h)
-        # (fresh aliases of dw_ih / dw_hh: a queued job keeps its tensors referenced, and autograd clones a gradient that
-        # is referenced elsewhere -- before the job has filled it)
+        # (fresh aliases of dw_ih / dw_hh / db_ih / db_hh: a queued job keeps its tensors referenced, and autograd clones a
+        # gradient that is referenced elsewhere -- before the job has filled it)
         return dx.to(dy.dtype) if dx.dtype != dy.dtype and not torch.is_autocast_enabled() else dx, \
-            dw_ih.view_as(dw_ih), db_ih.to(t_bih), dw_hh.view_as(dw_hh), db_hh.to(t_bhh), None, None
+            dw_ih.view_as(dw_ih), db_ih.view_as(db_ih), dw_hh.view_as(dw_hh), db_hh.view(2, 3 * h), None, None
 
 
 from seld_pack import adjacent as _adjacent, join as _join, pack as _pack   # noqa: E402  (shared with the attention layers)

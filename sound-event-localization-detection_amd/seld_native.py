@@ -83,6 +83,7 @@ def _declare(lib):
     lib.seld_multi_cast.argtypes = [_ptr, _ptr, _ptr, _int, _int, _ptr]
     lib.seld_stream_delay.argtypes = [_i64, _ptr]
     lib.seld_gru_fold_bias.argtypes = [_ptr, _ptr, _i64, _ptr, _int, _ptr, _ptr]
+    lib.seld_gru_prepare.argtypes = [_ptr, _ptr, _ptr, _int, _i64, _ptr, _int, _ptr, _ptr, _ptr]
     lib.seld_gru_bias_grads.argtypes = [_ptr, _i64, _i64, _ptr, _ptr, _ptr]
     lib.seld_sum_chunks.argtypes = [_ptr, _int, _i64, _i64, _ptr, _int, _ptr]
     lib.seld_gru_dwhh_finish.argtypes = [_ptr, _ptr, _int, _i64, _i64, _ptr, _int, _ptr]
@@ -134,6 +135,7 @@ def _declare(lib):
     lib.seld_gru_tile_rows.argtypes = []
     lib.seld_gru_forward.argtypes = [_ptr, _int, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr]
     lib.seld_gru_backward.argtypes = [_ptr, _ptr, _ptr, _int, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr]
+    lib.seld_gru_backward_direct.argtypes = [_ptr, _ptr, _ptr, _int, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr]
     lib.seld_grid_decode.argtypes = [_ptr, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, ctypes.c_float, _int,
                                      _ptr, _ptr, _ptr, _ptr, _ptr]
     lib.seld_doa_match.argtypes = [_ptr, _ptr, _int, _ptr, _ptr, _i64, _int, _int, ctypes.c_double, _ptr, _ptr, _ptr]
@@ -1046,10 +1048,14 @@ def gru_forward(gi: torch.Tensor, w_hh: torch.Tensor, b_hn: torch.Tensor, need_s
     return y[:b], saved
 
 
-def gru_backward(dy: torch.Tensor, saved: torch.Tensor, y: torch.Tensor, w_hh: torch.Tensor, raw_bias: bool = False):
+def gru_backward(dy: torch.Tensor, saved: torch.Tensor, y: torch.Tensor, w_hh: torch.Tensor, raw_bias: bool = False,
+                 w_hh_t: torch.Tensor = None, direct: bool = True):
     """dy [B, T, 2H], the forward's (saved, y) -> (dgi [B, T, 2, 3, H] = (da_r, da_z, da_n), dghn [B, T, 2, H] =
     da_n*r, both of dy's dtype, dbias [2, 4, H] fp32 = the four slots summed over batch and time; with ``raw_bias``
-    the per-tile sums [tiles, 2, 4, H] as the kernel left them, for ``gru_bias_grads``)."""
+    the per-tile sums [tiles, 2, 4, H] as the kernel left them, for ``gru_bias_grads``).  ``w_hh_t``: W_hh as bf16
+    [2, H, 3H] if the caller has it already (``gru_prepare``), else it is formed here.  bf16 tensors go through the
+    direct-layout kernel (one launch); fp32 ones, or ``direct=False``, through the layout converters and the tile kernel
+    (three launches, same bits)."""
     b, t, h2 = dy.shape
     h = h2 // 2
     index = ensure_init(dy.device)
@@ -1057,12 +1063,29 @@ def gru_backward(dy: torch.Tensor, saved: torch.Tensor, y: torch.Tensor, w_hh: t
         raise ValueError("gru_backward: saved activations do not belong to a forward pass of this dtype")
     if y.dtype != dy.dtype or tuple(y.shape) != (b, t, h2):
         raise ValueError("gru_backward: y must be the forward output matching dy")
+    if w_hh_t is None:
+        w_t = w_hh.to(torch.bfloat16).transpose(1, 2).contiguous()        # [2, H, 3H]
+    else:
+        if w_hh_t.dtype != torch.bfloat16 or tuple(w_hh_t.shape) != (2, h, 3 * h) or not w_hh_t.is_contiguous():
+            raise ValueError("gru_backward: w_hh_t must be contiguous bf16 [2, H, 3H]")
+        w_t = w_hh_t
+    if direct and dy.dtype == torch.bfloat16 and GRU_TILE == 4:           # (the 8-sequence build has no direct kernel)
+        tiles = (b + GRU_TILE - 1) // GRU_TILE
+        dy, y = dy.contiguous(), y.contiguous()
+        dgi = torch.empty((b, t, 2, 3, h), dtype=dy.dtype, device=dy.device)
+        dghn = torch.empty((b, t, 2, h), dtype=dy.dtype, device=dy.device)
+        dbias = torch.empty((tiles, 2, 4, h), dtype=torch.float32, device=dy.device)
+        with _device_guard(index):
+            check(load_library().seld_gru_backward_direct(_p(dy), _p(saved), _p(y), 1, _p(w_t), b, t, h, _p(dgi), _p(dghn),
+                                                          _p(dbias), _stream_ptr(dy.device)), "seld_gru_backward_direct")
+        if raw_bias:
+            return dgi, dghn, dbias
+        return dgi, dghn, dbias.sum(dim=0) if tiles > 1 else dbias[0]
     dy_tile = to_tile_device(dy.reshape(b, t, 2, 1, h), 1)
     tiles = dy_tile.shape[0]
     if tiles * GRU_TILE != b:               # the kernel reads whole tiles of y (h_{t-1}); pad rows are never used
         y = torch.cat((y, y.new_zeros((tiles * GRU_TILE - b, t, h2))), dim=0)
     y = y.contiguous()
-    w_t = w_hh.to(torch.bfloat16).transpose(1, 2).contiguous()            # [2, H, 3H]
     dg_tile = torch.empty((tiles, t, 2, 8, 2, 4, 16 // GRU_TILE, GRU_TILE, 2, 8 * GRU_TILE // 16), dtype=dy.dtype,
                           device=dy.device)
     dbias = torch.empty((tiles, 2, 4, h), dtype=torch.float32, device=dy.device)
@@ -1099,16 +1122,41 @@ def gru_fold_bias(b_ih: torch.Tensor, b_hh: torch.Tensor, dtype: torch.dtype):
     return gi_bias, b_hn
 
 
-def gru_bias_grads(partial: torch.Tensor):
-    """The backward recurrence's per-tile sums [tiles, 2, 4, H] fp32 -> (db_ih [2*3H], db_hh [2*3H]) fp32."""
+def gru_prepare(b_ih: torch.Tensor, b_hh: torch.Tensor, w_hh: torch.Tensor, dtype: torch.dtype):
+    """``gru_fold_bias`` plus, in the same launch, W_hh [2, 3H, H] (fp32 or bf16, contiguous) as the backward
+    recurrence reads it: bf16 [2, H, 3H] -> (gi_bias, b_hn, w_hh_t)."""
+    if not (b_ih.is_cuda and b_ih.dtype == torch.float32 and b_hh.dtype == torch.float32 and b_ih.is_contiguous()
+            and b_hh.is_contiguous() and b_ih.numel() == b_hh.numel() and b_ih.numel() % 6 == 0):
+        raise SeldNativeError("gru_prepare: b_ih, b_hh must be contiguous fp32 GPU tensors of 2 * 3H elements")
+    h = b_ih.numel() // 6
+    if not (w_hh.is_cuda and w_hh.is_contiguous() and tuple(w_hh.shape) == (2, 3 * h, h) and h % 32 == 0):
+        raise SeldNativeError("gru_prepare: w_hh must be a contiguous GPU tensor [2, 3H, H], H a multiple of 32")
+    gi_bias = torch.empty(6 * h, dtype=dtype, device=b_ih.device)
+    b_hn = torch.empty((2, h), dtype=torch.float32, device=b_ih.device)
+    w_t = torch.empty((2, h, 3 * h), dtype=torch.bfloat16, device=b_ih.device)
+    with _device_guard(ensure_init(b_ih.device)):
+        check(load_library().seld_gru_prepare(_p(b_ih), _p(b_hh), _p(w_hh), _is_bf16(w_hh), h, _p(gi_bias),
+                                              _is_bf16(gi_bias), _p(b_hn), _p(w_t), _stream_ptr(b_ih.device)),
+              "seld_gru_prepare")
+    return gi_bias, b_hn, w_t
+
+
+def gru_bias_grads(partial: torch.Tensor, out=None):
+    """The backward recurrence's per-tile sums [tiles, 2, 4, H] fp32 -> (db_ih [2*3H], db_hh [2*3H]) fp32; written
+    into ``out = (db_ih, db_hh)`` (contiguous fp32, 6H elements each) when given."""
     tiles, two, four, h = partial.shape
     if two != 2 or four != 4 or partial.dtype != torch.float32 or not partial.is_contiguous():
         raise SeldNativeError("gru_bias_grads: partial must be contiguous fp32 [tiles, 2, 4, H]")
-    db = torch.empty((2, 6 * h), dtype=torch.float32, device=partial.device)
+    if out is None:
+        db = torch.empty((2, 6 * h), dtype=torch.float32, device=partial.device)
+        out = (db[0], db[1])
+    elif not all(o.dtype == torch.float32 and o.is_contiguous() and o.numel() == 6 * h and o.device == partial.device
+                 for o in out):
+        raise SeldNativeError("gru_bias_grads: out must be two contiguous fp32 tensors of 6H elements")
     with _device_guard(ensure_init(partial.device)):
-        check(load_library().seld_gru_bias_grads(_p(partial), tiles, h, _p(db[0]), _p(db[1]),
+        check(load_library().seld_gru_bias_grads(_p(partial), tiles, h, _p(out[0]), _p(out[1]),
                                                  _stream_ptr(partial.device)), "seld_gru_bias_grads")
-    return db[0], db[1]
+    return out[0], out[1]
 
 
 def sum_chunks(partial: torch.Tensor, out: torch.Tensor) -> torch.Tensor:

@@ -67,7 +67,8 @@ def active(x):
 
 # The recurrence's 16 workgroups each need a whole CU's LDS: if the GEMMs get to the CUs first the recurrence waits for
 # a CU to drain (tools/bench_overlap.py: recurrence 383 us alone, 473 us beside a 139 us job, 440 us when the job starts
-# 20 us late).  The main stream still has the dy layout converter (~12 us) to run before the recurrence launches.
+# 20 us late).  (Measured when the main stream still ran a dy layout converter, ~12 us, before the recurrence; the bf16
+# recurrence reads dy as it is now and launches at once.  The fp32 path keeps the converter.)
 head_start_ns = 25000
 
 _pending = []       # (device, tensors, job): weight-gradient jobs waiting for the next recurrence launch (or the join)

@@ -50,8 +50,15 @@ k_f = timeit(lambda: lib.seld_gru_forward(P(gi), 1, P(wb), P(bn), B, T, H, P(yk)
 k_i = timeit(lambda: lib.seld_gru_forward(P(gi), 1, P(wb), P(bn), B, T, H, P(yk), None, st))
 dbias = torch.empty((tiles, 2, 4, H), device=dev)
 k_b = timeit(lambda: lib.seld_gru_backward(P(dy_tile), P(saved), P(yk), 1, P(wt), tiles, T, H, P(dg_tile), P(dbias), st))
+# the direct-layout backward kernel: natural dy / y / dgi / dghn, no converter launches around it
+dgi = torch.empty((B, T, 2, 3, H), dtype=torch.bfloat16, device=dev)
+dghn = torch.empty((B, T, 2, H), dtype=torch.bfloat16, device=dev)
+k_d = timeit(lambda: lib.seld_gru_backward_direct(P(dy), P(saved), P(y), 1, P(wt), B, T, H, P(dgi), P(dghn), P(dbias), st))
 print(f"[{seld_native.GRU_TILE} sequences per tile] kernels only: forward {k_f * 1e3:.0f} us ({k_f * 1e3 / T:.2f} us/step)  forward(no save) {k_i * 1e3:.0f} us "
-      f"({k_i * 1e3 / T:.2f} us/step)  backward {k_b * 1e3:.0f} us ({k_b * 1e3 / T:.2f} us/step)")
+      f"({k_i * 1e3 / T:.2f} us/step)  backward {k_b * 1e3:.1f} us ({k_b * 1e3 / T:.3f} us/step)  "
+      f"backward(direct) {k_d * 1e3:.1f} us ({k_d * 1e3 / T:.3f} us/step)")
+t_bt = timeit(lambda: seld_native.gru_backward(dy, saved, y, w, direct=False))
+print(f"gru_backward with its helper launches: direct {t_b * 1e3:.1f} us  tile path {t_bt * 1e3:.1f} us")
 flop = 2 * B * T * 2 * H * 3 * H * 2          # per kernel (both directions)
 print(f"gru B={B} T={T}: forward {t_f * 1e3:.0f} us ({t_f * 1e3 / T:.2f} us/step, {flop / t_f / 1e9:.1f} TFLOP/s) "
       f"backward {t_b * 1e3:.0f} us ({t_b * 1e3 / T:.2f} us/step)")
