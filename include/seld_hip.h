@@ -515,6 +515,25 @@ int seld_doa_match(const int32_t* det_cell, const int32_t* det_count, int K, con
                    const int32_t* ref_dirs, int64_t nq, int I, int J, double thr_deg, int32_t* stats, double* cost,
                    void* stream);
 
+/* ---- test-time augmentation of the decode (csrc/seld_tta.hip) ------------------------------
+ * seld_grid_decode_tta: seld_grid_decode over n_patterns (1..16) transformed copies of the windows, averaged in the
+ * ORIGINAL frame before the peak test.  logits [n_patterns][nw][250][648][14], contiguous: stack n holds windows
+ * [w0, w0+nw) gathered with spatial pattern patterns[n] (0..15, no duplicates; SELD_AUGMENT_* below seld_window_gather:
+ * mirror p >> 3, then (p >> 1) & 3 quarter turns, then elevation flip p & 1), so that an event at original cell (i, j)
+ * shows in stack n at dest_n(i, j) = (e ? 17 - i : i, ((m ? 35 - j : j) + 9 k) mod 36).  `patterns` is a HOST pointer,
+ * read before the launch (the list travels by value in the kernel arguments: no upload, graph-capture safe).
+ *   p_f[cell][c] = (sum over the windows w covering frame f (ascending), inside it over n (ascending), of
+ *                   softmax(logits[n][w][f - 50 w][dest_n(cell)][:])[c]) / (n_w * n_patterns), fp32
+ *   P_q = mean of p_f over the frames of q (ascending), and everything after it, as seld_grid_decode.
+ * patterns = {0} gives seld_grid_decode's outputs bit for bit.  Outputs, the coverage rule (a meta-frame whose windows
+ * are not all present writes nothing; the host checks before launching), no allocation, no synchronise: as
+ * seld_grid_decode.  -1 for n_patterns outside 1..16, a pattern outside 0..15, a duplicate, K outside 1..8, null
+ * pointers. */
+int seld_grid_decode_tta(const void* logits, int is_bf16, int64_t w0, int64_t nw, int64_t W, int64_t total,
+                         const int64_t* meta_first, const int32_t* meta_len, int64_t q0, int64_t nq,
+                         const int32_t* patterns, int n_patterns, float threshold, int K, int32_t* det_cell,
+                         float* det_score, int32_t* det_count, float* probs_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,9 @@ class Config:
     SELD_THRESHOLD = 0.5        # a grid cell is a detection when its meta-frame probability reaches this and beats its 8 neighbours
     SELD_MAX_PEAKS = 4          # detections kept per (100 ms meta-frame, class), 1..8
     SELD_DOA_THRESHOLD_DEG = 20  # a detection matches a reference within this great-circle angle (F20 / ER20)
+    SELD_TTA_PATTERNS = ()      # test-time augmentation in evaluate_seld / infer.py: the spatial patterns (0..15, section 11.1)
+                                # whose un-permuted grid maps are averaged before the peak test; () = off, "all" = the
+                                # 16, or a list such as (0, 2, 9).  One forward per pattern; 4-channel FOA features only
 
     def __init__(self):
         for folder in (self.OUTPUT_PATH, self.CHECKPOINT_PATH):

@@ -9,252 +9,19 @@
 //                     minimum-cost assignment of size min(R, P) and the maximum-cardinality matching within the DOA
 //                     threshold.
 // Both are deterministic: fixed summation order, no float atomics.
-#include "seld_common.h"
+#include "seld_eval_core.h"
 
 namespace seld {
 namespace eval {
 
-constexpr int kI = 18, kJ = 36, kCells = kI * kJ;      // 10-degree grid, cell = i * J + j (utils.py:77-90)
-constexpr int kM = 14, kC = 13;                        // 13 event classes + background
-constexpr int kWin = 250, kHop = 50;                   // windows of the timeline (dataset.py:267-317)
-constexpr int kRowElems = kCells * kM;                 // 9 072 logits per (window, frame)
-constexpr int kThreads = 512;                         // 8 waves: two per SIMD hide each other's latency
-constexpr int kCellsPerThread = (kCells + kThreads - 1) / kThreads;   // 2
-constexpr int kMaxK = 8;
-constexpr int kProbFloats = kCells * kC;               // 8 424: P_q of one meta-frame
-
-template <bool kBf16> struct Row {
-  static constexpr int kBytes = kRowElems * (kBf16 ? 2 : 4);
-  static constexpr int kChunks = kBytes / 16;                              // 1 134 (bf16) / 2 268 (fp32)
-  static constexpr int kPerThread = (kChunks + kThreads - 1) / kThreads;  // 3 / 5
-  // LDS: one staged row, reused for P_q once the rows are consumed
-  static constexpr int kLdsChunks = kChunks > kProbFloats / 4 ? kChunks : kProbFloats / 4;
-};
-static_assert(kRowElems * 2 % 16 == 0, "bf16 rows must be whole 16-byte chunks");
-static_assert(kProbFloats % 4 == 0, "P_q must be whole 16-byte chunks");
-
-// Windows covering frame f: HOP*w <= f < HOP*w + WIN, 0 <= w < W.
-__device__ __forceinline__ long first_window(long f) { return f < kWin ? 0 : (f - kWin) / kHop + 1; }
-__device__ __forceinline__ long last_window(long f, long W) { const long w = f / kHop; return w < W - 1 ? w : W - 1; }
-
-// 14 logits of one cell from the staged row -> the 13 event-class probabilities (softmax in fp32)
-template <bool kBf16> __device__ __forceinline__ void cell_softmax(const uint4* stage, int cell, float p[kC]) {
-  float x[kM];
-  if constexpr (kBf16) {
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(stage) + cell * (kM / 2);   // 28 B per cell, 4-byte aligned
-#pragma unroll
-    for (int e = 0; e < kM / 2; ++e) {
-      const uint32_t v = w[e];
-      x[2 * e] = __uint_as_float(v << 16);
-      x[2 * e + 1] = __uint_as_float(v & 0xffff0000u);
-    }
-  } else {
-    const float2* w = reinterpret_cast<const float2*>(stage) + cell * (kM / 2);       // 56 B per cell, 8-byte aligned
-#pragma unroll
-    for (int e = 0; e < kM / 2; ++e) {
-      const float2 v = w[e];
-      x[2 * e] = v.x;
-      x[2 * e + 1] = v.y;
-    }
-  }
-  float m = x[0];
-#pragma unroll
-  for (int k = 1; k < kM; ++k) m = fmaxf(m, x[k]);
-  // hardware exp2 and one reciprocal per cell: a few ulp of fp32, far inside the 2e-5 the decode is held to, and the
-  // row's arithmetic no longer outlasts its loads
-  float s = 0.0f;
-#pragma unroll
-  for (int k = 0; k < kM; ++k) {
-    x[k] = __expf(x[k] - m);
-    s += x[k];
-  }
-  const float inv = 1.0f / s;
-#pragma unroll
-  for (int k = 0; k < kC; ++k) p[k] = x[k] * inv;
-}
-
-// (score, cell) order of the detections: score descending, then cell ascending; cell == kCells marks "none"
-__device__ __forceinline__ bool before(float sa, int ca, float sb, int cb) {
-  if (cb == kCells) return ca != kCells;
-  if (ca == kCells) return false;
-  return sa > sb || (sa == sb && ca < cb);
-}
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // (HIP's uint4 wrapper keeps arrays of it in scratch)
-
-// this thread's 16-byte chunks of row (window wi, frame fr) into registers
-template <bool kBf16>
-__device__ __forceinline__ void load_row(const uint4* __restrict__ logits, long w0, long fr, long wi, int tid,
-                                         u32x4 (&next)[Row<kBf16>::kPerThread]) {
-  using R = Row<kBf16>;
-  const u32x4* src = reinterpret_cast<const u32x4*>(logits) + ((wi - w0) * kWin + (fr - kHop * wi)) * static_cast<long>(R::kChunks);
-#pragma unroll
-  for (int e = 0; e < R::kPerThread; ++e) {
-    const int ch = tid + e * kThreads;
-    if (ch < R::kChunks) next[e] = src[ch];
-  }
-}
-
-// One workgroup per meta-frame q0 + blockIdx.x.
+// One workgroup per meta-frame q0 + blockIdx.x (the body, shared with seld_tta.hip: seld_eval_core.h).
 template <bool kBf16>
 __global__ __launch_bounds__(kThreads) void grid_decode_kernel(
     const uint4* __restrict__ logits, long w0, long nw, long W, long total, const int64_t* __restrict__ meta_first,
     const int32_t* __restrict__ meta_len, long q0, float threshold, int K, int32_t* __restrict__ det_cell,
     float* __restrict__ det_score, int32_t* __restrict__ det_count, float* __restrict__ probs_out) {
-  using R = Row<kBf16>;
-  __shared__ uint4 stage[R::kLdsChunks];
-  const int tid = threadIdx.x;
-  const long q = q0 + blockIdx.x;
-  const long first = meta_first[q];
-  const int len = meta_len[q];
-  // a meta-frame whose windows are not all in this launch writes nothing (the host refuses such a call before it
-  // launches; this keeps a direct caller's mistake from reading outside `logits`)
-  if (len < 1 || len > 5 || first < 0 || first + len > total || first_window(first) < w0 ||
-      last_window(first + len - 1, W) >= w0 + nw)
-    return;
-
-  float pacc[kCellsPerThread][kC], facc[kCellsPerThread][kC];
-#pragma unroll
-  for (int t = 0; t < kCellsPerThread; ++t)
-#pragma unroll
-    for (int k = 0; k < kC; ++k) pacc[t][k] = facc[t][k] = 0.0f;
-
-  // rows in (frame ascending, window ascending) order; the next row's 16-byte loads are in flight while this one is
-  // reduced from LDS
-  long f = first, w = first_window(first);
-  u32x4 next[R::kPerThread];
-  load_row<kBf16>(logits, w0, f, w, tid, next);
-  const long f_end = first + len;
-  while (f < f_end) {
-    __syncthreads();                                   // the previous row's readers are done
-#pragma unroll
-    for (int e = 0; e < R::kPerThread; ++e) {
-      const int ch = tid + e * kThreads;
-      if (ch < R::kChunks) reinterpret_cast<u32x4*>(stage)[ch] = next[e];
-    }
-    __syncthreads();
-    const long cur_f = f, cur_w = w;
-    const long w_last = last_window(cur_f, W);
-    if (w < w_last) {
-      ++w;
-    } else {
-      ++f;
-      if (f < f_end) w = first_window(f);
-    }
-    if (f < f_end) load_row<kBf16>(logits, w0, f, w, tid, next);
-#pragma unroll
-    for (int t = 0; t < kCellsPerThread; ++t) {
-      const int cell = tid + t * kThreads;
-      if (cell < kCells) {
-        float p[kC];
-        cell_softmax<kBf16>(stage, cell, p);
-#pragma unroll
-        for (int k = 0; k < kC; ++k) facc[t][k] += p[k];
-      }
-    }
-    if (cur_w == w_last) {                             // frame complete: its mean over the covering windows
-      const float n_w = static_cast<float>(w_last - first_window(cur_f) + 1);
-#pragma unroll
-      for (int t = 0; t < kCellsPerThread; ++t)
-#pragma unroll
-        for (int k = 0; k < kC; ++k) {
-          pacc[t][k] += facc[t][k] / n_w;
-          facc[t][k] = 0.0f;
-        }
-    }
-  }
-
-  // P_q = mean over the meta-frame's frames, into LDS as [cell][13]
-  __syncthreads();
-  float* prob = reinterpret_cast<float*>(stage);
-  const float n_f = static_cast<float>(len);
-#pragma unroll
-  for (int t = 0; t < kCellsPerThread; ++t) {
-    const int cell = tid + t * kThreads;
-    if (cell < kCells)
-#pragma unroll
-      for (int k = 0; k < kC; ++k) prob[cell * kC + k] = pacc[t][k] / n_f;
-  }
-  __syncthreads();
-  const long qi = blockIdx.x;
-  if (probs_out) {
-    float4* dst = reinterpret_cast<float4*>(probs_out + qi * kProbFloats);
-    const float4* s4 = reinterpret_cast<const float4*>(prob);
-    for (int i = tid; i < kProbFloats / 4; i += kThreads) dst[i] = s4[i];
-  }
-
-  // peaks and top-K: wave v takes classes v and v + 8; lane l the cells l + 64 t
-  const int wave = tid >> 6, lane = tid & 63;
-  constexpr int kSlots = (kCells + 63) / 64;           // 11
-  for (int c = wave; c < kC; c += kThreads / 64) {
-    uint32_t peaks = 0;
-#pragma unroll
-    for (int t = 0; t < kSlots; ++t) {
-      const int x = lane + 64 * t;
-      if (x >= kCells) break;
-      const float s = prob[x * kC + c];
-      if (!(s >= threshold)) continue;
-      const int i = x / kJ, j = x - i * kJ;
-      bool peak = true;
-#pragma unroll
-      for (int di = -1; di <= 1; ++di) {
-        const int ii = i + di;
-        if (ii < 0 || ii >= kI) continue;              // no wrap over the poles
-#pragma unroll
-        for (int dj = -1; dj <= 1; ++dj) {
-          if (di == 0 && dj == 0) continue;
-          const int jj = (j + dj + kJ) % kJ;           // azimuth wraps
-          const int y = ii * kJ + jj;
-          const float sy = prob[y * kC + c];
-          peak = peak && (s > sy || (s == sy && x < y));
-        }
-      }
-      if (peak) peaks |= 1u << t;
-    }
-    float prev_s = 0.0f;
-    int prev_c = kCells;                               // nothing selected yet
-    int count = 0;
-    const long out = (qi * kC + c) * K;
-    for (int r = 0; r < K; ++r) {
-      float best_s = 0.0f;
-      int best_c = kCells;
-#pragma unroll
-      for (int t = 0; t < kSlots; ++t) {
-        if (!((peaks >> t) & 1u)) continue;
-        const int x = lane + 64 * t;
-        const float s = prob[x * kC + c];
-        if (prev_c != kCells && !before(prev_s, prev_c, s, x)) continue;   // already taken
-        if (before(s, x, best_s, best_c)) {
-          best_s = s;
-          best_c = x;
-        }
-      }
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        const float os = __shfl_xor(best_s, off);
-        const int oc = __shfl_xor(best_c, off);
-        if (before(os, oc, best_s, best_c)) {
-          best_s = os;
-          best_c = oc;
-        }
-      }
-      if (best_c == kCells) break;                     // wave-uniform
-      if (lane == 0) {
-        det_cell[out + r] = best_c;
-        det_score[out + r] = best_s;
-      }
-      prev_s = best_s;
-      prev_c = best_c;
-      ++count;
-    }
-    if (lane == 0) {
-      for (int r = count; r < K; ++r) {
-        det_cell[out + r] = -1;
-        det_score[out + r] = 0.0f;
-      }
-      det_count[qi * kC + c] = count;
-    }
-  }
+  decode_meta_frame<kBf16, false>(logits, w0, nw, W, total, meta_first, meta_len, q0, threshold, K, det_cell,
+                                  det_score, det_count, probs_out, 0, 1, 0);
 }
 
 // ---- matching ----------------------------------------------------------------------------------------------------

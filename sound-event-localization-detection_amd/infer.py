@@ -1,6 +1,6 @@
 """Inference CLI: recordings -> SELD event CSVs, one per recording (no reference counterpart).
 
-    python infer.py --checkpoint best_model.pth --out-dir DIR a.wav [b.wav ...]
+    python infer.py --checkpoint best_model.pth --out-dir DIR [--tta all | --tta 0,2,9] a.wav [b.wav ...]
 
 Each recording becomes a one-segment timeline (features through the dataset's own path, no metadata rows), its 5 s
 windows run through the checkpoint's model in timeline order, and the decoded events are written to DIR/<stem>.csv as
@@ -17,6 +17,7 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 import dataset  # noqa: E402
+import seld_augment  # noqa: E402
 import seld_eval  # noqa: E402
 import trainer  # noqa: E402
 from utils import safe_torch_load  # noqa: E402
@@ -31,6 +32,9 @@ def parse_args(argv=None):
     p.add_argument("--batch-size", type=int, default=cfg.BATCH_SIZE)
     p.add_argument("--threshold", type=float, default=cfg.SELD_THRESHOLD)
     p.add_argument("--max-peaks", type=int, default=cfg.SELD_MAX_PEAKS)
+    p.add_argument("--tta", default=None,
+                   help="test-time augmentation: 'all' or spatial patterns such as 0,2,9 whose un-permuted grid maps are "
+                        "averaged (one forward per pattern; default: Config.SELD_TTA_PATTERNS)")
     p.add_argument("--device", default=None, help="default: the current ROCm device")
     p.add_argument("--use-ema", action="store_true",
                    help="load the checkpoint's ema_state_dict (default: Config.EVAL_USE_EMA); an error when it has none")
@@ -53,20 +57,22 @@ def main(argv=None):
     model_type = args.model_type or getattr(checkpoint.get("config"), "MODEL_TYPE", None)
     if model_type:
         trainer.config.MODEL_TYPE = model_type
+    patterns = seld_augment.tta_patterns(getattr(trainer.config, "SELD_TTA_PATTERNS", ()) if args.tta is None else args.tta)
     model = None
     written = []
     for wav in args.wavs:
         pcm, rate = _pcm(wav)
         ds = dataset.SELDDataset.from_pcm([pcm], [np.zeros((0, 5), dtype=np.int64)], sample_rate=rate, device=device,
                                           use_gaussian_augmentation=False)
+        seld_augment.check_tta(patterns, getattr(trainer.config, "FEATURE_SET", "logmel"), ds.n_channels)
         if model is None:
             model = trainer.prepare_model_for_device(trainer.build_model((ds.I, ds.J), True, n_channels=ds.n_channels),
                                                      device)
             model.load_state_dict(trainer.select_state_dict(checkpoint, True if args.use_ema else None))
             model.eval()
-        result = seld_eval.evaluate_logits(trainer.timeline_logits(model, ds, args.batch_size, device), ds,
-                                           threshold=args.threshold, max_peaks=args.max_peaks, events_dir=args.out_dir,
-                                           names=[Path(wav).stem])
+        result = seld_eval.evaluate_logits(trainer.timeline_logits(model, ds, args.batch_size, device, patterns=patterns),
+                                           ds, threshold=args.threshold, max_peaks=args.max_peaks, events_dir=args.out_dir,
+                                           names=[Path(wav).stem], patterns=patterns)
         path = result["event_files"][0]
         written.append(path)
         print(f"{wav}: {result['FP']} events -> {path}")

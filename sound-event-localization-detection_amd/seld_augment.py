@@ -145,6 +145,56 @@ def identity_rows(n: int) -> np.ndarray:
     return np.zeros((int(n), PARAM_INTS), dtype=np.int32)
 
 
+# ------------------------------------------------------------------------------------------ test-time augmentation
+
+def tta_patterns(spec) -> tuple:
+    """The pattern list of test-time augmentation from a Config value or a command-line string:
+    None, (), 0, False and "" give () (off); "all" the 16 patterns; an iterable of ints or a comma-separated string is
+    checked (each in 0..15, no duplicates) and its order kept."""
+    if spec is None or spec is False or (isinstance(spec, (int, np.integer)) and not isinstance(spec, bool) and spec == 0):
+        return ()
+    if spec is True:
+        raise ValueError("test-time augmentation patterns: True names no list; use 'all' or the patterns")
+    if isinstance(spec, str):
+        text = spec.strip()
+        if text.lower() == "all":
+            return tuple(range(PATTERNS))
+        if text == "":
+            return ()
+        try:
+            spec = [int(part) for part in text.split(",")]
+        except ValueError:
+            raise ValueError(f"test-time augmentation patterns must be 'all' or comma-separated integers, got {text!r}") from None
+    elif isinstance(spec, (int, np.integer)):
+        spec = [spec]
+    out = []
+    for value in spec:
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+            raise ValueError(f"test-time augmentation pattern {value!r} is not an integer")
+        decode(value)
+        if int(value) in out:
+            raise ValueError(f"test-time augmentation pattern {int(value)} is listed twice")
+        out.append(int(value))
+    return tuple(out)
+
+
+def tta_rows(p: int, n: int) -> np.ndarray:
+    """int32 [n, 12] parameter rows of n windows under spatial pattern p and no masks."""
+    decode(p)
+    rows = identity_rows(n)
+    rows[:, 0] = int(p)
+    return rows
+
+
+def check_tta(patterns, feature_set: str, n_channels: int):
+    """Raise ValueError when a non-empty pattern list meets a feature set without a defined channel swap."""
+    if patterns and not spatial_supported(feature_set, int(n_channels)):
+        raise ValueError(
+            f"test-time augmentation over the spatial patterns is defined for 4-channel FOA features ('logmel' with 4 "
+            f"channels, 'logmel_iv'), not for FEATURE_SET={feature_set!r} with {n_channels} feature channels: a microphone "
+            f"array's geometry is unknown here, so no channel swap is defined")
+
+
 def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, bins: int = N_BINS) -> np.ndarray:
     """int32 [B, 12] parameter rows for the windows ``window_indices`` (dataset window indices) of ``epoch``.
 

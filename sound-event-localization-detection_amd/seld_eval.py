@@ -7,6 +7,11 @@ definitions are this project's, DESIGN.md section 10.  The hot paths are two HIP
                      the frames of each 100 ms meta-frame, 3x3 peak test per class, top-K per (meta-frame, class)
   seld_doa_match     per (meta-frame, class): minimum-cost assignment and maximum matching within the DOA threshold
 
+Test-time augmentation (csrc/seld_tta.hip): ``patterns`` on decode / evaluate_logits switches to
+
+  seld_grid_decode_tta   the same pass over one stack of logits per spatial pattern, each un-permuted to the original
+                         frame as it is read, averaged before the peak test
+
 The host side here builds the tables (meta-frames, reference CSR), drives the decode batch by batch as the windows are
 computed, reduces the match counts on the device and writes event CSVs.  There is no CPU fallback.
 """
@@ -125,6 +130,47 @@ def grid_decode(logits: torch.Tensor, w0: int, table: MetaFrameTable, q0: int, n
     return out
 
 
+def grid_decode_tta(logits: torch.Tensor, patterns, w0: int, table: MetaFrameTable, q0: int, nq: int, threshold: float,
+                    max_peaks: int, out=None, probs: torch.Tensor | None = None):
+    """seld_grid_decode_tta: ``grid_decode`` over ``logits`` [P, nw, 250, 648, 14], stack n holding windows
+    [w0, w0 + nw) gathered with spatial pattern ``patterns[n]``; the stacks are averaged in the original frame
+    (DESIGN.md section 13).  ``out`` / ``probs`` and the coverage check as ``grid_decode``; the pattern list itself is
+    checked by the library (SeldNativeError)."""
+    if not logits.is_cuda:
+        raise SeldNativeError("grid_decode_tta: logits must live on the GPU (no CPU fallback)")
+    if logits.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("grid_decode_tta: logits must be bfloat16 or float32")
+    if logits.dim() != 5 or tuple(logits.shape[2:]) != (WIN, GRID_I * GRID_J, NUM_EVENT_CLASSES + 1):
+        raise ValueError(f"grid_decode_tta: logits must be [P, nw, {WIN}, 648, 14], got {tuple(logits.shape)}")
+    pats = np.asarray(list(patterns), dtype=np.int32).reshape(-1)
+    if int(logits.shape[0]) != len(pats):
+        raise ValueError(f"grid_decode_tta: {int(logits.shape[0])} stacks of logits for {len(pats)} patterns")
+    logits = logits.contiguous()
+    nw = int(logits.shape[1])
+    if not (q0 >= 0 and nq >= 0 and q0 + nq <= len(table)):
+        raise ValueError("grid_decode_tta: meta-frame range outside the table")
+    if nq:
+        lo, hi = int(table.first_window[q0:q0 + nq].min()), int(table.last_window[q0:q0 + nq].max())
+        if lo < w0 or hi >= w0 + nw:
+            raise SeldNativeError(f"grid_decode_tta: meta-frames {q0}..{q0 + nq - 1} need windows {lo}..{hi}, the call "
+                                  f"holds {w0}..{w0 + nw - 1}")
+    device = logits.device
+    index = ensure_init(device)
+    k = int(max_peaks)
+    if out is None:
+        out = (torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.int32, device=device),
+               torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.float32, device=device),
+               torch.empty((nq, NUM_EVENT_CLASSES), dtype=torch.int32, device=device))
+    first, length = table.device(device)
+    with _device_guard(index):
+        check(load_library().seld_grid_decode_tta(_p(logits), int(logits.dtype == torch.bfloat16), int(w0), nw,
+                                                  table.windows, table.total, _p(first), _p(length), int(q0), int(nq),
+                                                  pats.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(pats),
+                                                  float(threshold), k, _p(out[0]), _p(out[1]), _p(out[2]), _p(probs),
+                                                  _stream_ptr(device)), "seld_grid_decode_tta")
+    return out
+
+
 def doa_match(det_cell: torch.Tensor, det_count: torch.Tensor, ref_offsets: torch.Tensor, ref_dirs: torch.Tensor,
               doa_threshold_deg: float, I: int = GRID_I, J: int = GRID_J):
     """seld_doa_match: (stats int32 [Q, 13, 4] = (R, P, k, tp), cost f64 [Q, 13]) on the detections' device.  A pair is
@@ -150,13 +196,18 @@ def doa_match(det_cell: torch.Tensor, det_count: torch.Tensor, ref_offsets: torc
 
 # ------------------------------------------------------------------------------------------------------ decode driver
 
-def decode(batches, table: MetaFrameTable, threshold: float, max_peaks: int, device=None, keep_probs: bool = False):
+def decode(batches, table: MetaFrameTable, threshold: float, max_peaks: int, device=None, keep_probs: bool = False,
+           patterns=None):
     """Streaming decode of a whole timeline.  ``batches`` yields logit tensors [B, 250, 648, 14] of consecutive windows
     in timeline order (window 0 first, ``table.windows`` in all).  After each batch every meta-frame whose last
     covering window has been seen is decoded; the last KEEP_WINDOWS windows stay on the device for the next call.
     Returns (det_cell int32 [Q, 13, K], det_score f32 [Q, 13, K], det_count int32 [Q, 13], probs f32 [Q, 648, 13] or
-    None) on the device."""
+    None) on the device.
+    ``patterns``: a non-empty list of spatial patterns switches to test-time augmentation: the batches are then
+    [P, B, 250, 648, 14], stack n under ``patterns[n]``, and every call goes to ``grid_decode_tta``."""
     k = int(max_peaks)
+    patterns = tuple(patterns) if patterns is not None else ()
+    wdim = 1 if patterns else 0                  # the window axis of a batch
     if not 1 <= k <= MAX_PEAKS:
         raise ValueError(f"max_peaks must be in 1..{MAX_PEAKS}, got {max_peaks}")
     n_q = len(table)
@@ -174,16 +225,23 @@ def decode(batches, table: MetaFrameTable, threshold: float, max_peaks: int, dev
                 probs = torch.empty((n_q, GRID_I * GRID_J, NUM_EVENT_CLASSES), dtype=torch.float32, device=device)
         if batch.dtype not in (torch.bfloat16, torch.float32):
             batch = batch.float()
-        held = batch if carry is None else torch.cat([carry, batch.to(carry.dtype)], dim=0)
-        w0 = seen - (0 if carry is None else int(carry.shape[0]))
-        seen += int(batch.shape[0])
+        held = batch if carry is None else torch.cat([carry, batch.to(carry.dtype)], dim=wdim)
+        w0 = seen - (0 if carry is None else int(carry.shape[wdim]))
+        seen += int(batch.shape[wdim])
         end = int(np.searchsorted(table.last_window, seen - 1, side="right"))
         if end > done:
-            grid_decode(held, w0, table, done, end - done, threshold, k,
-                        out=(det[0][done:end], det[1][done:end], det[2][done:end]),
-                        probs=probs[done:end] if probs is not None else None)
+            out = (det[0][done:end], det[1][done:end], det[2][done:end])
+            if patterns:
+                grid_decode_tta(held, patterns, w0, table, done, end - done, threshold, k, out=out,
+                                probs=probs[done:end] if probs is not None else None)
+            else:
+                grid_decode(held, w0, table, done, end - done, threshold, k, out=out,
+                            probs=probs[done:end] if probs is not None else None)
             done = end
-        carry = held[-KEEP_WINDOWS:]
+        if patterns:            # (a producer may reuse its [P, B, ...] buffer: the first carry is still a view of the batch)
+            carry = held[:, -KEEP_WINDOWS:].clone() if held is batch else held[:, -KEEP_WINDOWS:]
+        else:
+            carry = held[-KEEP_WINDOWS:]
     if seen != table.windows or done != n_q:
         raise ValueError(f"decode: the timeline has {table.windows} windows, got {seen}")
     if det is None:             # an empty timeline
@@ -298,13 +356,16 @@ def segment_names(dataset):
 # ------------------------------------------------------------------------------------------------------ entry point
 
 def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_threshold_deg=None, events_dir=None,
-                    names=None) -> dict:
+                    names=None, patterns=None) -> dict:
     """Decode + score for any iterator of logit batches [B, 250, 648, 14] that covers ``dataset``'s windows in order.
     ``dataset``: an SELDDataset (``segments``, ``metadata_rows``, ``total_frames``, ``I``, ``J``, ``device``).  Defaults
     come from Config (SELD_THRESHOLD, SELD_MAX_PEAKS, SELD_DOA_THRESHOLD_DEG).  Returns F20, ER20, LE_CD, LR_CD, TP, FP,
     FN, N, per_class (plus S, D, I, matched and the settings); with ``events_dir`` one CSV per segment, named after
-    ``names`` or the audio stems, listed under "event_files"."""
+    ``names`` or the audio stems, listed under "event_files".
+    ``patterns``: test-time augmentation (``decode``): the batches are [P, B, 250, 648, 14]; the result's "tta_patterns"
+    lists them ([] when off)."""
     from config import Config
+    patterns = tuple(int(p) for p in patterns) if patterns is not None else ()
     threshold = Config.SELD_THRESHOLD if threshold is None else threshold
     max_peaks = Config.SELD_MAX_PEAKS if max_peaks is None else max_peaks
     doa_threshold_deg = Config.SELD_DOA_THRESHOLD_DEG if doa_threshold_deg is None else doa_threshold_deg
@@ -312,9 +373,10 @@ def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_thresh
         raise NotImplementedError(f"the decode kernel is built for the {GRID_I} x {GRID_J} grid, got "
                                   f"{dataset.I} x {dataset.J}")
     table = meta_frame_table(dataset.segments, dataset.total_frames)
-    det_cell, _, det_count, _ = decode(batches, table, threshold, max_peaks, device=dataset.device)
+    det_cell, _, det_count, _ = decode(batches, table, threshold, max_peaks, device=dataset.device, patterns=patterns)
     result = match_and_score(det_cell, det_count, table, dataset.metadata_rows, doa_threshold_deg, dataset.I, dataset.J)
-    result.update(threshold=float(threshold), max_peaks=int(max_peaks), doa_threshold_deg=float(doa_threshold_deg))
+    result.update(threshold=float(threshold), max_peaks=int(max_peaks), doa_threshold_deg=float(doa_threshold_deg),
+                  tta_patterns=list(patterns))
     if events_dir is not None:
         names = segment_names(dataset) if names is None else list(names)
         cells, counts = det_cell.cpu().numpy(), det_count.cpu().numpy()

@@ -1058,11 +1058,26 @@ def test_model(test_loader, model_path=None, batch_size=None, device=None, num_v
 # evaluate_seld: detections and SELD metrics (no reference counterpart; seld_eval.py)
 # ------------------------------------------------------------------------------------------------
 
-def timeline_logits(model, dataset, batch_size, device):
+def timeline_logits(model, dataset, batch_size, device, patterns=None):
     """The model's logits [B, 250, 648, 14] for every window of ``dataset`` in timeline order, one batch at a time (eval
-    mode is the caller's; autocast as in training).  Windows come from the device timeline when the dataset keeps one."""
-    n = len(dataset)
+    mode is the caller's; autocast as in training).  Windows come from the device timeline when the dataset keeps one.
+    ``patterns``: a non-empty list of spatial patterns (test-time augmentation) yields
+    [P, B, 250, 648, 14] instead: every batch of windows is gathered once per pattern by the augmenting gather (channel
+    table row of the pattern, no masks; its permuted labels are not used) and the model runs once per pattern on a batch
+    of the usual size, into one buffer that is reused from batch to batch -- a yielded tensor is valid until the next
+    one is asked for.  Needs the device timeline (no CPU fallback)."""
     on_device = device.type == "cuda" and getattr(dataset, "spec_tm", None) is not None
+    patterns = seld_augment.tta_patterns(patterns)
+    if not patterns:
+        return _plain_logits(model, dataset, batch_size, device, on_device)
+    if not on_device:
+        raise RuntimeError("test-time augmentation gathers its windows on the GPU: it needs a ROCm device and a dataset "
+                           "that keeps its device timeline (keep_on_device=True); there is no CPU fallback")
+    return _tta_logits(model, dataset, batch_size, device, patterns)
+
+
+def _plain_logits(model, dataset, batch_size, device, on_device):
+    n = len(dataset)
     for lo in range(0, n, batch_size):
         idx = list(range(lo, min(lo + batch_size, n)))
         if on_device:
@@ -1074,15 +1089,36 @@ def timeline_logits(model, dataset, batch_size, device):
         yield logits
 
 
+def _tta_logits(model, dataset, batch_size, device, patterns):
+    n = len(dataset)
+    stacks = None
+    for lo in range(0, n, batch_size):
+        idx = list(range(lo, min(lo + batch_size, n)))
+        for k, p in enumerate(patterns):
+            spec, _ = dataset.device_batch(idx, augment=seld_augment.tta_rows(p, len(idx)))
+            with torch.no_grad(), autocast_context(device):
+                logits = model(spec)
+            if stacks is None:
+                stacks = torch.empty((len(patterns), min(batch_size, n)) + tuple(logits.shape[1:]), dtype=logits.dtype,
+                                     device=logits.device)
+            stacks[k, :len(idx)] = logits
+        yield stacks[:, :len(idx)]
+
+
 def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, threshold=None, max_peaks=None,
-                  doa_threshold_deg=None, events_dir=None, use_ema=None):
+                  doa_threshold_deg=None, events_dir=None, use_ema=None, tta=None):
     """Evaluate a checkpoint on what it detects: the windows of ``test_loader.dataset`` (an SELDDataset) run through the
     model in timeline order, the overlapping grid maps are decoded into DOA events on the GPU and scored against the
     dataset's CSV rows.  Returns F20, ER20, LE_CD, LR_CD, TP, FP, FN, N, per_class (seld_eval.evaluate_logits); with
     ``events_dir`` one event CSV per file, named after its audio stem.  The checkpoint is loaded as test_model loads it;
-    runs on rank 0 only."""
+    runs on rank 0 only.
+    ``tta``: the spatial patterns of test-time augmentation (seld_augment.tta_patterns: "all", a list, or () for off;
+    None reads Config.SELD_TTA_PATTERNS): the model runs on every transformed copy of a window and the un-permuted grid
+    maps are averaged before the peak test; the result's "tta_patterns" lists them."""
     import seld_eval
     test_dataset = test_loader.dataset
+    patterns = seld_augment.tta_patterns(getattr(config, "SELD_TTA_PATTERNS", ()) if tta is None else tta)
+    seld_augment.check_tta(patterns, getattr(config, "FEATURE_SET", "logmel"), getattr(test_dataset, "n_channels", 0))
     batch_size = batch_size or getattr(test_loader, "batch_size", None) or config.BATCH_SIZE
     model_path = Path(model_path or (config.CHECKPOINT_PATH / "best_model.pth"))
     device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -1099,9 +1135,11 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
     model.load_state_dict(select_state_dict(checkpoint, use_ema))
     model.eval()
     logger.info(f"SELD evaluation: {len(test_dataset)} windows, checkpoint epoch {checkpoint['epoch']}")
-    results = seld_eval.evaluate_logits(timeline_logits(model, test_dataset, batch_size, device), test_dataset,
-                                        threshold=threshold, max_peaks=max_peaks, doa_threshold_deg=doa_threshold_deg,
-                                        events_dir=events_dir)
+    if patterns:
+        logger.info(f"test-time augmentation: {len(patterns)} forwards per window, spatial patterns {list(patterns)}")
+    results = seld_eval.evaluate_logits(timeline_logits(model, test_dataset, batch_size, device, patterns=patterns),
+                                        test_dataset, threshold=threshold, max_peaks=max_peaks,
+                                        doa_threshold_deg=doa_threshold_deg, events_dir=events_dir, patterns=patterns)
     results["checkpoint_epoch"] = checkpoint["epoch"]
     logger.info(f"F20 {results['F20']:.4f}  ER20 {results['ER20']:.4f}  LE_CD {results['LE_CD']:.2f} deg  "
                 f"LR_CD {results['LR_CD']:.4f}  (TP {results['TP']}, FP {results['FP']}, FN {results['FN']}, "
