@@ -534,6 +534,32 @@ int seld_grid_decode_tta(const void* logits, int is_bf16, int64_t w0, int64_t nw
                          const int32_t* patterns, int n_patterns, float threshold, int K, int32_t* det_cell,
                          float* det_score, int32_t* det_count, float* probs_out, void* stream);
 
+/* ---- track linking of the decoded detections (csrc/seld_track.hip) ---------------------------
+ * seld_track_link: detections as seld_grid_decode writes them (det_cell [Q][13][K], det_count [Q][13]; a count above K is
+ * K, a cell outside [0, I*J) ends its list) -> event tracks.  A chain is one (segment s, class c), x = 13 s + c, its
+ * frames m = 0..M_s-1 at q = seg_offsets[s] + m (seg_offsets int64 [S+1], device), walked in ascending m; chains are
+ * independent.  dist(a, b) = dist_table[i_a][i_b][(j_b - j_a) mod J] (int32 [I][I][J], device, I*I*J <= 16384):
+ * milli-degrees between the cell centres, built by the host.  Per chain 8 slots, free or (id, cell, first_m, last_m),
+ * next_id = 0.  At frame m with detections d_0..d_{n-1} in rank order:
+ *   1. a slot with m - last_m > max_gap + 1 becomes free;
+ *   2. candidates: (occupied slot t, rank r) with dist(slot.cell, d_r) <= gate_mdeg, taken in ascending (dist, t, r)
+ *      when neither t nor r has been taken this frame: emit (id, slot.cell) at every frame last_m+1..m-1 (the fill),
+ *      then slot.cell = d_r, last_m = m, emit (id, d_r) at m;
+ *   3. each unlinked detection in rank order takes the lowest free slot, else the slot not linked this frame with the
+ *      smallest last_m (lowest index on ties; that track ends): id = next_id++, first_m = last_m = m, emit (id, d_r).
+ * A track with last_m - first_m + 1 < min_len is removed, fills included.  Outputs: trk_cell / trk_id int32 [Q][13][8]
+ * = the surviving emissions of (q, c) in ascending id, -1 past trk_count int32 [Q][13]; tracks int32 [T][4] =
+ * (first_m, last_m, detected frames, kept), track id of chain x at row chain_offsets[x] + id (chain_offsets int64
+ * [13 S + 1], device: the exclusive prefix sum of the chains' detection counts, an upper bound on their tracks; rows no
+ * track uses are not written); chain_tracks int32 [13 S] = next_id.  trk_cell, trk_id and tracks 16-byte aligned.
+ * Two launches (the chain walk, one wavefront per chain; filter and compaction, one thread per (q, c)), integer
+ * arithmetic, plain stores in a fixed order: exact and independent of the schedule.  No allocation, no synchronise.
+ * -1, launching nothing, for K outside 1..8, max_gap outside 0..16, min_len < 1, gate_mdeg < 0 or a null pointer. */
+int seld_track_link(const int32_t* det_cell, const int32_t* det_count, int K, const int64_t* seg_offsets, int64_t S,
+                    const int32_t* dist_table, int I, int J, int gate_mdeg, int max_gap, int min_len,
+                    const int64_t* chain_offsets, int32_t* trk_cell, int32_t* trk_id, int32_t* trk_count, int32_t* tracks,
+                    int32_t* chain_tracks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,12 @@ class Config:
     SELD_TTA_PATTERNS = ()      # test-time augmentation in evaluate_seld / infer.py: the spatial patterns (0..15, section 11.1)
                                 # whose un-permuted grid maps are averaged before the peak test; () = off, "all" = the
                                 # 16, or a list such as (0, 2, 9).  One forward per pattern; 4-channel FOA features only
+    # Track linking of the decoded detections (seld_eval.track, csrc/seld_track.hip)
+    SELD_TRACK = False          # evaluate_seld / infer.py link the frame-wise detections into tracks: the CSV's third column is
+                                # then a track id, short tracks are dropped, short gaps filled
+    SELD_TRACK_GATE_DEG = 20    # a detection continues a track when it lies within this great-circle angle of its last cell
+    SELD_TRACK_MAX_GAP = 2      # a track survives this many meta-frames without a detection (they are filled), 0..16
+    SELD_TRACK_MIN_LEN = 3      # tracks spanning fewer meta-frames (onset to offset) are removed
 
     def __init__(self):
         for folder in (self.OUTPUT_PATH, self.CHECKPOINT_PATH):

@@ -1,10 +1,12 @@
 """Inference CLI: recordings -> SELD event CSVs, one per recording (no reference counterpart).
 
-    python infer.py --checkpoint best_model.pth --out-dir DIR [--tta all | --tta 0,2,9] a.wav [b.wav ...]
+    python infer.py --checkpoint best_model.pth --out-dir DIR [--tta all | --tta 0,2,9] [--track] a.wav [b.wav ...]
 
 Each recording becomes a one-segment timeline (features through the dataset's own path, no metadata rows), its 5 s
 windows run through the checkpoint's model in timeline order, and the decoded events are written to DIR/<stem>.csv as
-``meta_frame,class,rank,azimuth,elevation`` rows -- the metadata format the dataset reads.
+``meta_frame,class,rank,azimuth,elevation`` rows -- the metadata format the dataset reads.  With ``--track`` the
+detections are linked into tracks first: the third column is the track id, and DIR/<stem>.tracks.csv
+lists ``class,track,onset_m,offset_m,detected_frames`` of every kept track.
 """
 import argparse
 import logging
@@ -35,6 +37,15 @@ def parse_args(argv=None):
     p.add_argument("--tta", default=None,
                    help="test-time augmentation: 'all' or spatial patterns such as 0,2,9 whose un-permuted grid maps are "
                         "averaged (one forward per pattern; default: Config.SELD_TTA_PATTERNS)")
+    p.add_argument("--track", action=argparse.BooleanOptionalAction, default=bool(getattr(cfg, "SELD_TRACK", False)),
+                   help="link the detections into tracks: CSV column 3 becomes a track id, <stem>.tracks.csv lists the tracks "
+                        "(default: Config.SELD_TRACK; --no-track switches it off)")
+    p.add_argument("--track-gate-deg", type=float, default=cfg.SELD_TRACK_GATE_DEG,
+                   help="a detection continues a track within this angle of its last cell")
+    p.add_argument("--track-max-gap", type=int, default=cfg.SELD_TRACK_MAX_GAP,
+                   help="meta-frames a track survives without a detection (filled), 0..16")
+    p.add_argument("--track-min-len", type=int, default=cfg.SELD_TRACK_MIN_LEN,
+                   help="tracks spanning fewer meta-frames are removed")
     p.add_argument("--device", default=None, help="default: the current ROCm device")
     p.add_argument("--use-ema", action="store_true",
                    help="load the checkpoint's ema_state_dict (default: Config.EVAL_USE_EMA); an error when it has none")
@@ -58,6 +69,8 @@ def main(argv=None):
     if model_type:
         trainer.config.MODEL_TYPE = model_type
     patterns = seld_augment.tta_patterns(getattr(trainer.config, "SELD_TTA_PATTERNS", ()) if args.tta is None else args.tta)
+    track = {"gate_deg": args.track_gate_deg, "max_gap": args.track_max_gap, "min_len": args.track_min_len} \
+        if args.track else False
     model = None
     written = []
     for wav in args.wavs:
@@ -72,10 +85,14 @@ def main(argv=None):
             model.eval()
         result = seld_eval.evaluate_logits(trainer.timeline_logits(model, ds, args.batch_size, device, patterns=patterns),
                                            ds, threshold=args.threshold, max_peaks=args.max_peaks, events_dir=args.out_dir,
-                                           names=[Path(wav).stem], patterns=patterns)
+                                           names=[Path(wav).stem], patterns=patterns, track=track)
         path = result["event_files"][0]
         written.append(path)
-        print(f"{wav}: {result['FP']} events -> {path}")
+        if result["tracking"]:
+            print(f"{wav}: {result['FP']} events of {result['tracking']['tracks_kept']} tracks -> {path}, "
+                  f"{result['track_files'][0]}")
+        else:
+            print(f"{wav}: {result['FP']} events -> {path}")
     return written
 
 

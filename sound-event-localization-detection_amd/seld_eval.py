@@ -12,6 +12,11 @@ Test-time augmentation (csrc/seld_tta.hip): ``patterns`` o
   seld_grid_decode_tta   the same pass over one stack of logits per spatial pattern, each un-permuted to the original
                          frame as it is read, averaged before the peak test
 
+Track linking (csrc/seld_track.hip): ``track`` on evaluate_logits puts between decode and match
+
+  seld_track_link        one wavefront per (segment, class) links the frame-wise peaks into tracks with an identity over
+                         time: gated greedy nearest-cell linking, gap filling, a minimum duration, onset / offset
+
 The host side here builds the tables (meta-frames, reference CSR), drives the decode batch by batch as the windows are
 computed, reduces the match counts on the device and writes event CSVs.  There is no CPU fallback.
 """
@@ -82,6 +87,14 @@ class MetaFrameTable:
         if key not in self._device:
             self._device[key] = (torch.from_numpy(self.first.copy()).to(device),
                                  torch.from_numpy(self.length.copy()).to(device))
+        return self._device[key]
+
+    def device_segments(self, device):
+        """(seg_offsets int64 [S + 1], segment int64 [Q]) on ``device``, uploaded once."""
+        key = ("segments", str(device))
+        if key not in self._device:
+            self._device[key] = (torch.from_numpy(self.seg_offsets.astype(np.int64)).to(device),
+                                 torch.from_numpy(self.segment.astype(np.int64)).to(device))
         return self._device[key]
 
 
@@ -192,6 +205,119 @@ def doa_match(det_cell: torch.Tensor, det_count: torch.Tensor, ref_offsets: torc
                                             _p(dirs), q, int(I), int(J), float(doa_threshold_deg) + DOA_MARGIN_DEG,
                                             _p(stats), _p(cost), _stream_ptr(device)), "seld_doa_match")
     return stats, cost
+
+
+# ------------------------------------------------------------------------------------------------------ tracking
+
+_distance_tables = {}
+
+
+def _distance_table_host(I: int, J: int) -> np.ndarray:
+    """int32 [I, I, J]: rint(1000 d), d the float64 great-circle angle in degrees between the centres of cells (i_a, j_a)
+    and (i_b, j_b) by the atan2 form of DESIGN.md 10.1, indexed (i_a, i_b, (j_b - j_a) mod J)."""
+    rad = np.pi / 180.0
+    el = (-90.0 + (np.arange(I, dtype=np.float64) + 0.5) * (180.0 / I)) * rad
+    az = (np.arange(J, dtype=np.float64) * (360.0 / J)) * rad             # j_b - j_a cells of azimuth
+    e1, e2, a2 = np.broadcast_arrays(el[:, None, None], el[None, :, None], az[None, None, :])
+    u = np.stack([np.cos(e1), np.zeros_like(e1), np.sin(e1)], -1)
+    v = np.stack([np.cos(e2) * np.cos(a2), np.cos(e2) * np.sin(a2), np.sin(e2)], -1)
+    cr = np.cross(u, v)
+    d = np.arctan2(np.sqrt((cr ** 2).sum(-1)), (u * v).sum(-1)) * (180.0 / np.pi)
+    d[np.arange(I), np.arange(I), 0] = 0.0                                 # identical cells are exactly 0
+    return np.rint(1000.0 * d).astype(np.int32)
+
+
+def track_distance_table(I: int = GRID_I, J: int = GRID_J, device=None) -> torch.Tensor:
+    """The cell-to-cell distance table of the track kernel in milli-degrees, int32 [I, I, J]; built once with numpy and
+    cached per device (``device`` None: the host copy)."""
+    host_key, key = (int(I), int(J), None), (int(I), int(J), None if device is None else str(device))
+    if host_key not in _distance_tables:
+        _distance_tables[host_key] = torch.from_numpy(_distance_table_host(int(I), int(J)))
+    if key not in _distance_tables:
+        _distance_tables[key] = _distance_tables[host_key].to(device)
+    return _distance_tables[key]
+
+
+def track_settings(track) -> dict | None:
+    """``track`` as evaluate_logits takes it -> {gate_deg, max_gap, min_len} or None (off).  None reads Config.SELD_TRACK;
+    True or a dict switches tracking on, a dict's keys override the Config.SELD_TRACK_* defaults."""
+    from config import Config
+    if track is None:
+        track = bool(getattr(Config, "SELD_TRACK", False))
+    if track is False:
+        return None
+    settings = {"gate_deg": float(Config.SELD_TRACK_GATE_DEG), "max_gap": int(Config.SELD_TRACK_MAX_GAP),
+                "min_len": int(Config.SELD_TRACK_MIN_LEN)}
+    if isinstance(track, dict):
+        unknown = set(track) - set(settings)
+        if unknown:
+            raise ValueError(f"track: unknown keys {sorted(unknown)}; expected gate_deg, max_gap, min_len")
+        settings.update(gate_deg=float(track.get("gate_deg", settings["gate_deg"])),
+                        max_gap=int(track.get("max_gap", settings["max_gap"])),
+                        min_len=int(track.get("min_len", settings["min_len"])))
+    elif track is not True:
+        raise TypeError("track must be None, a bool or a dict")
+    return settings
+
+
+def track(det_cell: torch.Tensor, det_count: torch.Tensor, table: MetaFrameTable, gate_deg: float, max_gap: int,
+          min_len: int, I: int = GRID_I, J: int = GRID_J):
+    """seld_track_link: the decode's outputs det_cell int32 [Q, 13, K] / det_count int32 [Q, 13] of
+    the timeline of ``table`` -> (trk_cell int32 [Q, 13, 8], trk_id int32 [Q, 13, 8], trk_count int32 [Q, 13], tracks
+    int32 [T, 4] = (first_m, last_m, detected, kept), chain_tracks int32 [13 S], chain_offsets int64 [13 S + 1]) on the
+    detections' device.  Track ``id`` of chain x = 13 s + c is row chain_offsets[x] + id; rows no track uses are 0."""
+    if not (det_cell.is_cuda and det_count.is_cuda):
+        raise SeldNativeError("track: detections must live on the GPU (no CPU fallback)")
+    if det_cell.dim() != 3 or det_cell.shape[1] != NUM_EVENT_CLASSES or tuple(det_count.shape) != tuple(det_cell.shape[:2]):
+        raise ValueError("track: det_cell must be [Q, 13, K] and det_count [Q, 13]")
+    q, k = int(det_cell.shape[0]), int(det_cell.shape[2])
+    if q != len(table):
+        raise ValueError(f"track: {q} meta-frames of detections for a timeline of {len(table)}")
+    device = det_cell.device
+    index = ensure_init(device)
+    gate_mdeg = int(np.rint(1000.0 * float(gate_deg)))
+    det_cell, det_count = det_cell.to(torch.int32).contiguous(), det_count.to(torch.int32).contiguous()
+    n_seg = len(table.seg_offsets) - 1
+    seg_offsets, segment = table.device_segments(device)
+    # detections per chain (segment, class): an integer index_add over the meta-frames (a scan along the timeline costs
+    # four times the track kernels)
+    per_chain = torch.zeros((n_seg, NUM_EVENT_CLASSES), dtype=torch.int64, device=device)
+    per_chain.index_add_(0, segment, det_count.clamp(0, max(k, 0)).to(torch.int64))
+    per_chain = per_chain.reshape(-1)
+    chain_offsets = torch.zeros(n_seg * NUM_EVENT_CLASSES + 1, dtype=torch.int64, device=device)
+    chain_offsets[1:] = torch.cumsum(per_chain, 0)
+    rank = torch.arange(k, dtype=torch.int32, device=device)
+    stray = ((det_cell < 0) | (det_cell >= int(I) * int(J))) & (rank < det_count[..., None])
+    total, stray = (int(v) for v in torch.stack([chain_offsets[-1], stray.sum()]).tolist())    # the one host read
+    if stray:
+        raise ValueError(f"track: {stray} detections lie outside the {I} x {J} grid")
+    trk_cell = torch.empty((q, NUM_EVENT_CLASSES, MAX_PEAKS), dtype=torch.int32, device=device)
+    trk_id = torch.empty((q, NUM_EVENT_CLASSES, MAX_PEAKS), dtype=torch.int32, device=device)
+    trk_count = torch.empty((q, NUM_EVENT_CLASSES), dtype=torch.int32, device=device)
+    tracks = torch.zeros((max(total, 1), 4), dtype=torch.int32, device=device)
+    chain_tracks = torch.zeros(max(n_seg * NUM_EVENT_CLASSES, 1), dtype=torch.int32, device=device)
+    dist = track_distance_table(I, J, device)
+    if q == 0:                                              # an empty timeline: nothing to launch
+        return trk_cell, trk_id, trk_count, tracks[:0], chain_tracks[:n_seg * NUM_EVENT_CLASSES], chain_offsets
+    with _device_guard(index):
+        check(load_library().seld_track_link(_p(det_cell), _p(det_count), k, _p(seg_offsets), n_seg, _p(dist), int(I),
+                                             int(J), gate_mdeg, int(max_gap), int(min_len), _p(chain_offsets),
+                                             _p(trk_cell), _p(trk_id), _p(trk_count), _p(tracks), _p(chain_tracks),
+                                             _stream_ptr(device)), "seld_track_link")
+    return trk_cell, trk_id, trk_count, tracks[:total], chain_tracks[:n_seg * NUM_EVENT_CLASSES], chain_offsets
+
+
+_track_link = track        # (evaluate_logits has a parameter of that name)
+
+
+def track_summary(trk_count: torch.Tensor, tracks: torch.Tensor, chain_tracks: torch.Tensor) -> dict:
+    """Counts of one ``track`` call, reduced on the device: tracks born, tracks kept, removed (shorter than min_len) and
+    filled = emissions of kept tracks at frames where they were not detected."""
+    t = tracks.to(torch.int64)
+    sums = torch.stack([chain_tracks.to(torch.int64).sum(), t[:, 3].sum(), (t[:, 2] * t[:, 3]).sum(),
+                        trk_count.to(torch.int64).sum()]).cpu().tolist()
+    born, kept, detected, emitted = (int(v) for v in sums)
+    return {"tracks": born, "tracks_kept": kept, "filled": emitted - detected, "removed": born - kept}
 
 
 # ------------------------------------------------------------------------------------------------------ decode driver
@@ -321,9 +447,12 @@ def match_and_score(det_cell: torch.Tensor, det_count: torch.Tensor, table: Meta
 
 # ------------------------------------------------------------------------------------------------------ events
 
-def events_for_segment(det_cell, det_count, table: MetaFrameTable, segment: int, I: int = GRID_I, J: int = GRID_J):
+def events_for_segment(det_cell, det_count, table: MetaFrameTable, segment: int, I: int = GRID_I, J: int = GRID_J,
+                       ids=None):
     """Event rows of one segment: int32 [R, 5] = (meta_frame, class, rank, azimuth, elevation) in (m, c, rank) order,
-    the DOA being the detection's cell centre (integer degrees on the 10-degree grid)."""
+    the DOA being the detection's cell centre (integer degrees on the 10-degree grid).
+    ``ids``: the track ids that go with ``det_cell`` (``track``'s trk_id next to trk_cell / trk_count); the third column
+    is then the track id, rows in (m, c, id) order -- the order ``track`` writes them in."""
     lo, hi = int(table.seg_offsets[segment]), int(table.seg_offsets[segment + 1])
     cells = det_cell[lo:hi].cpu().numpy() if torch.is_tensor(det_cell) else np.asarray(det_cell)[lo:hi]
     count = det_count[lo:hi].cpu().numpy() if torch.is_tensor(det_count) else np.asarray(det_count)[lo:hi]
@@ -332,7 +461,22 @@ def events_for_segment(det_cell, det_count, table: MetaFrameTable, segment: int,
     cell = cells[sel].astype(np.int64)
     az = np.rint(-180.0 + (cell % J + 0.5) * (360.0 / J))
     el = np.rint(-90.0 + (cell // J + 0.5) * (180.0 / I))
+    if ids is not None:
+        rank = ids[lo:hi].cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)[lo:hi]
     return np.stack([m[sel], c[sel], rank[sel], az, el], axis=1).astype(np.int32).reshape(-1, 5)
+
+
+def tracks_for_segment(tracks, chain_tracks, chain_offsets, segment: int):
+    """Rows of one segment's kept tracks: int32 [R, 5] = (class, track, onset_m, offset_m, detected_frames) in (class,
+    track) order, from the host copies of ``track``'s tracks / chain_tracks / chain_offsets; onset and offset are meta-frame
+    indices, both inclusive.  Five integer columns, so write_events_csv writes them."""
+    rows = []
+    for c in range(NUM_EVENT_CLASSES):
+        x = segment * NUM_EVENT_CLASSES + c
+        part = np.asarray(tracks)[int(chain_offsets[x]):int(chain_offsets[x]) + int(chain_tracks[x])]
+        for tid in np.nonzero(part[:, 3])[0]:
+            rows.append([c, int(tid), int(part[tid, 0]), int(part[tid, 1]), int(part[tid, 2])])
+    return np.array(rows, dtype=np.int32).reshape(-1, 5)
 
 
 def write_events_csv(path, rows) -> Path:
@@ -356,15 +500,22 @@ def segment_names(dataset):
 # ------------------------------------------------------------------------------------------------------ entry point
 
 def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_threshold_deg=None, events_dir=None,
-                    names=None, patterns=None) -> dict:
+                    names=None, patterns=None, track=None) -> dict:
     """Decode + score for any iterator of logit batches [B, 250, 648, 14] that covers ``dataset``'s windows in order.
     ``dataset``: an SELDDataset (``segments``, ``metadata_rows``, ``total_frames``, ``I``, ``J``, ``device``).  Defaults
     come from Config (SELD_THRESHOLD, SELD_MAX_PEAKS, SELD_DOA_THRESHOLD_DEG).  Returns F20, ER20, LE_CD, LR_CD, TP, FP,
     FN, N, per_class (plus S, D, I, matched and the settings); with ``events_dir`` one CSV per segment, named after
     ``names`` or the audio stems, listed under "event_files".
     ``patterns``: test-time augmentation (``decode``): the batches are [P, B, 250, 648, 14]; the result's "tta_patterns"
-    lists them ([] when off)."""
+    lists them ([] when off).
+    ``track``: track linking of the decoded detections.  None reads Config.SELD_TRACK; True or a
+    dict with any of gate_deg, max_gap, min_len (defaults: Config.SELD_TRACK_*) switches it on: the whole timeline is
+    decoded, linked into tracks (``track``) and the surviving emissions are what is scored and written.  The result's
+    "tracking" is then {gate_deg, max_gap, min_len, tracks, tracks_kept, filled, removed}, else None; the CSV rows are
+    ``m,c,track_id,az,el`` and ``<name>.tracks.csv`` (class, track, onset_m, offset_m, detected_frames of the kept
+    tracks) is written next to each, listed under "track_files"."""
     from config import Config
+    tracking = track_settings(track)
     patterns = tuple(int(p) for p in patterns) if patterns is not None else ()
     threshold = Config.SELD_THRESHOLD if threshold is None else threshold
     max_peaks = Config.SELD_MAX_PEAKS if max_peaks is None else max_peaks
@@ -374,13 +525,26 @@ def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_thresh
                                   f"{dataset.I} x {dataset.J}")
     table = meta_frame_table(dataset.segments, dataset.total_frames)
     det_cell, _, det_count, _ = decode(batches, table, threshold, max_peaks, device=dataset.device, patterns=patterns)
+    ids = linked = None
+    if tracking is not None:
+        linked = _track_link(det_cell, det_count, table, tracking["gate_deg"], tracking["max_gap"], tracking["min_len"],
+                             dataset.I, dataset.J)
+        det_cell, ids, det_count = linked[:3]
+        tracking = {**tracking, **track_summary(linked[2], linked[3], linked[4])}
     result = match_and_score(det_cell, det_count, table, dataset.metadata_rows, doa_threshold_deg, dataset.I, dataset.J)
     result.update(threshold=float(threshold), max_peaks=int(max_peaks), doa_threshold_deg=float(doa_threshold_deg),
-                  tta_patterns=list(patterns))
+                  tta_patterns=list(patterns), tracking=tracking)
     if events_dir is not None:
         names = segment_names(dataset) if names is None else list(names)
         cells, counts = det_cell.cpu().numpy(), det_count.cpu().numpy()
+        ids = ids.cpu().numpy() if ids is not None else None
         result["event_files"] = [str(write_events_csv(Path(events_dir) / f"{name}.csv",
-                                                      events_for_segment(cells, counts, table, s, dataset.I, dataset.J)))
+                                                      events_for_segment(cells, counts, table, s, dataset.I, dataset.J,
+                                                                         ids=ids)))
                                  for s, name in enumerate(names)]
+        if linked is not None:
+            rows, born, offsets = (t.cpu().numpy() for t in linked[3:6])
+            result["track_files"] = [str(write_events_csv(Path(events_dir) / f"{name}.tracks.csv",
+                                                          tracks_for_segment(rows, born, offsets, s)))
+                                     for s, name in enumerate(names)]
     return result

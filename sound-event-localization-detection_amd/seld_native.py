@@ -141,6 +141,8 @@ def _declare(lib):
     lib.seld_doa_match.argtypes = [_ptr, _ptr, _int, _ptr, _ptr, _i64, _int, _int, ctypes.c_double, _ptr, _ptr, _ptr]
     lib.seld_grid_decode_tta.argtypes = [_ptr, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _pi32, _int,
                                          ctypes.c_float, _int, _ptr, _ptr, _ptr, _ptr, _ptr]
+    lib.seld_track_link.argtypes = [_ptr, _ptr, _int, _ptr, _i64, _ptr, _int, _int, _int, _int, _int, _ptr, _ptr, _ptr, _ptr,
+                                    _ptr, _ptr, _ptr]
     return lib
 
 

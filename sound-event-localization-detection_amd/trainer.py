@@ -1106,7 +1106,7 @@ def _tta_logits(model, dataset, batch_size, device, patterns):
 
 
 def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, threshold=None, max_peaks=None,
-                  doa_threshold_deg=None, events_dir=None, use_ema=None, tta=None):
+                  doa_threshold_deg=None, events_dir=None, use_ema=None, tta=None, track=None):
     """Evaluate a checkpoint on what it detects: the windows of ``test_loader.dataset`` (an SELDDataset) run through the
     model in timeline order, the overlapping grid maps are decoded into DOA events on the GPU and scored against the
     dataset's CSV rows.  Returns F20, ER20, LE_CD, LR_CD, TP, FP, FN, N, per_class (seld_eval.evaluate_logits); with
@@ -1114,7 +1114,9 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
     runs on rank 0 only.
     ``tta``: the spatial patterns of test-time augmentation (seld_augment.tta_patterns: "all", a list, or () for off;
     None reads Config.SELD_TTA_PATTERNS): the model runs on every transformed copy of a window and the un-permuted grid
-    maps are averaged before the peak test; the result's "tta_patterns" lists them."""
+    maps are averaged before the peak test; the result's "tta_patterns" lists them.
+    ``track``: track linking of the detections (seld_eval.evaluate_logits: None reads Config.SELD_TRACK, True or a dict
+    of gate_deg / max_gap / min_len switches it on); the result's "tracking" holds its counts."""
     import seld_eval
     test_dataset = test_loader.dataset
     patterns = seld_augment.tta_patterns(getattr(config, "SELD_TTA_PATTERNS", ()) if tta is None else tta)
@@ -1139,8 +1141,13 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
         logger.info(f"test-time augmentation: {len(patterns)} forwards per window, spatial patterns {list(patterns)}")
     results = seld_eval.evaluate_logits(timeline_logits(model, test_dataset, batch_size, device, patterns=patterns),
                                         test_dataset, threshold=threshold, max_peaks=max_peaks,
-                                        doa_threshold_deg=doa_threshold_deg, events_dir=events_dir, patterns=patterns)
+                                        doa_threshold_deg=doa_threshold_deg, events_dir=events_dir, patterns=patterns,
+                                        track=track)
     results["checkpoint_epoch"] = checkpoint["epoch"]
+    if results.get("tracking"):
+        tr = results["tracking"]
+        logger.info(f"track linking (gate {tr['gate_deg']:g} deg, gap {tr['max_gap']}, min length {tr['min_len']}): "
+                    f"{tr['tracks_kept']} of {tr['tracks']} tracks kept, {tr['filled']} frames filled")
     logger.info(f"F20 {results['F20']:.4f}  ER20 {results['ER20']:.4f}  LE_CD {results['LE_CD']:.2f} deg  "
                 f"LR_CD {results['LR_CD']:.4f}  (TP {results['TP']}, FP {results['FP']}, FN {results['FN']}, "
                 f"N {results['N']})")
