@@ -358,6 +358,15 @@ int64_t seld_conv3x3_wgrad_workspace_floats(int64_t B, int64_t T, int64_t F, int
 int seld_conv3x3_wgrad(const void* x, const void* dy, int64_t B, int64_t T, int64_t F, int64_t Cin, int64_t Cout,
                        void* dw, int dw_is_bf16, float* workspace, void* stream);
 
+/* Data gradient of the same convolution from the weights where they lie (csrc/convdgrad.hip): dy [B][T][F][Cout] and
+ * w [Cout][3][3][Cin] (the weight's channels-last memory) -> dx [B][T][F][Cin], all bf16, fp32 accumulation, one
+ * rounding.  dx[b][t][f][ci] = sum over (r, s, co) of dy[b][t+1-r][f+1-s][co] * w[co][r][s][ci]: no flipped, transposed
+ * copy of the weights is formed.  F in {8, 16, 32}, Cin % 64 == 0, Cout % 64 == 0 (see _supported); all pointers
+ * 16-byte aligned.  Every output is written once in a fixed summation order: deterministic, no atomics, no workspace. */
+int seld_conv3x3_dgrad_supported(int64_t F, int64_t Cin, int64_t Cout);
+int seld_conv3x3_dgrad(const void* dy, const void* w, int64_t B, int64_t T, int64_t F, int64_t Cin, int64_t Cout,
+                       void* dx, void* stream);
+
 /* ---- First encoder block with the convolution recomputed in place (csrc/convfirst.hip) --------------------- */
 /* Conv3x3(4 -> 64, stride 1, pad 1, no bias) -> BatchNorm2d (training mode, affine, running statistics) -> ReLU ->
  * MaxPool2d((1,2)) of model_crnn.py:5-17 without ever writing the convolution output or its gradient.

@@ -24,50 +24,32 @@
 //     ([Cout][3][3][Cin]) and dtype.  Deterministic: the same inputs give the same bits on every call.
 #include <hip/hip_bf16.h>
 
+#include "conv3x3_image.h"
 #include "seld_common.h"
 
 namespace seld {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+using namespace conv3x3;            // types, the staged image and the transposed reads (conv3x3_image.h)
 
-constexpr int kWgThreads = 256;
+constexpr int kWgThreads = kThreads;
 constexpr int kWgTile = 64;          // output channels and input channels per workgroup
 constexpr int kWgKc = 128;           // positions per staged chunk
-constexpr int kWgPitch = 80;         // LDS row pitch in bf16: 64 channels + 16 pad = 160 B
+constexpr int kWgPitch = kPitch;
 constexpr int kWgSumThreads = 256;
 constexpr int kWgSumRows = 8;        // slab subsets per element of the fixed-order sum
 
 template <int F>
 struct WgradGeom {
-  static_assert(F == 8 || F == 16 || F == 32, "frequency bins: 8, 16 or 32");
-  static constexpr int TC = kWgKc / F;                       // time rows per chunk
-  static constexpr int XR = (TC + 2) * (F + 2);              // x image rows (with halo rows and edge columns)
+  using Img = Image<F, kWgKc>;
+  static constexpr int TC = Img::TC;                         // time rows per chunk
+  static constexpr int XR = Img::kRows;                      // x image rows (with halo rows and edge columns)
   static constexpr int kDyLoads = kWgKc * 8 / kWgThreads;    // 16-byte pieces per thread
-  static constexpr int kXLoads = (XR * 8 + kWgThreads - 1) / kWgThreads;
+  static constexpr int kXLoads = Img::kLoads;
   static constexpr int kLdsShorts = (kWgKc + XR) * kWgPitch;
   static_assert(kLdsShorts * 2 <= 64 * 1024, "LDS image larger than the default limit");
 };
-
-// x image row of position `pos` of the chunk (tap (1, 1), i.e. no shift)
-template <int F>
-__device__ __forceinline__ int x_row(int pos) {
-  return (pos / F + 1) * (F + 2) + pos % F + 1;
-}
-
-__device__ __forceinline__ s16x4 tr_read(const unsigned short* base, int offset_shorts) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + offset_shorts));
-}
-
-__device__ __forceinline__ bf16x8 join(s16x4 lo, s16x4 hi) {
-  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 template <int F>
 __global__ __launch_bounds__(kWgThreads, 2) void conv3x3_wgrad_kernel(
@@ -111,11 +93,7 @@ __global__ __launch_bounds__(kWgThreads, 2) void conv3x3_wgrad_kernel(
     }
 #pragma unroll
     for (int i = 0; i < G::kXLoads; ++i) {
-      const int piece = tid + i * kWgThreads, r = piece >> 3, ch = piece & 7;
-      const int tr = r / (F + 2), f = r - tr * (F + 2) - 1, t = t0 - 1 + tr;
-      rx[i] = make_uint4(0u, 0u, 0u, 0u);
-      if (r < G::XR && t >= 0 && t < T && f >= 0 && f < F)
-        rx[i] = *reinterpret_cast<const uint4*>(x + ((clip_row + t) * F + f) * Cin + ci0 + ch * 8);
+      rx[i] = image_piece<F, kWgKc>(x, clip_row, t0, T, Cin, ci0, tid + i * kWgThreads);
     }
   };
 
@@ -141,10 +119,10 @@ __global__ __launch_bounds__(kWgThreads, 2) void conv3x3_wgrad_kernel(
 #pragma unroll
       for (int m = 0; m < 2; ++m)
         a[m] = join(tr_read(ldy, pos_lo * kWgPitch + a_col + m * 16), tr_read(ldy, pos_hi * kWgPitch + a_col + m * 16));
-      const int xr_lo = x_row<F>(pos_lo), xr_hi = x_row<F>(pos_hi);
+      const int xr_lo = image_row<F>(pos_lo), xr_hi = image_row<F>(pos_hi);
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
-        const int shift = (tap / 3 - 1) * (F + 2) + (tap % 3 - 1);
+        const int shift = tap_shift<F>(tap);
         bf16x8 bfr[2];
 #pragma unroll
         for (int n = 0; n < 2; ++n)

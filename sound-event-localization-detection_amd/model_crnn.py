@@ -19,13 +19,15 @@ from seld_rnn import SeldGRU
 
 
 class _Conv3x3(torch.autograd.Function):
-    """3x3 / stride 1 / pad 1 convolution whose DATA gradient is evaluated as a forward convolution of dy with the
-    transposed, flipped weights.  Same numbers (a different summation order); on gfx950 MIOpen's forward solvers beat
-    its backward-data solvers on the encoder's shapes (tools/bench_conv_bwd.py, bf16 channels-last, batch 32:
+    """3x3 / stride 1 / pad 1 convolution whose DATA gradient comes from csrc/convdgrad.hip where that applies (bf16,
+    F in {8, 16, 32}, channel counts multiples of 64: encoder blocks 2-4) and is otherwise evaluated as a forward
+    convolution of dy with the transposed, flipped weights.  Same numbers (a different summation order); on gfx950
+    MIOpen's forward solvers beat its backward-data solvers on the encoder's shapes (tools/bench_conv_bwd.py, batch 32:
     256->512 channels 219 -> 170 us, 128->256 130 -> 115 us, 64->128 100 -> 87 us including the weight transform)."""
 
     enabled = True
     fused_wgrad = True          # weight gradient by csrc/convwgrad.hip where it applies (config.FUSED_CONV_WGRAD)
+    fused_dgrad = True          # data gradient by csrc/convdgrad.hip where it applies (config.FUSED_CONV_DGRAD)
 
     @staticmethod
     def forward(ctx, x, weight):
@@ -47,14 +49,19 @@ class _Conv3x3(torch.autograd.Function):
             dy = dy.to(xc.dtype).contiguous(memory_format=torch.channels_last)
             dx = None
             if ctx.needs_input_grad[0]:
-                if wc.is_contiguous(memory_format=torch.channels_last):
-                    import seld_native
-                    wt = seld_native.conv_weight_flip_transpose(wc)                 # one launch (flip + copy are two)
-                else:
-                    wt = wc.transpose(0, 1).flip(2, 3).contiguous(memory_format=torch.channels_last)
+                import seld_native
                 import seld_overlap
-                seld_overlap.release_held(dy.device)      # (wgrad_order "late": the previous block's weight gradient)
-                dx = F.conv2d(dy, wt, padding=1)
+                if _Conv3x3.fused_dgrad and seld_native.conv3x3_dgrad_applicable(dy, wc):
+                    # the HIP kernel reads the weights where they lie: no flipped, transposed copy, no library call
+                    seld_overlap.release_held(dy.device)
+                    dx = seld_native.conv3x3_dgrad(dy, wc)
+                else:
+                    if wc.is_contiguous(memory_format=torch.channels_last):
+                        wt = seld_native.conv_weight_flip_transpose(wc)             # one launch (flip + copy are two)
+                    else:
+                        wt = wc.transpose(0, 1).flip(2, 3).contiguous(memory_format=torch.channels_last)
+                    seld_overlap.release_held(dy.device)  # (wgrad_order "late": the previous block's weight gradient)
+                    dx = F.conv2d(dy, wt, padding=1)
                 if dx.dtype != x_dtype:
                     dx = dx.to(x_dtype)
             import seld_overlap

@@ -105,6 +105,8 @@ def _declare(lib):
     lib.seld_conv3x3_wgrad_workspace_floats.restype = _i64
     lib.seld_conv3x3_wgrad_workspace_floats.argtypes = [_i64, _i64, _i64, _i64, _i64]
     lib.seld_conv3x3_wgrad.argtypes = [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _int, _ptr, _ptr]
+    lib.seld_conv3x3_dgrad_supported.argtypes = [_i64, _i64, _i64]
+    lib.seld_conv3x3_dgrad.argtypes = [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr]
     lib.seld_convfirst_supported.argtypes = [_i64, _i64, _i64]
     lib.seld_convfirst_workspace_floats.restype = _i64
     lib.seld_convfirst_workspace_floats.argtypes = [_int]
@@ -1314,6 +1316,36 @@ def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor) -> torch.
         check(lib.seld_conv3x3_wgrad(_p(x), _p(dy), b, t, f, cin, cout, _p(dw), _is_bf16(dw), _p(ws),
                                      _stream_ptr(x.device)), "seld_conv3x3_wgrad")
     return dw
+
+
+def conv3x3_dgrad_applicable(dy: torch.Tensor, w: torch.Tensor) -> bool:
+    """True when ``conv3x3_dgrad`` covers this 3x3 / stride 1 / pad 1 convolution: bf16 dy [B, Cout, T, F] and bf16
+    weights [Cout, Cin, 3, 3], both in channels-last memory, F in {8, 16, 32}, channel counts multiples of 64."""
+    if not (dy.is_cuda and dy.dim() == 4 and w.dim() == 4 and dy.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+            and tuple(w.shape[2:]) == (3, 3) and dy.shape[1] == w.shape[0]):
+        return False
+    if not (dy.is_contiguous(memory_format=torch.channels_last) and w.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    return bool(load_library().seld_conv3x3_dgrad_supported(dy.shape[3], w.shape[1], w.shape[0]))
+
+
+def conv3x3_dgrad(dy: torch.Tensor, w: torch.Tensor, out: "torch.Tensor | None" = None) -> torch.Tensor:
+    """dx [B, Cin, T, F] (bf16, channels-last memory; ``out`` when given) = the data gradient of a 3x3 / stride 1 /
+    pad 1 bias-free convolution with weights w and output gradient dy (``conv3x3_dgrad_applicable``), read from w as it
+    lies: no flipped, transposed copy.  fp32 accumulation, one rounding; deterministic."""
+    if not conv3x3_dgrad_applicable(dy, w):
+        raise SeldNativeError("conv3x3_dgrad: unsupported shapes, dtypes or layouts")
+    b, cout, t, f = dy.shape
+    cin = w.shape[1]
+    if out is None:
+        out = torch.empty((b, cin, t, f), dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
+    elif not (out.dtype == torch.bfloat16 and out.device == dy.device and tuple(out.shape) == (b, cin, t, f)
+              and out.is_contiguous(memory_format=torch.channels_last)):
+        raise SeldNativeError("conv3x3_dgrad: out must be bf16 [B, Cin, T, F] in channels-last memory")
+    with _device_guard(ensure_init(dy.device)):
+        check(load_library().seld_conv3x3_dgrad(_p(dy), _p(w), b, t, f, cin, cout, _p(out), _stream_ptr(dy.device)),
+              "seld_conv3x3_dgrad")
+    return out
 
 
 # --------------------------------------------------------------------------- first encoder block (conv recomputed)
