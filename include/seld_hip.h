@@ -569,6 +569,35 @@ int seld_track_link(const int32_t* det_cell, const int32_t* det_count, int K, co
                     const int64_t* chain_offsets, int32_t* trk_cell, int32_t* trk_id, int32_t* trk_count, int32_t* tracks,
                     int32_t* chain_tracks, void* stream);
 
+/* ---- sub-cell DOA refinement of the decode (csrc/seld_refine.hip) ----------------------------
+ * seld_grid_decode_refine: seld_grid_decode (n_patterns == 0 and patterns == NULL: the plain walk over logits
+ * [nw][250][648][14]) or seld_grid_decode_tta (n_patterns 1..16: logits [n_patterns][nw][250][648][14], `patterns` a HOST
+ * pointer) with one more output.  det_cell, det_score, det_count and probs_out are what that export writes for the same
+ * input, bit for bit.  For the detection of class c at peak cell x = (i, j), with N(x) = x and its up-to-8 neighbours
+ * under the peak test's rule (j +- 1 mod 36; i +- 1 only inside [0, 18)) and u(y) = cell_unit[y] (f32 [648][3], device:
+ * the unit vector (cos el cos az, cos el sin az, sin el) of the centre of cell y, computed in float64 by the host and
+ * rounded once):
+ *   v = sum over y in N(x) of P_q[y][c] u(y), fp32 fused multiply-adds in the order di = -1, 0, 1 outer, dj = -1, 0, 1
+ *   inner (the centre included);  az = atan2(v_y, v_x), el = atan2(v_z, hypot(v_x, v_y)) in degrees, az = +180 written
+ *   as -180;  the cell centre when |v|^2 is 0 or not finite.
+ * det_dir f32 [nq][13][K][2] = (az, el) of detection r of (qi, c), 0 past the count; 16-byte aligned.  An epilogue of
+ * the decode while P_q is in LDS: no extra pass over memory, no second launch; one workgroup per meta-frame, plain
+ * stores in a fixed order: bit-identical however the meta-frames are split across calls.  Coverage rule, no
+ * allocation, no synchronise: as seld_grid_decode.  -1, launching nothing, for what seld_grid_decode_tta refuses
+ * (n_patterns 0 allowed, exactly when patterns is NULL), and for a null cell_unit or det_dir. */
+int seld_grid_decode_refine(const void* logits, int is_bf16, int64_t w0, int64_t nw, int64_t W, int64_t total,
+                            const int64_t* meta_first, const int32_t* meta_len, int64_t q0, int64_t nq,
+                            const int32_t* patterns, int n_patterns, float threshold, int K, const float* cell_unit,
+                            int32_t* det_cell, float* det_score, int32_t* det_count, float* det_dir, float* probs_out,
+                            void* stream);
+
+/* seld_doa_match_dirs: seld_doa_match with the detections' directions given as det_dir f32 [nq][13][K][2] = (azimuth,
+ * elevation) degrees (what seld_grid_decode_refine writes; 8-byte aligned) in place of det_cell, I, J.  The directions
+ * are widened to float64; distance, matching and assignment are seld_doa_match's own code, so the exact cell centres
+ * reproduce its stats and cost bit for bit. */
+int seld_doa_match_dirs(const float* det_dir, const int32_t* det_count, int K, const int32_t* ref_offsets,
+                        const int32_t* ref_dirs, int64_t nq, double thr_deg, int32_t* stats, double* cost, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,9 @@ class Config:
     SELD_TRACK_GATE_DEG = 20    # a detection continues a track when it lies within this great-circle angle of its last cell
     SELD_TRACK_MAX_GAP = 2      # a track survives this many meta-frames without a detection (they are filled), 0..16
     SELD_TRACK_MIN_LEN = 3      # tracks spanning fewer meta-frames (onset to offset) are removed
+    # Sub-cell DOA refinement of the decoded detections (seld_eval.grid_decode_refine, csrc/seld_refine.hip)
+    SELD_REFINE = False         # evaluate_seld / infer.py score and write a direction finer than the 10-degree cell: the
+                                # probability-weighted mean of the unit vectors of the peak cell and its neighbours
 
     def __init__(self):
         for folder in (self.OUTPUT_PATH, self.CHECKPOINT_PATH):

@@ -1,7 +1,8 @@
-// The grid-map decode shared by seld_grid_decode (seld_eval.hip) and seld_grid_decode_tta (seld_tta.hip): one meta-frame
-// per workgroup of 512 threads, DESIGN.md sections 10 and 13.  decode_meta_frame<kBf16, kTta> is the whole kernel body;
-// with kTta = false every `if constexpr (kTta)` drops out and what is left is the plain decode, so the two entry points
-// cannot drift apart in summation order or arithmetic.
+// The grid-map decode shared by seld_grid_decode (seld_eval.hip), seld_grid_decode_tta (seld_tta.hip) and
+// seld_grid_decode_refine (seld_refine.hip): one meta-frame per workgroup of 512 threads, DESIGN.md sections 10, 13 and
+// 15.  decode_meta_frame<kBf16, kTta, kRefine> is the whole kernel body; with kTta = false every `if constexpr (kTta)`
+// drops out and what is left is the plain decode, and with kRefine = false so does the sub-cell DOA epilogue, so the
+// entry points cannot drift apart in summation order or arithmetic.
 #pragma once
 
 #include "seld_common.h"
@@ -101,16 +102,50 @@ __device__ __forceinline__ int cell_dest(int i, int j, int p) {
   return i2 * kJ + j2;
 }
 
+// Sub-cell DOA of the detection of class c at peak cell x (section 15.1): v = sum over x and its up-to-8 neighbours y
+// (the peak test's rule) of P_q[y][c] u(y), u = cell_unit [648][3], accumulated in fp32 in the order di = -1, 0, 1 outer,
+// dj = -1, 0, 1 inner; (az, el) of v in degrees, +180 written as -180; the cell centre when |v|^2 is 0 or not finite.
+__device__ __forceinline__ float2 refine_doa(const float* prob, const float* __restrict__ cell_unit, int x, int c) {
+  const int i = x / kJ, j = x - i * kJ;
+  float vx = 0.0f, vy = 0.0f, vz = 0.0f;
+#pragma unroll
+  for (int di = -1; di <= 1; ++di) {
+    const int ii = i + di;
+    if (ii < 0 || ii >= kI) continue;                  // no wrap over the poles
+#pragma unroll
+    for (int dj = -1; dj <= 1; ++dj) {
+      int jj = j + dj;
+      jj = jj < 0 ? jj + kJ : (jj >= kJ ? jj - kJ : jj);           // azimuth wraps
+      const int y = ii * kJ + jj;
+      const float p = prob[y * kC + c];
+      vx = fmaf(p, cell_unit[3 * y], vx);
+      vy = fmaf(p, cell_unit[3 * y + 1], vy);
+      vz = fmaf(p, cell_unit[3 * y + 2], vz);
+    }
+  }
+  const float n2 = vx * vx + vy * vy + vz * vz;
+  if (!(n2 > 0.0f) || !(n2 <= 3.0e38f))                // zero, NaN or infinite: the cell centre (exact in fp32)
+    return make_float2(-180.0f + (j + 0.5f) * (360.0f / kJ), -90.0f + (i + 0.5f) * (180.0f / kI));
+  constexpr float kDeg = 57.295779513082323f;
+  float az = atan2f(vy, vx) * kDeg;
+  const float el = atan2f(vz, sqrtf(vx * vx + vy * vy)) * kDeg;
+  az = az >= 180.0f ? -180.0f : az;
+  return make_float2(az, el);
+}
+
 // One workgroup's work: meta-frame q0 + blockIdx.x from `logits`; the kernel's only LDS is the staged row declared here.
 // kTta: `logits` holds n_pat stacks [n_pat][nw][250][648][14] (stack_chunks 16-byte chunks apart), stack n the windows
 // gathered with pattern (patterns >> 4 n) & 15; rows are walked in (frame, window, n) ascending order, the thread that
 // owns cell x reads the staged row at cell_dest(x), and a frame's sum is divided once by n_w * n_pat.
-template <bool kBf16, bool kTta>
+// kRefine: after a class's top-K, while P_q is still in LDS, lane r of the wave that selected it writes the sub-cell
+// DOA of its detection r to det_dir [nq][13][K][2] (0 past the count).
+template <bool kBf16, bool kTta, bool kRefine = false>
 __device__ __forceinline__ void decode_meta_frame(
     const uint4* logits, long w0, long nw, long W, long total,
     const int64_t* meta_first, const int32_t* meta_len, long q0, float threshold, int K,
     int32_t* det_cell, float* det_score, int32_t* det_count,
-    float* probs_out, uint64_t patterns, int n_pat, long stack_chunks) {
+    float* probs_out, uint64_t patterns, int n_pat, long stack_chunks, const float* cell_unit = nullptr,
+    float* det_dir = nullptr) {
   using R = Row<kBf16>;
   __shared__ uint4 stage[R::kLdsChunks];
   const int tid = threadIdx.x;
@@ -252,6 +287,7 @@ __device__ __forceinline__ void decode_meta_frame(
     float prev_s = 0.0f;
     int prev_c = kCells;                               // nothing selected yet
     int count = 0;
+    [[maybe_unused]] int mine = kCells;                // kRefine: lane r keeps the cell of detection r
     const long out = (qi * kC + c) * K;
     for (int r = 0; r < K; ++r) {
       float best_s = 0.0f;
@@ -281,9 +317,15 @@ __device__ __forceinline__ void decode_meta_frame(
         det_cell[out + r] = best_c;
         det_score[out + r] = best_s;
       }
+      if constexpr (kRefine) mine = lane == r ? best_c : mine;
       prev_s = best_s;
       prev_c = best_c;
       ++count;
+    }
+    if constexpr (kRefine) {
+      if (lane < K)
+        reinterpret_cast<float2*>(det_dir)[out + lane] =
+            lane < count ? refine_doa(prob, cell_unit, mine, c) : make_float2(0.0f, 0.0f);
     }
     if (lane == 0) {
       for (int r = count; r < K; ++r) {

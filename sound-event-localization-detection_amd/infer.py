@@ -1,12 +1,13 @@
 """Inference CLI: recordings -> SELD event CSVs, one per recording (no reference counterpart).
 
-    python infer.py --checkpoint best_model.pth --out-dir DIR [--tta all | --tta 0,2,9] [--track] a.wav [b.wav ...]
+    python infer.py --checkpoint best_model.pth --out-dir DIR [--tta all | --tta 0,2,9] [--track] [--refine] a.wav [b.wav ...]
 
 Each recording becomes a one-segment timeline (features through the dataset's own path, no metadata rows), its 5 s
 windows run through the checkpoint's model in timeline order, and the decoded events are written to DIR/<stem>.csv as
 ``meta_frame,class,rank,azimuth,elevation`` rows -- the metadata format the dataset reads.  With ``--track`` the
 detections are linked into tracks first: the third column is the track id, and DIR/<stem>.tracks.csv
-lists ``class,track,onset_m,offset_m,detected_frames`` of every kept track.
+lists ``class,track,onset_m,offset_m,detected_frames`` of every kept track.  With ``--refine`` azimuth and elevation are the
+nearest integer degrees of the detections' sub-cell directions, not the centres of their 10-degree cells.
 """
 import argparse
 import logging
@@ -46,6 +47,9 @@ def parse_args(argv=None):
                    help="meta-frames a track survives without a detection (filled), 0..16")
     p.add_argument("--track-min-len", type=int, default=cfg.SELD_TRACK_MIN_LEN,
                    help="tracks spanning fewer meta-frames are removed")
+    p.add_argument("--refine", action=argparse.BooleanOptionalAction, default=bool(getattr(cfg, "SELD_REFINE", False)),
+                   help="write sub-cell directions (integer degrees) in place of the 10-degree cell centres "
+                        "(default: Config.SELD_REFINE; --no-refine switches it off)")
     p.add_argument("--device", default=None, help="default: the current ROCm device")
     p.add_argument("--use-ema", action="store_true",
                    help="load the checkpoint's ema_state_dict (default: Config.EVAL_USE_EMA); an error when it has none")
@@ -85,7 +89,8 @@ def main(argv=None):
             model.eval()
         result = seld_eval.evaluate_logits(trainer.timeline_logits(model, ds, args.batch_size, device, patterns=patterns),
                                            ds, threshold=args.threshold, max_peaks=args.max_peaks, events_dir=args.out_dir,
-                                           names=[Path(wav).stem], patterns=patterns, track=track)
+                                           names=[Path(wav).stem], patterns=patterns, track=track,
+                                           refine=args.refine)
         path = result["event_files"][0]
         written.append(path)
         if result["tracking"]:

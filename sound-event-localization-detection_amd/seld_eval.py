@@ -17,6 +17,12 @@ Track linking (csrc/seld_track.hip): ``track`` on evaluate
   seld_track_link        one wavefront per (segment, class) links the frame-wise peaks into tracks with an identity over
                          time: gated greedy nearest-cell linking, gap filling, a minimum duration, onset / offset
 
+Sub-cell DOA refinement (csrc/seld_refine.hip): ``refine`` on decode / evaluate_logits switches to
+
+  seld_grid_decode_refine  either decode with an epilogue that gives every detection a direction finer than its cell,
+                           from the peak's 3x3 neighbourhood of the class map while it is still in LDS
+  seld_doa_match_dirs      seld_doa_match on those float directions
+
 The host side here builds the tables (meta-frames, reference CSR), drives the decode batch by batch as the windows are
 computed, reduces the match counts on the device and writes event CSVs.  There is no CPU fallback.
 """
@@ -207,6 +213,124 @@ def doa_match(det_cell: torch.Tensor, det_count: torch.Tensor, ref_offsets: torc
     return stats, cost
 
 
+# ------------------------------------------------------------------------------------------------------ refinement
+
+_cell_units = {}
+
+
+def cell_unit_table(device=None, I: int = GRID_I, J: int = GRID_J) -> torch.Tensor:
+    """The unit vectors of the cell centres, f32 [I * J, 3] = (cos el cos az, cos el sin az, sin el): computed in float64,
+    rounded once to fp32, cached per device (``device`` None: the host copy).  The table seld_grid_decode_refine reads."""
+    host_key, key = (int(I), int(J), None), (int(I), int(J), None if device is None else str(device))
+    if host_key not in _cell_units:
+        cell = np.arange(int(I) * int(J), dtype=np.int64)
+        az = np.deg2rad(-180.0 + (cell % J + 0.5) * (360.0 / J))
+        el = np.deg2rad(-90.0 + (cell // J + 0.5) * (180.0 / I))
+        unit = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], axis=1)
+        _cell_units[host_key] = torch.from_numpy(unit.astype(np.float32))
+    if key not in _cell_units:
+        _cell_units[key] = _cell_units[host_key].to(device).contiguous()
+    return _cell_units[key]
+
+
+def grid_decode_refine(logits: torch.Tensor, w0: int, table: MetaFrameTable, q0: int, nq: int, threshold: float,
+                       max_peaks: int, out=None, probs: torch.Tensor | None = None, patterns=None):
+    """seld_grid_decode_refine: ``grid_decode`` (``patterns`` None or empty; logits [nw, 250, 648, 14]) or
+    ``grid_decode_tta`` (logits [P, nw, 250, 648, 14]) that also writes every detection's sub-cell direction (DESIGN.md
+    section 15).  ``out``: contiguous (det_cell, det_score, det_count, det_dir f32 [nq, 13, K, 2] = (az, el) degrees, 0
+    past the count) to write, else allocated; the first three and ``probs`` are the un-refined call's bit for bit."""
+    pats = np.asarray(list(patterns) if patterns is not None else [], dtype=np.int32).reshape(-1)
+    tta = len(pats) > 0
+    if not logits.is_cuda:
+        raise SeldNativeError("grid_decode_refine: logits must live on the GPU (no CPU fallback)")
+    if logits.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("grid_decode_refine: logits must be bfloat16 or float32")
+    rows = (WIN, GRID_I * GRID_J, NUM_EVENT_CLASSES + 1)
+    if logits.dim() != (5 if tta else 4) or tuple(logits.shape[-3:]) != rows:
+        raise ValueError(f"grid_decode_refine: logits must be {'[P, nw' if tta else '[nw'}, {WIN}, 648, 14], got "
+                         f"{tuple(logits.shape)}")
+    if tta and int(logits.shape[0]) != len(pats):
+        raise ValueError(f"grid_decode_refine: {int(logits.shape[0])} stacks of logits for {len(pats)} patterns")
+    logits = logits.contiguous()
+    nw = int(logits.shape[-4])
+    if not (q0 >= 0 and nq >= 0 and q0 + nq <= len(table)):
+        raise ValueError("grid_decode_refine: meta-frame range outside the table")
+    if nq:
+        lo, hi = int(table.first_window[q0:q0 + nq].min()), int(table.last_window[q0:q0 + nq].max())
+        if lo < w0 or hi >= w0 + nw:
+            raise SeldNativeError(f"grid_decode_refine: meta-frames {q0}..{q0 + nq - 1} need windows {lo}..{hi}, the call "
+                                  f"holds {w0}..{w0 + nw - 1}")
+    device = logits.device
+    index = ensure_init(device)
+    k = int(max_peaks)
+    if out is None:
+        out = (torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.int32, device=device),
+               torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.float32, device=device),
+               torch.empty((nq, NUM_EVENT_CLASSES), dtype=torch.int32, device=device),
+               torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1), 2), dtype=torch.float32, device=device))
+    first, length = table.device(device)
+    unit = cell_unit_table(device)
+    with _device_guard(index):
+        check(load_library().seld_grid_decode_refine(
+            _p(logits), int(logits.dtype == torch.bfloat16), int(w0), nw, table.windows, table.total, _p(first),
+            _p(length), int(q0), int(nq), pats.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if tta else None,
+            len(pats), float(threshold), k, _p(unit), _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _p(probs),
+            _stream_ptr(device)), "seld_grid_decode_refine")
+    return out
+
+
+def doa_match_dirs(det_dir: torch.Tensor, det_count: torch.Tensor, ref_offsets: torch.Tensor, ref_dirs: torch.Tensor,
+                   doa_threshold_deg: float):
+    """seld_doa_match_dirs: ``doa_match`` with the detections' directions det_dir f32 [Q, 13, K, 2] = (az, el) degrees in
+    place of their cells."""
+    device = det_dir.device
+    if not det_dir.is_cuda:
+        raise SeldNativeError("doa_match_dirs: detections must live on the GPU (no CPU fallback)")
+    if det_dir.dim() != 4 or det_dir.shape[1] != NUM_EVENT_CLASSES or det_dir.shape[3] != 2 or \
+            tuple(det_count.shape) != tuple(det_dir.shape[:2]):
+        raise ValueError("doa_match_dirs: det_dir must be [Q, 13, K, 2] and det_count [Q, 13]")
+    q = int(det_count.shape[0])
+    if ref_offsets.numel() != q * NUM_EVENT_CLASSES + 1:
+        raise ValueError("doa_match_dirs: ref_offsets must have Q * 13 + 1 entries")
+    index = ensure_init(device)
+    stats = torch.empty((q, NUM_EVENT_CLASSES, 4), dtype=torch.int32, device=device)
+    cost = torch.empty((q, NUM_EVENT_CLASSES), dtype=torch.float64, device=device)
+    dirs = ref_dirs if ref_dirs.numel() else torch.zeros((1, 2), dtype=torch.int32, device=device)
+    det_dir, det_count = det_dir.to(torch.float32).contiguous(), det_count.to(torch.int32).contiguous()
+    ref_offsets, dirs = ref_offsets.to(torch.int32).contiguous(), dirs.to(torch.int32).contiguous()
+    with _device_guard(index):
+        check(load_library().seld_doa_match_dirs(_p(det_dir), _p(det_count), int(det_dir.shape[2]), _p(ref_offsets),
+                                                 _p(dirs), q, float(doa_threshold_deg) + DOA_MARGIN_DEG, _p(stats),
+                                                 _p(cost), _stream_ptr(device)), "seld_doa_match_dirs")
+    return stats, cost
+
+
+def cell_centre_dirs(cells: torch.Tensor, I: int = GRID_I, J: int = GRID_J) -> torch.Tensor:
+    """Cells int [...] -> their centres f32 [..., 2] = (az, el) degrees (exact in fp32 on the 10-degree grid)."""
+    cells = cells.to(torch.int64)
+    az = -180.0 + (cells % J).to(torch.float32).add(0.5) * (360.0 / J)
+    el = -90.0 + torch.div(cells, J, rounding_mode="floor").to(torch.float32).add(0.5) * (180.0 / I)
+    return torch.stack([az, el], dim=-1)
+
+
+def track_dirs(trk_cell: torch.Tensor, trk_count: torch.Tensor, det_cell: torch.Tensor, det_count: torch.Tensor,
+               det_dir: torch.Tensor, I: int = GRID_I, J: int = GRID_J) -> torch.Tensor:
+    """Directions of ``track``'s surviving emissions, f32 [Q, 13, 8, 2]: an emission takes the refined direction of the
+    detection with the same cell at its (q, c) (a frame's detections of one class are distinct cells); a gap-filled
+    emission, whose cell is not among that frame's detections, takes its cell centre; 0 past trk_count.  Framework ops
+    where the tensors live."""
+    k = int(det_cell.shape[-1])
+    rank = torch.arange(k, device=det_cell.device)
+    valid = rank < det_count[..., None]                                             # [Q, 13, K]
+    same = (trk_cell[..., :, None] == det_cell[..., None, :]) & valid[..., None, :]  # [Q, 13, 8, K]
+    found = same.any(-1)
+    pick = same.to(torch.int32).argmax(-1)                                           # the detection's rank, 0 when none
+    taken = torch.gather(det_dir, 2, pick[..., None].expand(-1, -1, -1, 2))
+    dirs = torch.where(found[..., None], taken, cell_centre_dirs(trk_cell, I, J))
+    slot = torch.arange(int(trk_cell.shape[-1]), device=trk_cell.device)
+    return torch.where((slot < trk_count[..., None])[..., None], dirs, torch.zeros_like(dirs))
+
+
 # ------------------------------------------------------------------------------------------------------ tracking
 
 _distance_tables = {}
@@ -323,14 +447,16 @@ def track_summary(trk_count: torch.Tensor, tracks: torch.Tensor, chain_tracks: t
 # ------------------------------------------------------------------------------------------------------ decode driver
 
 def decode(batches, table: MetaFrameTable, threshold: float, max_peaks: int, device=None, keep_probs: bool = False,
-           patterns=None):
+           patterns=None, refine: bool = False):
     """Streaming decode of a whole timeline.  ``batches`` yields logit tensors [B, 250, 648, 14] of consecutive windows
     in timeline order (window 0 first, ``table.windows`` in all).  After each batch every meta-frame whose last
     covering window has been seen is decoded; the last KEEP_WINDOWS windows stay on the device for the next call.
     Returns (det_cell int32 [Q, 13, K], det_score f32 [Q, 13, K], det_count int32 [Q, 13], probs f32 [Q, 648, 13] or
     None) on the device.
     ``patterns``: a non-empty list of spatial patterns switches to test-time augmentation: the batches are then
-    [P, B, 250, 648, 14], stack n under ``patterns[n]``, and every call goes to ``grid_decode_tta``."""
+    [P, B, 250, 648, 14], stack n under ``patterns[n]``, and every call goes to ``grid_decode_tta``.
+    ``refine``: every call goes to ``grid_decode_refine`` (either walk) and a fifth tensor is returned: det_dir f32
+    [Q, 13, K, 2], the detections' sub-cell directions."""
     k = int(max_peaks)
     patterns = tuple(patterns) if patterns is not None else ()
     wdim = 1 if patterns else 0                  # the window axis of a batch
@@ -347,6 +473,8 @@ def decode(batches, table: MetaFrameTable, threshold: float, max_peaks: int, dev
             det = (torch.empty((n_q, NUM_EVENT_CLASSES, k), dtype=torch.int32, device=device),
                    torch.empty((n_q, NUM_EVENT_CLASSES, k), dtype=torch.float32, device=device),
                    torch.empty((n_q, NUM_EVENT_CLASSES), dtype=torch.int32, device=device))
+            if refine:
+                det += (torch.empty((n_q, NUM_EVENT_CLASSES, k, 2), dtype=torch.float32, device=device),)
             if keep_probs:
                 probs = torch.empty((n_q, GRID_I * GRID_J, NUM_EVENT_CLASSES), dtype=torch.float32, device=device)
         if batch.dtype not in (torch.bfloat16, torch.float32):
@@ -356,8 +484,11 @@ def decode(batches, table: MetaFrameTable, threshold: float, max_peaks: int, dev
         seen += int(batch.shape[wdim])
         end = int(np.searchsorted(table.last_window, seen - 1, side="right"))
         if end > done:
-            out = (det[0][done:end], det[1][done:end], det[2][done:end])
-            if patterns:
+            out = tuple(t[done:end] for t in det)
+            if refine:
+                grid_decode_refine(held, w0, table, done, end - done, threshold, k, out=out,
+                                   probs=probs[done:end] if probs is not None else None, patterns=patterns)
+            elif patterns:
                 grid_decode_tta(held, patterns, w0, table, done, end - done, threshold, k, out=out,
                                 probs=probs[done:end] if probs is not None else None)
             else:
@@ -375,7 +506,9 @@ def decode(batches, table: MetaFrameTable, threshold: float, max_peaks: int, dev
         det = (torch.zeros((0, NUM_EVENT_CLASSES, k), dtype=torch.int32, device=device),
                torch.zeros((0, NUM_EVENT_CLASSES, k), dtype=torch.float32, device=device),
                torch.zeros((0, NUM_EVENT_CLASSES), dtype=torch.int32, device=device))
-    return det[0], det[1], det[2], probs
+        if refine:
+            det += (torch.zeros((0, NUM_EVENT_CLASSES, k, 2), dtype=torch.float32, device=device),)
+    return (det[0], det[1], det[2], probs, det[3]) if refine else (det[0], det[1], det[2], probs)
 
 
 # ------------------------------------------------------------------------------------------------------ references
@@ -435,24 +568,41 @@ def score(stats: torch.Tensor, cost: torch.Tensor) -> dict:
             "per_class": per_class}
 
 
+def refine_setting(refine) -> bool:
+    """``refine`` as evaluate_logits takes it -> bool; None reads Config.SELD_REFINE."""
+    from config import Config
+    return bool(getattr(Config, "SELD_REFINE", False)) if refine is None else bool(refine)
+
+
 def match_and_score(det_cell: torch.Tensor, det_count: torch.Tensor, table: MetaFrameTable, metadata_rows,
-                    doa_threshold_deg: float, I: int = GRID_I, J: int = GRID_J) -> dict:
-    """References (numpy CSR) -> seld_doa_match on the detections' device -> score()."""
+                    doa_threshold_deg: float, I: int = GRID_I, J: int = GRID_J, det_dir: torch.Tensor | None = None,
+                    refine=None) -> dict:
+    """References (numpy CSR) -> seld_doa_match on the detections' device -> score().
+    ``det_dir`` with ``refine`` (None reads Config.SELD_REFINE when ``det_dir`` is given): the detections' directions
+    f32 [Q, 13, K, 2] are matched by seld_doa_match_dirs in place of the cell centres."""
+    if det_dir is None and refine:
+        raise ValueError("match_and_score: refine needs det_dir (decode(..., refine=True))")
+    refine = det_dir is not None and refine_setting(refine)
     offsets, dirs = reference_table(table, metadata_rows)
     device = det_cell.device
-    stats, cost = doa_match(det_cell, det_count, torch.from_numpy(offsets).to(device), torch.from_numpy(dirs).to(device),
-                            doa_threshold_deg, I, J)
+    offsets, dirs = torch.from_numpy(offsets).to(device), torch.from_numpy(dirs).to(device)
+    if refine:
+        stats, cost = doa_match_dirs(det_dir, det_count, offsets, dirs, doa_threshold_deg)
+    else:
+        stats, cost = doa_match(det_cell, det_count, offsets, dirs, doa_threshold_deg, I, J)
     return score(stats, cost)
 
 
 # ------------------------------------------------------------------------------------------------------ events
 
 def events_for_segment(det_cell, det_count, table: MetaFrameTable, segment: int, I: int = GRID_I, J: int = GRID_J,
-                       ids=None):
+                       ids=None, dirs=None):
     """Event rows of one segment: int32 [R, 5] = (meta_frame, class, rank, azimuth, elevation) in (m, c, rank) order,
     the DOA being the detection's cell centre (integer degrees on the 10-degree grid).
     ``ids``: the track ids that go with ``det_cell`` (``track``'s trk_id next to trk_cell / trk_count); the third column
-    is then the track id, rows in (m, c, id) order -- the order ``track`` writes them in."""
+    is then the track id, rows in (m, c, id) order -- the order ``track`` writes them in.
+    ``dirs``: the refined directions that go with ``det_cell`` (f32 [Q, 13, K, 2] degrees); the DOA
+    is then their nearest integer degree, an azimuth that rounds to 180 written as -180."""
     lo, hi = int(table.seg_offsets[segment]), int(table.seg_offsets[segment + 1])
     cells = det_cell[lo:hi].cpu().numpy() if torch.is_tensor(det_cell) else np.asarray(det_cell)[lo:hi]
     count = det_count[lo:hi].cpu().numpy() if torch.is_tensor(det_count) else np.asarray(det_count)[lo:hi]
@@ -461,6 +611,10 @@ def events_for_segment(det_cell, det_count, table: MetaFrameTable, segment: int,
     cell = cells[sel].astype(np.int64)
     az = np.rint(-180.0 + (cell % J + 0.5) * (360.0 / J))
     el = np.rint(-90.0 + (cell // J + 0.5) * (180.0 / I))
+    if dirs is not None:
+        d = dirs[lo:hi].cpu().numpy() if torch.is_tensor(dirs) else np.asarray(dirs)[lo:hi]
+        az, el = np.rint(d[..., 0][sel].astype(np.float64)), np.rint(d[..., 1][sel].astype(np.float64))
+        az = np.where(az >= 180.0, az - 360.0, az)
     if ids is not None:
         rank = ids[lo:hi].cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)[lo:hi]
     return np.stack([m[sel], c[sel], rank[sel], az, el], axis=1).astype(np.int32).reshape(-1, 5)
@@ -500,7 +654,7 @@ def segment_names(dataset):
 # ------------------------------------------------------------------------------------------------------ entry point
 
 def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_threshold_deg=None, events_dir=None,
-                    names=None, patterns=None, track=None) -> dict:
+                    names=None, patterns=None, track=None, refine=None) -> dict:
     """Decode + score for any iterator of logit batches [B, 250, 648, 14] that covers ``dataset``'s windows in order.
     ``dataset``: an SELDDataset (``segments``, ``metadata_rows``, ``total_frames``, ``I``, ``J``, ``device``).  Defaults
     come from Config (SELD_THRESHOLD, SELD_MAX_PEAKS, SELD_DOA_THRESHOLD_DEG).  Returns F20, ER20, LE_CD, LR_CD, TP, FP,
@@ -513,9 +667,15 @@ def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_thresh
     decoded, linked into tracks (``track``) and the surviving emissions are what is scored and written.  The result's
     "tracking" is then {gate_deg, max_gap, min_len, tracks, tracks_kept, filled, removed}, else None; the CSV rows are
     ``m,c,track_id,az,el`` and ``<name>.tracks.csv`` (class, track, onset_m, offset_m, detected_frames of the kept
-    tracks) is written next to each, listed under "track_files"."""
+    tracks) is written next to each, listed under "track_files".
+    ``refine``: sub-cell DOA refinement.  None reads Config.SELD_REFINE; True decodes with
+    ``grid_decode_refine``, scores the detections' refined directions (seld_doa_match_dirs) and writes their nearest
+    integer degrees to the CSVs in place of the cell centres.  With ``track`` the linking itself stays on cells; a
+    surviving emission takes the refined direction of the detection it is, a filled one its cell centre
+    (``track_dirs``).  The result's "refine" says which."""
     from config import Config
     tracking = track_settings(track)
+    refine = refine_setting(refine)
     patterns = tuple(int(p) for p in patterns) if patterns is not None else ()
     threshold = Config.SELD_THRESHOLD if threshold is None else threshold
     max_peaks = Config.SELD_MAX_PEAKS if max_peaks is None else max_peaks
@@ -524,23 +684,28 @@ def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_thresh
         raise NotImplementedError(f"the decode kernel is built for the {GRID_I} x {GRID_J} grid, got "
                                   f"{dataset.I} x {dataset.J}")
     table = meta_frame_table(dataset.segments, dataset.total_frames)
-    det_cell, _, det_count, _ = decode(batches, table, threshold, max_peaks, device=dataset.device, patterns=patterns)
+    decoded = decode(batches, table, threshold, max_peaks, device=dataset.device, patterns=patterns, refine=refine)
+    det_cell, det_count, det_dir = decoded[0], decoded[2], decoded[4] if refine else None
     ids = linked = None
     if tracking is not None:
         linked = _track_link(det_cell, det_count, table, tracking["gate_deg"], tracking["max_gap"], tracking["min_len"],
                              dataset.I, dataset.J)
+        if refine:
+            det_dir = track_dirs(linked[0], linked[2], det_cell, det_count, det_dir, dataset.I, dataset.J)
         det_cell, ids, det_count = linked[:3]
         tracking = {**tracking, **track_summary(linked[2], linked[3], linked[4])}
-    result = match_and_score(det_cell, det_count, table, dataset.metadata_rows, doa_threshold_deg, dataset.I, dataset.J)
+    result = match_and_score(det_cell, det_count, table, dataset.metadata_rows, doa_threshold_deg, dataset.I, dataset.J,
+                             det_dir=det_dir, refine=refine)
     result.update(threshold=float(threshold), max_peaks=int(max_peaks), doa_threshold_deg=float(doa_threshold_deg),
-                  tta_patterns=list(patterns), tracking=tracking)
+                  tta_patterns=list(patterns), tracking=tracking, refine=refine)
     if events_dir is not None:
         names = segment_names(dataset) if names is None else list(names)
         cells, counts = det_cell.cpu().numpy(), det_count.cpu().numpy()
         ids = ids.cpu().numpy() if ids is not None else None
+        dirs = det_dir.cpu().numpy() if det_dir is not None else None
         result["event_files"] = [str(write_events_csv(Path(events_dir) / f"{name}.csv",
                                                       events_for_segment(cells, counts, table, s, dataset.I, dataset.J,
-                                                                         ids=ids)))
+                                                                         ids=ids, dirs=dirs)))
                                  for s, name in enumerate(names)]
         if linked is not None:
             rows, born, offsets = (t.cpu().numpy() for t in linked[3:6])

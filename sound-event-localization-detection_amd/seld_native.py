@@ -145,6 +145,9 @@ def _declare(lib):
                                          ctypes.c_float, _int, _ptr, _ptr, _ptr, _ptr, _ptr]
     lib.seld_track_link.argtypes = [_ptr, _ptr, _int, _ptr, _i64, _ptr, _int, _int, _int, _int, _int, _ptr, _ptr, _ptr, _ptr,
                                     _ptr, _ptr, _ptr]
+    lib.seld_grid_decode_refine.argtypes = [_ptr, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _pi32, _int,
+                                            ctypes.c_float, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]
+    lib.seld_doa_match_dirs.argtypes = [_ptr, _ptr, _int, _ptr, _ptr, _i64, ctypes.c_double, _ptr, _ptr, _ptr]
     return lib
 
 

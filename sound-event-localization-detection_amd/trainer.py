@@ -1108,7 +1108,7 @@ def _tta_logits(model, dataset, batch_size, device, patterns):
 
 
 def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, threshold=None, max_peaks=None,
-                  doa_threshold_deg=None, events_dir=None, use_ema=None, tta=None, track=None):
+                  doa_threshold_deg=None, events_dir=None, use_ema=None, tta=None, track=None, refine=None):
     """Evaluate a checkpoint on what it detects: the windows of ``test_loader.dataset`` (an SELDDataset) run through the
     model in timeline order, the overlapping grid maps are decoded into DOA events on the GPU and scored against the
     dataset's CSV rows.  Returns F20, ER20, LE_CD, LR_CD, TP, FP, FN, N, per_class (seld_eval.evaluate_logits); with
@@ -1118,7 +1118,9 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
     None reads Config.SELD_TTA_PATTERNS): the model runs on every transformed copy of a window and the un-permuted grid
     maps are averaged before the peak test; the result's "tta_patterns" lists them.
     ``track``: track linking of the detections (seld_eval.evaluate_logits: None reads Config.SELD_TRACK, True or a dict
-    of gate_deg / max_gap / min_len switches it on); the result's "tracking" holds its counts."""
+    of gate_deg / max_gap / min_len switches it on); the result's "tracking" holds its counts.
+    ``refine``: sub-cell DOA refinement of the detections (seld_eval.evaluate_logits: None reads Config.SELD_REFINE;
+    DESIGN.md section 15); the result's "refine" says whether the scored and written directions are refined."""
     import seld_eval
     test_dataset = test_loader.dataset
     patterns = seld_augment.tta_patterns(getattr(config, "SELD_TTA_PATTERNS", ()) if tta is None else tta)
@@ -1144,7 +1146,7 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
     results = seld_eval.evaluate_logits(timeline_logits(model, test_dataset, batch_size, device, patterns=patterns),
                                         test_dataset, threshold=threshold, max_peaks=max_peaks,
                                         doa_threshold_deg=doa_threshold_deg, events_dir=events_dir, patterns=patterns,
-                                        track=track)
+                                        track=track, refine=refine)
     results["checkpoint_epoch"] = checkpoint["epoch"]
     if results.get("tracking"):
         tr = results["tracking"]
