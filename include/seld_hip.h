@@ -598,6 +598,36 @@ int seld_grid_decode_refine(const void* logits, int is_bf16, int64_t w0, int64_t
 int seld_doa_match_dirs(const float* det_dir, const int32_t* det_count, int K, const int32_t* ref_offsets,
                         const int32_t* ref_dirs, int64_t nq, double thr_deg, int32_t* stats, double* cost, void* stream);
 
+/* ---- sample-rate conversion in front of the 24 kHz feature kernels (csrc/resample.hip) ---------
+ * No reference counterpart (dataset.py:27-58 hands the file's rate to MelSpectrogram).  A windowed-sinc polyphase FIR with
+ * zero delay and zero extension: with g = gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g,
+ *   y[m] = sum over t of x[q - (t - half)] * table[p][t],  p = (m * down) mod up,  q = (m * down) div up,  x = 0 outside
+ *   [0, L),  m = 0 .. L_out - 1,  L_out = ceil(L * up / down);  output sample m sits at time m / rate_out.
+ *
+ * seld_resample_plan: the geometry of the designed table for a pair of rates -- host only, no GPU.  Any pointer may be
+ * NULL.  -1, with the rate and the limit in seld_last_error(), for a rate that is not positive or needs up > 320 phases
+ * or more than 1100 taps per output (8000, 11025, 12000, 16000, 22050, 32000, 44100, 48000, 88200, 96000 and 192000 Hz
+ * to 24000 Hz pass).
+ *
+ * seld_resample_table_host: the designed table itself -- host only, no GPU, HOST pointers: table [up][taps] fp32 and / or
+ * table_f64 [up][taps] (either may be NULL), table = (float) table_f64.  table[p][t] = g[p + (t - half) * up] of the
+ * prototype on the dense grid fs = rate_in * up: Kaiser window (beta 10.06) over 64 zero crossings per side of a sinc
+ * with cut-off 0.95 * min(rate_in, rate_out) / 2, gain up, evaluated in double. */
+int seld_resample_plan(int64_t rate_in, int64_t rate_out, int* up, int* down, int* taps, int* half);
+int seld_resample_table_host(int64_t rate_in, int64_t rate_out, float* table, double* table_f64);
+
+/* The conversion.  pcm [N][C][L] (float, or int16 scaled by 2^-15 on load like seld_logmel_i16), table_dev [up][taps]
+ * fp32 on the DEVICE (the caller uploads what seld_resample_table_host wrote, or a table of its own: taps must be
+ * 2 * half + 1, 1 <= up, down <= 32768, half <= 32768), out [N][C][L_out] fp32 with L_out = ceil(L * up / down) exactly (-1 otherwise).
+ * fp32 accumulation with fused multiply-adds, one output written once: deterministic, and a (clip, channel) row does not
+ * depend on the others of the call.  64-bit sample indices.  No allocation, no synchronise, no state inside the library:
+ * the call needs no seld_init.  -4 when `down` is so large that the input span of one output does not fit 64 KB of LDS
+ * (no designed table is). */
+int seld_resample_f32(const float* pcm, int64_t N, int64_t C, int64_t L, const float* table_dev, int up, int down, int taps,
+                      int half, float* out, int64_t L_out, void* stream);
+int seld_resample_i16(const int16_t* pcm, int64_t N, int64_t C, int64_t L, const float* table_dev, int up, int down, int taps,
+                      int half, float* out, int64_t L_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,9 @@ class Config:
     # Sub-cell DOA refinement of the decoded detections (seld_eval.grid_decode_refine, csrc/seld_refine.hip)
     SELD_REFINE = False         # evaluate_seld / infer.py score and write a direction finer than the 10-degree cell: the
                                 # probability-weighted mean of the unit vectors of the peak cell and its neighbours
+    # Sample-rate conversion of the input (seld_native.resample, csrc/resample.hip)
+    RESAMPLE_INPUT = False      # SELDDataset / audio_to_mel_spectrogram / infer.py convert recordings whose rate is not SR (48 kHz,
+                                # 44.1 kHz, ...) to SR on the GPU before the feature kernels; off: such a recording raises
 
     def __init__(self):
         for folder in (self.OUTPUT_PATH, self.CHECKPOINT_PATH):

@@ -86,7 +86,8 @@ def audio_to_mel_spectrogram(waveform, sample_rate, n_fft=None, hop_length=None,
     n_fft = config.SPECTROGRAM_N_FFT if n_fft is None else n_fft
     hop_length = config.SPECTROGRAM_HOP_LENGTH if hop_length is None else hop_length
     n_mels = config.N_MELS if n_mels is None else n_mels
-    if (int(sample_rate), int(n_fft), int(hop_length), int(n_mels)) != (24000, 960, 480, 64):
+    convert = int(sample_rate) != 24000 and bool(getattr(config, "RESAMPLE_INPUT", False))
+    if (24000 if convert else int(sample_rate), int(n_fft), int(hop_length), int(n_mels)) != (24000, 960, 480, 64):
         raise NotImplementedError(
             "the HIP log-mel kernel is built for sr=24000, n_fft=960, hop=480, n_mels=64 (config.py:85-88); "
             f"got sr={sample_rate}, n_fft={n_fft}, hop={hop_length}, n_mels={n_mels}")
@@ -94,6 +95,8 @@ def audio_to_mel_spectrogram(waveform, sample_rate, n_fft=None, hop_length=None,
     x = waveform.to(_compute_device()) if on_host else waveform
     if x.dtype not in (torch.float32, torch.int16):
         x = x.to(torch.float32)
+    if convert:                                   # Config.RESAMPLE_INPUT: to 24 kHz on the device first
+        x = seld_native.resample(x.contiguous(), int(sample_rate), 24000)
     out = seld_native.logmel(x, layout="cft")
     return out.cpu() if on_host else out
 
@@ -269,10 +272,13 @@ class SELDDataset(Dataset):
         import hashlib
         a, m = Path(audio_path), Path(metadata_path)
         sa, sm = a.stat(), m.stat()
-        key = "|".join(str(v) for v in (a.resolve(), sa.st_size, sa.st_mtime_ns, m.resolve(), sm.st_size, sm.st_mtime_ns,
-                                        getattr(config, "FEATURE_SET", "logmel"), self.I, self.J, self.sample_rate,
-                                        config.SPECTROGRAM_N_FFT, config.SPECTROGRAM_HOP_LENGTH, config.N_MELS,
-                                        self.num_classes, getattr(config, "GRID_CELL_DEGREES", 10), "v2"))
+        fields = (a.resolve(), sa.st_size, sa.st_mtime_ns, m.resolve(), sm.st_size, sm.st_mtime_ns,
+                  getattr(config, "FEATURE_SET", "logmel"), self.I, self.J, self.sample_rate,
+                  config.SPECTROGRAM_N_FFT, config.SPECTROGRAM_HOP_LENGTH, config.N_MELS,
+                  self.num_classes, getattr(config, "GRID_CELL_DEGREES", 10), "v2")
+        if getattr(config, "RESAMPLE_INPUT", False):       # the converter's design is part of what the arrays depend on;
+            fields += ("resample-kaiser10.06-zc64-v1",)    # with the switch off the names are the ones they always were
+        key = "|".join(str(v) for v in fields)
         return Path(root) / f"{a.stem}.{hashlib.sha1(key.encode()).hexdigest()[:16]}.npz"
 
     def _file_features(self, audio_path, metadata_path):
@@ -300,11 +306,16 @@ class SELDDataset(Dataset):
         return self._features_from_pcm(pcm, rate, _read_metadata_rows(metadata_path))
 
     def _features_from_pcm(self, pcm, rate, rows):
+        signal = pcm
         if int(rate) != self.sample_rate:
-            raise NotImplementedError(f"sample rate {rate} != {self.sample_rate}: the feature kernel is built for 24 kHz")
+            if not getattr(config, "RESAMPLE_INPUT", False):
+                raise NotImplementedError(f"sample rate {rate} != {self.sample_rate}: the feature kernel is built for 24 kHz")
+            # Config.RESAMPLE_INPUT: polyphase conversion on the device (csrc/resample.hip), fp32 straight into the feature
+            # kernels; the labels below keep the FILE's duration, so they do not move
+            signal = seld_native.resample(pcm.contiguous(), int(rate), self.sample_rate)
         # [F, C_total, 64]: the reference's per-channel log-mel, optionally followed by the north-star additions
         # (FOA intensity vectors / GCC-PHAT, csrc/spatial.hip) as extra input channels
-        spec = seld_native.spatial_features(pcm, getattr(config, "FEATURE_SET", "logmel"))
+        spec = seld_native.spatial_features(signal, getattr(config, "FEATURE_SET", "logmel"))
         audio_duration = pcm.shape[1] / rate                                   # dataset.py:232 (float64)
         if self.use_gaussian_augmentation:                                      # smrl_seld_gaussian.py:608-618
             mask, _, _ = augment_with_gaussian_mask(rows, audio_duration, self.I, self.J,

@@ -1,6 +1,7 @@
 """Inference CLI: recordings -> SELD event CSVs, one per recording (no reference counterpart).
 
-    python infer.py --checkpoint best_model.pth --out-dir DIR [--tta all | --tta 0,2,9] [--track] [--refine] a.wav [b.wav ...]
+    python infer.py --checkpoint best_model.pth --out-dir DIR [--tta all | --tta 0,2,9] [--track] [--refine] [--resample]
+                    a.wav [b.wav ...]
 
 Each recording becomes a one-segment timeline (features through the dataset's own path, no metadata rows), its 5 s
 windows run through the checkpoint's model in timeline order, and the decoded events are written to DIR/<stem>.csv as
@@ -8,6 +9,7 @@ windows run through the checkpoint's model in timeline order, and the decoded ev
 detections are linked into tracks first: the third column is the track id, and DIR/<stem>.tracks.csv
 lists ``class,track,onset_m,offset_m,detected_frames`` of every kept track.  With ``--refine`` azimuth and elevation are the
 nearest integer degrees of the detections' sub-cell directions, not the centres of their 10-degree cells.
+With ``--resample`` a recording whose rate is not 24 kHz is converted on the GPU first.
 """
 import argparse
 import logging
@@ -50,10 +52,14 @@ def parse_args(argv=None):
     p.add_argument("--refine", action=argparse.BooleanOptionalAction, default=bool(getattr(cfg, "SELD_REFINE", False)),
                    help="write sub-cell directions (integer degrees) in place of the 10-degree cell centres "
                         "(default: Config.SELD_REFINE; --no-refine switches it off)")
+    p.add_argument("--resample", action=argparse.BooleanOptionalAction, default=bool(getattr(cfg, "RESAMPLE_INPUT", False)),
+                   help="convert recordings whose rate is not 24 kHz (48 kHz, 44.1 kHz, ...) on the GPU first "
+                        "(default: Config.RESAMPLE_INPUT; --no-resample: such a recording is an error)")
     p.add_argument("--device", default=None, help="default: the current ROCm device")
     p.add_argument("--use-ema", action="store_true",
                    help="load the checkpoint's ema_state_dict (default: Config.EVAL_USE_EMA); an error when it has none")
-    p.add_argument("wavs", nargs="+", help="PCM WAV recordings (24 kHz)")
+    p.add_argument("wavs", nargs="+", help="PCM WAV recordings: 24 kHz, or with --resample any rate the converter covers "
+                                             "(8, 11.025, 12, 16, 22.05, 32, 44.1, 48, 88.2, 96, 192 kHz)")
     return p.parse_args(argv)
 
 
@@ -79,8 +85,13 @@ def main(argv=None):
     written = []
     for wav in args.wavs:
         pcm, rate = _pcm(wav)
-        ds = dataset.SELDDataset.from_pcm([pcm], [np.zeros((0, 5), dtype=np.int64)], sample_rate=rate, device=device,
-                                          use_gaussian_augmentation=False)
+        saved = dataset.config.RESAMPLE_INPUT
+        dataset.config.RESAMPLE_INPUT = bool(args.resample)      # the switch the dataset path reads, for this run only
+        try:
+            ds = dataset.SELDDataset.from_pcm([pcm], [np.zeros((0, 5), dtype=np.int64)], sample_rate=rate, device=device,
+                                              use_gaussian_augmentation=False)
+        finally:
+            dataset.config.RESAMPLE_INPUT = saved
         seld_augment.check_tta(patterns, getattr(trainer.config, "FEATURE_SET", "logmel"), ds.n_channels)
         if model is None:
             model = trainer.prepare_model_for_device(trainer.build_model((ds.I, ds.J), True, n_channels=ds.n_channels),

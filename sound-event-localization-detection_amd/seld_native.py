@@ -148,6 +148,10 @@ def _declare(lib):
     lib.seld_grid_decode_refine.argtypes = [_ptr, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _pi32, _int,
                                             ctypes.c_float, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]
     lib.seld_doa_match_dirs.argtypes = [_ptr, _ptr, _int, _ptr, _ptr, _i64, ctypes.c_double, _ptr, _ptr, _ptr]
+    lib.seld_resample_plan.argtypes = [_i64, _i64, _pi32, _pi32, _pi32, _pi32]
+    lib.seld_resample_table_host.argtypes = [_i64, _i64, _ptr, _ptr]
+    for fn in (lib.seld_resample_f32, lib.seld_resample_i16):
+        fn.argtypes = [_ptr, _i64, _i64, _i64, _ptr, _int, _int, _int, _int, _ptr, _i64, _ptr]
     return lib
 
 
@@ -278,6 +282,83 @@ def logmel(pcm: torch.Tensor, layout: str = "cft", out: torch.Tensor | None = No
     with _device_guard(index):
         check(fn(ctypes.c_void_p(pcm.data_ptr()), n, c, length, ctypes.c_void_p(out.data_ptr()), code,
                  _stream_ptr(pcm.device)), "seld_logmel")
+    return out[0] if squeeze else out
+
+
+# --------------------------------------------------------------------------- sample-rate conversion
+
+SAMPLE_RATE = 24000
+_resample_tables = {}
+
+
+def resample_plan(rate_in: int, rate_out: int = SAMPLE_RATE):
+    """(up, down, taps, half) of the designed polyphase table for ``rate_in -> rate_out``; host
+    only.  Raises for a rate the design does not cover (more than 320 phases or 1100 taps per output)."""
+    vals = [ctypes.c_int32() for _ in range(4)]
+    check(load_library().seld_resample_plan(int(rate_in), int(rate_out), *[ctypes.byref(v) for v in vals]),
+          "seld_resample_plan")
+    return tuple(int(v.value) for v in vals)
+
+
+def resample_length(num_samples: int, rate_in: int, rate_out: int = SAMPLE_RATE) -> int:
+    """Output samples for ``num_samples`` input samples: ceil(L * up / down), exact integers."""
+    up, down, _, _ = resample_plan(rate_in, rate_out)
+    return -((-int(num_samples) * up) // down)
+
+
+def resample_table(rate_in: int, rate_out: int = SAMPLE_RATE):
+    """The designed table on the host: (float32 [up, taps], float64 [up, taps]) as numpy arrays."""
+    import numpy as np
+    up, _, taps, _ = resample_plan(rate_in, rate_out)
+    t32, t64 = np.zeros((up, taps), dtype=np.float32), np.zeros((up, taps), dtype=np.float64)
+    check(load_library().seld_resample_table_host(int(rate_in), int(rate_out), ctypes.c_void_p(t32.ctypes.data),
+                                                  ctypes.c_void_p(t64.ctypes.data)), "seld_resample_table_host")
+    return t32, t64
+
+
+def _resample_table_device(rate_in: int, rate_out: int, device, index: int):
+    """The table of a rate pair, designed once and kept on the device it was asked for."""
+    key = (int(rate_in), int(rate_out), index)
+    hit = _resample_tables.get(key)
+    if hit is None:
+        plan = resample_plan(rate_in, rate_out)
+        hit = (plan, torch.from_numpy(resample_table(rate_in, rate_out)[0]).to(device))
+        _resample_tables[key] = hit
+    return hit
+
+
+def resample(pcm: torch.Tensor, rate_in: int, rate_out: int = SAMPLE_RATE, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Sample-rate conversion on the GPU (csrc/resample.hip).  ``pcm``: [N, C, L] or [C, L], float32 in [-1, 1) or int16
+    (scaled by 2^-15), contiguous; returns float32 [N, C, ceil(L * up / down)] (or [C, ...]): what the 24 kHz feature
+    kernels take as it is.  The table of a rate pair is designed on first use and stays on the device."""
+    squeeze = pcm.dim() == 2
+    if squeeze:
+        pcm = pcm.unsqueeze(0)
+    if pcm.dim() != 3:
+        raise ValueError("pcm must be [N, C, L] or [C, L]")
+    if not pcm.is_cuda:
+        raise SeldNativeError("resample: pcm must live on the GPU (no CPU fallback in the product path)")
+    if pcm.dtype not in (torch.float32, torch.int16):
+        raise TypeError(f"resample: pcm dtype must be float32 or int16, got {pcm.dtype}")
+    if not pcm.is_contiguous():
+        raise ValueError("resample: pcm must be contiguous")
+    n, c, length = pcm.shape
+    index = ensure_init(pcm.device)
+    (up, down, taps, half), table = _resample_table_device(rate_in, rate_out, pcm.device, index)
+    out_len = -((-length * up) // down)
+    shape = (n, c, out_len)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=pcm.device)
+    else:
+        if squeeze and out.dim() == 2:                      # [C, L] in: [C, L_out] out
+            out = out.unsqueeze(0)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != pcm.device:
+            raise ValueError(f"resample: out must be contiguous float32 {shape[1:] if squeeze else shape} on {pcm.device}")
+    lib = load_library()
+    fn = lib.seld_resample_f32 if pcm.dtype == torch.float32 else lib.seld_resample_i16
+    with _device_guard(index):
+        check(fn(ctypes.c_void_p(pcm.data_ptr()), n, c, length, ctypes.c_void_p(table.data_ptr()), up, down, taps, half,
+                 ctypes.c_void_p(out.data_ptr()), out_len, _stream_ptr(pcm.device)), "seld_resample")
     return out[0] if squeeze else out
 
 
