@@ -598,6 +598,36 @@ int seld_grid_decode_refine(const void* logits, int is_bf16, int64_t w0, int64_t
 int seld_doa_match_dirs(const float* det_dir, const int32_t* det_count, int K, const int32_t* ref_offsets,
                         const int32_t* ref_dirs, int64_t nq, double thr_deg, int32_t* stats, double* cost, void* stream);
 
+/* ---- threshold sweep of the evaluation (csrc/seld_sweep.hip) --------------------------------------
+ * The detections of a (q, c) are sorted by (score descending, cell ascending) and the peak test does not depend on the
+ * threshold, so the list at any threshold t >= t0 is a prefix of the list decoded at t0.
+ *
+ * seld_doa_match_prefix: seld_doa_match (det_dir NULL: det_cell, I, J name the detections) or seld_doa_match_dirs (det_dir
+ * f32 [nq][13][K][2], 8-byte aligned, in place of det_cell, I, J) for every prefix of every (q, c) in one launch:
+ *   ptp int32 [nq][13][K+1], pcost f64 [nq][13][K+1]: entry p <= min(det_count, K) = the tp and the cost that export
+ *   writes when the entry's count is replaced by p (tp equal, cost bit-equal); entries past the count repeat the entry at
+ *   the count.  An entry seld_doa_match refuses (more than 8 references, a count outside 0..K) is -1 / NaN throughout.
+ * One thread per (q, c); no allocation, no synchronise.  -1, launching nothing, for K outside 1..8, bad extents or a null
+ * pointer. */
+int seld_doa_match_prefix(const int32_t* det_cell, const float* det_dir, const int32_t* det_count, int K,
+                          const int32_t* ref_offsets, const int32_t* ref_dirs, int64_t nq, int I, int J, double thr_deg,
+                          int32_t* ptp, double* pcost, void* stream);
+
+/* seld_sweep_score: the sums behind the metrics at T thresholds from the prefix tables.  `thresholds` is a HOST pointer to T
+ * floats (1 <= T <= 64, strictly ascending, in (0, 1]; else -1), read before the launch and passed by value in the kernel
+ * arguments.  With R = ref_offsets[qc+1] - ref_offsets[qc], P_t = the number of LEADING detections of (q, c) with
+ * det_score >= thresholds[t] (fp32, the decode's comparison; det_score f32 [nq][13][K], det_count clamped to 0..K),
+ * k = min(R, P_t), tp = ptp[qc][P_t] (a refused entry: k = tp = -1) and chunk x = meta-frames [x chunk, min(nq, (x+1) chunk)):
+ *   counts int64 [T][n_chunks][13][5] = per class the sums of (tp, P_t - tp, R - tp, R, k) over the chunk,
+ *   sdi    int64 [T][n_chunks][3]     = sums over the chunk's meta-frames of (min(FN_q, FP_q), max(0, FN_q - FP_q),
+ *                                       max(0, FP_q - FN_q)), FN_q / FP_q summed over the 13 classes of q,
+ *   cost   f64   [T][n_chunks][13]    = per class the sum of pcost[qc][P_t] in ascending q,
+ * n_chunks = ceil(nq / chunk), chunk >= 1.  One lane per threshold, one wave per chunk, plain stores: a repeated run is
+ * bit-identical.  No allocation, no synchronise. */
+int seld_sweep_score(const int32_t* ptp, const double* pcost, const float* det_score, const int32_t* det_count, int K,
+                     const int32_t* ref_offsets, int64_t nq, const float* thresholds, int T, int64_t chunk,
+                     int64_t* counts, int64_t* sdi, double* cost, void* stream);
+
 /* ---- sample-rate conversion in front of the 24 kHz feature kernels (csrc/resample.hip) ---------
  * No reference counterpart (dataset.py:27-58 hands the file's rate to MelSpectrogram).  A windowed-sinc polyphase FIR with
  * zero delay and zero extension: with g = gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g,

@@ -186,6 +186,12 @@ class Config:
     # Sub-cell DOA refinement of the decoded detections (seld_eval.grid_decode_refine, csrc/seld_refine.hip)
     SELD_REFINE = False         # evaluate_seld / infer.py score and write a direction finer than the 10-degree cell: the
                                 # probability-weighted mean of the unit vectors of the peak cell and its neighbours
+    # Threshold sweep and per-class thresholds (seld_eval.sweep / apply_thresholds, csrc/seld_sweep.hip)
+    SELD_SWEEP_THRESHOLDS = ()  # evaluate_seld also scores these detection thresholds from its one decode (at the lowest of
+                                # them): a list, or a spelling such as "0.05:0.95:0.05" (start:stop:step); () = off.  Up to 64
+    SELD_CLASS_THRESHOLDS = None  # 13 detection thresholds, one per class, or the path of a thresholds.json that a sweep
+                                # wrote (thresholds_out); takes the place of SELD_THRESHOLD.  None = one threshold for all
+    SELD_THRESHOLDS_OUT = None  # evaluate_seld writes the swept grid and its best global / per-class thresholds to this file
     # Sample-rate conversion of the input (seld_native.resample, csrc/resample.hip)
     RESAMPLE_INPUT = False      # SELDDataset / audio_to_mel_spectrogram / infer.py convert recordings whose rate is not SR (48 kHz,
                                 # 44.1 kHz, ...) to SR on the GPU before the feature kernels; off: such a recording raises

@@ -1,7 +1,7 @@
 """Inference CLI: recordings -> SELD event CSVs, one per recording (no reference counterpart).
 
     python infer.py --checkpoint best_model.pth --out-dir DIR [--tta all | --tta 0,2,9] [--track] [--refine] [--resample]
-                    a.wav [b.wav ...]
+                    [--thresholds thresholds.json] a.wav [b.wav ...]
 
 Each recording becomes a one-segment timeline (features through the dataset's own path, no metadata rows), its 5 s
 windows run through the checkpoint's model in timeline order, and the decoded events are written to DIR/<stem>.csv as
@@ -10,6 +10,8 @@ detections are linked into tracks first: the third column
 lists ``class,track,onset_m,offset_m,detected_frames`` of every kept track.  With ``--refine`` azimuth and elevation are the
 nearest integer degrees of the detections' sub-cell directions, not the centres of their 10-degree cells.
 With ``--resample`` a recording whose rate is not 24 kHz is converted on the GPU first.
+With ``--thresholds`` the per-class detection thresholds of a sweep's thresholds file take the place of ``--threshold``
+(DESIGN.md section 17).
 """
 import argparse
 import logging
@@ -36,6 +38,9 @@ def parse_args(argv=None):
     p.add_argument("--model-type", default=None, help="model kind; default: the checkpoint's Config, else Config.MODEL_TYPE")
     p.add_argument("--batch-size", type=int, default=cfg.BATCH_SIZE)
     p.add_argument("--threshold", type=float, default=cfg.SELD_THRESHOLD)
+    p.add_argument("--thresholds", default=None,
+                   help="thresholds file written by a sweep (evaluate_seld(..., thresholds_out=FILE)): its per-class "
+                        "detection thresholds are applied; wins over --threshold")
     p.add_argument("--max-peaks", type=int, default=cfg.SELD_MAX_PEAKS)
     p.add_argument("--tta", default=None,
                    help="test-time augmentation: 'all' or spatial patterns such as 0,2,9 whose un-permuted grid maps are "
@@ -81,6 +86,10 @@ def main(argv=None):
     patterns = seld_augment.tta_patterns(getattr(trainer.config, "SELD_TTA_PATTERNS", ()) if args.tta is None else args.tta)
     track = {"gate_deg": args.track_gate_deg, "max_gap": args.track_max_gap, "min_len": args.track_min_len} \
         if args.track else False
+    per_class = None
+    if args.thresholds:
+        per_class = seld_eval.load_thresholds(args.thresholds, max_peaks=args.max_peaks, tta_patterns=patterns,
+                                              refine=args.refine)["per_class"]
     model = None
     written = []
     for wav in args.wavs:
@@ -99,9 +108,9 @@ def main(argv=None):
             model.load_state_dict(trainer.select_state_dict(checkpoint, True if args.use_ema else None))
             model.eval()
         result = seld_eval.evaluate_logits(trainer.timeline_logits(model, ds, args.batch_size, device, patterns=patterns),
-                                           ds, threshold=args.threshold, max_peaks=args.max_peaks, events_dir=args.out_dir,
-                                           names=[Path(wav).stem], patterns=patterns, track=track,
-                                           refine=args.refine)
+                                           ds, threshold=None if per_class else args.threshold, max_peaks=args.max_peaks,
+                                           events_dir=args.out_dir, names=[Path(wav).stem], patterns=patterns, track=track,
+                                           refine=args.refine, sweep=(), class_thresholds=per_class)
         path = result["event_files"][0]
         written.append(path)
         if result["tracking"]:

@@ -23,6 +23,12 @@ Sub-cell DOA refinement (csrc/seld_refine.hip): ``refine``
                            from the peak's 3x3 neighbourhood of the class map while it is still in LDS
   seld_doa_match_dirs      seld_doa_match on those float directions
 
+Threshold sweep and per-class thresholds (csrc/seld_sweep.hip): ``sweep`` / ``class_thresholds`` on
+evaluate_logits decode once at the lowest threshold involved -- the detections at a higher one are a prefix -- and run
+
+  seld_doa_match_prefix    seld_doa_match / seld_doa_match_dirs for every prefix of every (meta-frame, class) at once
+  seld_sweep_score         the sums behind the metrics for up to 64 thresholds from those tables, one lane per threshold
+
 The host side here builds the tables (meta-frames, reference CSR), drives the decode batch by batch as the windows are
 computed, reduces the match counts on the device and writes event CSVs.  There is no CPU fallback.
 """
@@ -552,8 +558,12 @@ def score(stats: torch.Tensor, cost: torch.Tensor) -> dict:
                           torch.clamp(fp_q - fn_q, min=0).sum()])                                  # S, D, I
     counts = torch.stack([tp.sum(0), fp_qc.sum(0), fn_qc.sum(0), r.sum(0), k.sum(0)])            # [5, 13]
     cost_c = cost.to(torch.float64).sum(0)
-    counts, totals, cost_c = counts.cpu().numpy(), totals.cpu().numpy(), cost_c.cpu().numpy()
+    return _score_record(counts.cpu().numpy(), totals.cpu().numpy(), cost_c.cpu().numpy())
 
+
+def _score_record(counts, totals, cost_c) -> dict:
+    """The record ``score`` returns, from the host copies of counts int64 [5, 13] = (tp, fp, fn, r, k) per class, totals
+    int64 [3] = (S, D, I) and cost_c float64 [13]."""
     def div(a, b):
         return float(a) / float(b) if b else math.nan
 
@@ -568,6 +578,12 @@ def score(stats: torch.Tensor, cost: torch.Tensor) -> dict:
             "per_class": per_class}
 
 
+def device_references(table: MetaFrameTable, metadata_rows, device):
+    """``reference_table`` on ``device``: (offsets int32 [Q * 13 + 1], dirs int32 [R, 2])."""
+    offsets, dirs = reference_table(table, metadata_rows)
+    return torch.from_numpy(offsets).to(device), torch.from_numpy(dirs).to(device)
+
+
 def refine_setting(refine) -> bool:
     """``refine`` as evaluate_logits takes it -> bool; None reads Config.SELD_REFINE."""
     from config import Config
@@ -576,21 +592,304 @@ def refine_setting(refine) -> bool:
 
 def match_and_score(det_cell: torch.Tensor, det_count: torch.Tensor, table: MetaFrameTable, metadata_rows,
                     doa_threshold_deg: float, I: int = GRID_I, J: int = GRID_J, det_dir: torch.Tensor | None = None,
-                    refine=None) -> dict:
+                    refine=None, refs=None) -> dict:
     """References (numpy CSR) -> seld_doa_match on the detections' device -> score().
     ``det_dir`` with ``refine`` (None reads Config.SELD_REFINE when ``det_dir`` is given): the detections' directions
-    f32 [Q, 13, K, 2] are matched by seld_doa_match_dirs in place of the cell centres."""
+    f32 [Q, 13, K, 2] are matched by seld_doa_match_dirs in place of the cell centres.
+    ``refs``: what ``device_references`` returned for this timeline, for a caller that matches more than once."""
     if det_dir is None and refine:
         raise ValueError("match_and_score: refine needs det_dir (decode(..., refine=True))")
     refine = det_dir is not None and refine_setting(refine)
-    offsets, dirs = reference_table(table, metadata_rows)
-    device = det_cell.device
-    offsets, dirs = torch.from_numpy(offsets).to(device), torch.from_numpy(dirs).to(device)
+    offsets, dirs = device_references(table, metadata_rows, det_cell.device) if refs is None else refs
     if refine:
         stats, cost = doa_match_dirs(det_dir, det_count, offsets, dirs, doa_threshold_deg)
     else:
         stats, cost = doa_match(det_cell, det_count, offsets, dirs, doa_threshold_deg, I, J)
     return score(stats, cost)
+
+
+# ------------------------------------------------------------------------------------------------------ threshold sweep
+
+MAX_SWEEP = 64             # thresholds one seld_sweep_score launch takes (one lane each)
+SWEEP_CHUNK = 64           # meta-frames per partial sum of seld_sweep_score
+THRESHOLDS_VERSION = 1     # of the thresholds file
+
+
+def _f32(value) -> float:
+    """``value`` rounded once to fp32, as a Python float: the number the decode and the sweep kernel compare against."""
+    return float(np.float32(value))
+
+
+def parse_sweep(spec) -> tuple:
+    """The thresholds of a sweep, ascending, each rounded once to fp32.  ``spec``: None, () or "" (off: returns ()), a
+    sequence of numbers, or a string: "start:stop:step" (inclusive; "0.05:0.95:0.05" is 19 values) or a comma list
+    ("0.1,0.25,0.5").  Raises ValueError for values outside (0, 1], duplicates (after the rounding) or more than 64."""
+    if spec is None:
+        return ()
+    if isinstance(spec, str):
+        text = spec.strip()
+        if not text:
+            return ()
+        try:
+            if ":" in text:
+                parts = [float(v) for v in text.split(":")]
+                if len(parts) != 3:
+                    raise ValueError
+                start, stop, step = parts
+                if not (step > 0 and stop >= start):
+                    raise ValueError
+                n = int(math.floor((stop - start) / step + 1e-9)) + 1
+                values = [round(start + i * step, 12) for i in range(n)]
+            else:
+                values = [float(v) for v in text.split(",") if v.strip()]
+        except ValueError:
+            raise ValueError(f"sweep: expected start:stop:step with step > 0 and stop >= start, or a comma list, got "
+                             f"{spec!r}") from None
+    else:
+        values = [float(v) for v in spec]
+    values = sorted(_f32(v) for v in values)
+    if len(values) > MAX_SWEEP:
+        raise ValueError(f"sweep: at most {MAX_SWEEP} thresholds, got {len(values)}")
+    if any(not (0.0 < v <= 1.0) for v in values):
+        raise ValueError(f"sweep: thresholds must lie in (0, 1], got {values}")
+    if any(b <= a for a, b in zip(values, values[1:])):
+        raise ValueError(f"sweep: duplicate thresholds in {values}")
+    return tuple(values)
+
+
+def class_threshold_vector(values) -> list:
+    """13 detection thresholds, one per class, each rounded once to fp32; ValueError unless 13 numbers in (0, 1]."""
+    try:
+        out = [_f32(v) for v in values]
+    except TypeError:
+        raise ValueError("class_thresholds: expected 13 numbers or the path of a thresholds file") from None
+    if len(out) != NUM_EVENT_CLASSES or any(not (0.0 < v <= 1.0) for v in out):
+        raise ValueError(f"class_thresholds: expected {NUM_EVENT_CLASSES} numbers in (0, 1], got {out}")
+    return out
+
+
+def apply_thresholds(det_cell: torch.Tensor, det_score: torch.Tensor, det_count: torch.Tensor, class_thresholds,
+                     det_dir: torch.Tensor | None = None):
+    """The detections of a decode at a lower threshold cut to per-class thresholds: each (q, c) list keeps its LEADING
+    detections with score >= class_thresholds[c] (fp32, the decode's comparison) -- the lists are sorted by score, so this
+    is what the decode at that threshold keeps -- and is restored to the decode's conventions
+    past the new count (cell -1, score 0, direction 0).  Returns new tensors (det_cell, det_score, det_count) and, given
+    ``det_dir``, det_dir; framework ops where the tensors live."""
+    thr = torch.tensor(class_threshold_vector(class_thresholds), dtype=torch.float32, device=det_score.device)
+    rank = torch.arange(int(det_score.shape[-1]), device=det_score.device)
+    ok = (rank < det_count[..., None]) & (det_score >= thr[None, :, None])
+    keep = torch.cumprod(ok.to(torch.int32), dim=-1).bool()
+    out = (torch.where(keep, det_cell, torch.full_like(det_cell, -1)),
+           torch.where(keep, det_score, torch.zeros_like(det_score)), keep.sum(-1).to(det_count.dtype))
+    if det_dir is not None:
+        out += (torch.where(keep[..., None], det_dir, torch.zeros_like(det_dir)),)
+    return out
+
+
+def doa_match_prefix(det_cell: torch.Tensor, det_count: torch.Tensor, ref_offsets: torch.Tensor, ref_dirs: torch.Tensor,
+                     doa_threshold_deg: float, I: int = GRID_I, J: int = GRID_J, det_dir: torch.Tensor | None = None):
+    """seld_doa_match_prefix: (ptp int32 [Q, 13, K + 1], pcost f64 [Q, 13, K + 1]); entry p is the tp and cost of
+    ``doa_match`` (``doa_match_dirs`` given ``det_dir`` f32 [Q, 13, K, 2]) with the entry's count replaced by p, entries
+    past the count repeat the one at the count."""
+    device = det_count.device
+    if not det_count.is_cuda:
+        raise SeldNativeError("doa_match_prefix: detections must live on the GPU (no CPU fallback)")
+    q = int(det_count.shape[0])
+    if det_dir is not None:
+        if det_dir.dim() != 4 or det_dir.shape[1] != NUM_EVENT_CLASSES or det_dir.shape[3] != 2 or \
+                tuple(det_count.shape) != tuple(det_dir.shape[:2]):
+            raise ValueError("doa_match_prefix: det_dir must be [Q, 13, K, 2] and det_count [Q, 13]")
+        det_dir, k = det_dir.to(torch.float32).contiguous(), int(det_dir.shape[2])
+        det_cell = None
+    else:
+        det_cell, k = det_cell.to(torch.int32).contiguous(), int(det_cell.shape[-1])
+    if ref_offsets.numel() != q * NUM_EVENT_CLASSES + 1:
+        raise ValueError("doa_match_prefix: ref_offsets must have Q * 13 + 1 entries")
+    index = ensure_init(device)
+    ptp = torch.empty((q, NUM_EVENT_CLASSES, k + 1), dtype=torch.int32, device=device)
+    pcost = torch.empty((q, NUM_EVENT_CLASSES, k + 1), dtype=torch.float64, device=device)
+    dirs = ref_dirs if ref_dirs.numel() else torch.zeros((1, 2), dtype=torch.int32, device=device)
+    det_count = det_count.to(torch.int32).contiguous()
+    ref_offsets, dirs = ref_offsets.to(torch.int32).contiguous(), dirs.to(torch.int32).contiguous()
+    with _device_guard(index):
+        check(load_library().seld_doa_match_prefix(_p(det_cell), _p(det_dir), _p(det_count), k, _p(ref_offsets), _p(dirs),
+                                                   q, int(I), int(J), float(doa_threshold_deg) + DOA_MARGIN_DEG, _p(ptp),
+                                                   _p(pcost), _stream_ptr(device)), "seld_doa_match_prefix")
+    return ptp, pcost
+
+
+def sweep_score(ptp: torch.Tensor, pcost: torch.Tensor, det_score: torch.Tensor, det_count: torch.Tensor,
+                ref_offsets: torch.Tensor, thresholds, chunk: int = SWEEP_CHUNK):
+    """seld_sweep_score: per threshold and per chunk of ``chunk`` consecutive meta-frames (counts int64 [T, n_chunks, 13,
+    5] = (tp, fp, fn, r, k) per class, sdi int64 [T, n_chunks, 3], cost f64 [T, n_chunks, 13]).  ``thresholds`` go to the
+    kernel as fp32 and are checked by the library (1..64 of them, strictly ascending, in (0, 1]: SeldNativeError)."""
+    device = ptp.device
+    if not ptp.is_cuda:
+        raise SeldNativeError("sweep_score: the prefix tables must live on the GPU (no CPU fallback)")
+    q, k = int(det_score.shape[0]), int(det_score.shape[-1])
+    if tuple(ptp.shape) != (q, NUM_EVENT_CLASSES, k + 1) or tuple(pcost.shape) != tuple(ptp.shape) or \
+            tuple(det_score.shape) != (q, NUM_EVENT_CLASSES, k) or tuple(det_count.shape) != (q, NUM_EVENT_CLASSES):
+        raise ValueError("sweep_score: expected ptp / pcost [Q, 13, K + 1], det_score [Q, 13, K], det_count [Q, 13]")
+    if ref_offsets.numel() != q * NUM_EVENT_CLASSES + 1:
+        raise ValueError("sweep_score: ref_offsets must have Q * 13 + 1 entries")
+    if int(chunk) < 1:
+        raise ValueError("sweep_score: chunk must be >= 1")
+    thr = np.ascontiguousarray(np.asarray(list(thresholds), dtype=np.float32).reshape(-1))
+    index = ensure_init(device)
+    t, n_chunks = len(thr), (q + int(chunk) - 1) // int(chunk)
+    counts = torch.empty((t, n_chunks, NUM_EVENT_CLASSES, 5), dtype=torch.int64, device=device)
+    sdi = torch.empty((t, n_chunks, 3), dtype=torch.int64, device=device)
+    cost = torch.empty((t, n_chunks, NUM_EVENT_CLASSES), dtype=torch.float64, device=device)
+    ptp, pcost = ptp.to(torch.int32).contiguous(), pcost.to(torch.float64).contiguous()
+    det_score, det_count = det_score.to(torch.float32).contiguous(), det_count.to(torch.int32).contiguous()
+    ref_offsets = ref_offsets.to(torch.int32).contiguous()
+    with _device_guard(index):
+        check(load_library().seld_sweep_score(_p(ptp), _p(pcost), _p(det_score), _p(det_count), k, _p(ref_offsets), q,
+                                              thr.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), t, int(chunk),
+                                              _p(counts), _p(sdi), _p(cost), _stream_ptr(device)), "seld_sweep_score")
+    return counts, sdi, cost
+
+
+def _nan_last(value) -> float:
+    return math.inf if value is None or math.isnan(value) else float(value)
+
+
+def select_best(thresholds, f20, er20, per_class_f20, per_class_n) -> dict:
+    """The operating points of a sweep: {"global": threshold or None, "per_class": [13 thresholds or None]}.  "global" is
+    the threshold with the highest F20; ties go to the lower ER20 (nan last), then to the lower threshold; a nan F20
+    never wins, None when every F20 is nan.  "per_class"[c] is chosen the same way on the class's own F20
+    (per_class_f20[t][c]); a class without references (per_class_n[t][c] == 0) takes the global value."""
+    def pick(scores):
+        rows = [(-s, _nan_last(e), t) for s, e, t in zip(scores, er20, thresholds) if not math.isnan(s)]
+        return min(rows)[2] if rows else None
+
+    best = pick(f20)
+    per_class = []
+    for c in range(NUM_EVENT_CLASSES):
+        own = pick([row[c] for row in per_class_f20]) if any(int(row[c]) for row in per_class_n) else None
+        per_class.append(best if own is None else own)
+    return {"global": best, "per_class": per_class}
+
+
+def _sweep_result(thresholds, records) -> dict:
+    """One ``score`` record per threshold -> the sweep's result: score's keys with lists over the thresholds, plus
+    "thresholds", "precision", "recall" and "best" (``select_best``)."""
+    def div(a, b):
+        return float(a) / float(b) if b else math.nan
+
+    out = {"thresholds": [float(t) for t in thresholds]}
+    for key in records[0]:
+        if key == "per_class":
+            out[key] = {name: [rec[key][name] for rec in records] for name in records[0][key]}
+        else:
+            out[key] = [rec[key] for rec in records]
+    out["precision"] = [div(rec["TP"], rec["TP"] + rec["FP"]) for rec in records]
+    out["recall"] = [div(rec["TP"], rec["TP"] + rec["FN"]) for rec in records]
+    out["best"] = select_best(out["thresholds"], out["F20"], out["ER20"], out["per_class"]["F20"], out["per_class"]["N"])
+    return out
+
+
+def sweep(det_cell: torch.Tensor, det_score: torch.Tensor, det_count: torch.Tensor, table: MetaFrameTable, metadata_rows,
+          thresholds, doa_threshold_deg: float, I: int = GRID_I, J: int = GRID_J, det_dir: torch.Tensor | None = None,
+          refs=None, chunk: int = SWEEP_CHUNK) -> dict:
+    """Every threshold of ``thresholds`` (``parse_sweep``) scored from ONE decode at or below the lowest of them
+    (DESIGN.md section 17): seld_doa_match_prefix, seld_sweep_score, one sum over the chunks.  Returns score's keys with
+    lists over the thresholds -- row t is ``score`` of the detections ``apply_thresholds`` leaves at thresholds[t] (the
+    costs to the last bits: they are summed in another shape) -- plus "thresholds", "precision", "recall" and "best".
+    ``det_dir``: the detections' refined directions, matched in place of the cell centres.  ``refs``: as match_and_score."""
+    thresholds = parse_sweep(thresholds)
+    if not thresholds:
+        raise ValueError("sweep: no thresholds")
+    offsets, dirs = device_references(table, metadata_rows, det_count.device) if refs is None else refs
+    ptp, pcost = doa_match_prefix(det_cell, det_count, offsets, dirs, doa_threshold_deg, I, J, det_dir=det_dir)
+    counts, sdi, cost = sweep_score(ptp, pcost, det_score, det_count, offsets, thresholds, chunk)
+    counts, sdi, cost = counts.sum(1).cpu().numpy(), sdi.sum(1).cpu().numpy(), cost.sum(1).cpu().numpy()
+    return _sweep_result(thresholds, [_score_record(counts[t].T, sdi[t], cost[t]) for t in range(len(thresholds))])
+
+
+_sweep = sweep             # (evaluate_logits has a parameter of that name)
+
+
+def write_thresholds(path, swept: dict, max_peaks: int, doa_threshold_deg: float, tta_patterns=(), refine: bool = False,
+                     tracking=None) -> Path:
+    """The operating points of a sweep as a JSON file: version, global, per_class [13], the settings they were found
+    under (max_peaks, doa_threshold_deg, tta_patterns, refine, tracking) and the swept grid with its F20 / ER20 (nan
+    written as null).  ValueError when the sweep has no best threshold (every F20 nan)."""
+    import json
+    best = swept["best"]
+    if best["global"] is None:
+        raise ValueError("write_thresholds: every F20 of the sweep is nan (no references and no detections?)")
+
+    def clean(values):
+        return [None if math.isnan(v) else float(v) for v in values]
+
+    tracking = {k: tracking[k] for k in ("gate_deg", "max_gap", "min_len")} if tracking else None
+    doc = {"version": THRESHOLDS_VERSION, "global": float(best["global"]),
+           "per_class": [float(v) for v in best["per_class"]], "max_peaks": int(max_peaks),
+           "doa_threshold_deg": float(doa_threshold_deg), "tta_patterns": [int(p) for p in tta_patterns],
+           "refine": bool(refine), "tracking": tracking,
+           "grid": {"thresholds": [float(t) for t in swept["thresholds"]], "F20": clean(swept["F20"]),
+                    "ER20": clean(swept["ER20"])}}
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text(json.dumps(doc, indent=1) + "\n")
+    return path
+
+
+def load_thresholds(path, max_peaks=None, tta_patterns=None, refine=None) -> dict:
+    """A thresholds file (``write_thresholds``) validated: version, "global" in (0, 1] and 13 "per_class" values in
+    (0, 1], each returned rounded to fp32 (what they were when written).  ValueError otherwise.  Given the run's
+    ``max_peaks`` / ``tta_patterns`` / ``refine``, warns (UserWarning) when the file was found under other settings: the
+    best operating point moves with them."""
+    import json
+    import warnings
+    path = Path(path)
+    try:
+        doc = json.loads(path.read_text())
+    except (OSError, ValueError) as exc:
+        raise ValueError(f"{path}: not a readable thresholds file ({exc})") from None
+    if not isinstance(doc, dict) or doc.get("version") != THRESHOLDS_VERSION:
+        raise ValueError(f"{path}: expected a thresholds file of version {THRESHOLDS_VERSION}")
+    for key in ("global", "per_class", "max_peaks", "doa_threshold_deg", "tta_patterns", "refine"):
+        if key not in doc:
+            raise ValueError(f"{path}: missing \"{key}\"")
+    glob = doc["global"]
+    if isinstance(glob, bool) or not isinstance(glob, (int, float)) or not (0.0 < glob <= 1.0):
+        raise ValueError(f"{path}: \"global\" must be a number in (0, 1]")
+    per_class = doc["per_class"]
+    if not isinstance(per_class, list) or len(per_class) != NUM_EVENT_CLASSES or \
+            any(isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 < v <= 1.0) for v in per_class):
+        raise ValueError(f"{path}: \"per_class\" must be {NUM_EVENT_CLASSES} numbers in (0, 1]")
+    doc = dict(doc, per_class=class_threshold_vector(per_class))
+    doc["global"] = _f32(glob)
+    run = {"max_peaks": None if max_peaks is None else int(max_peaks),
+           "tta_patterns": None if tta_patterns is None else [int(p) for p in tta_patterns],
+           "refine": None if refine is None else bool(refine)}
+    for key, value in run.items():
+        if value is not None and doc[key] != value:
+            warnings.warn(f"{path}: thresholds were found with {key} = {doc[key]}, this run uses {value}; the best "
+                          f"operating point moves with it", UserWarning, stacklevel=2)
+    return doc
+
+
+def sweep_setting(sweep) -> tuple:
+    """``sweep`` as evaluate_logits takes it -> thresholds; None reads Config.SELD_SWEEP_THRESHOLDS."""
+    from config import Config
+    return parse_sweep(getattr(Config, "SELD_SWEEP_THRESHOLDS", ()) if sweep is None else sweep)
+
+
+def class_thresholds_setting(class_thresholds, max_peaks=None, tta_patterns=None, refine=None):
+    """``class_thresholds`` as evaluate_logits takes it -> 13 fp32 thresholds or None (off).  None reads
+    Config.SELD_CLASS_THRESHOLDS; a str or Path is a thresholds file (``load_thresholds``, which warns when the file's
+    settings are not the run's), else 13 numbers."""
+    from config import Config
+    if class_thresholds is None:
+        class_thresholds = getattr(Config, "SELD_CLASS_THRESHOLDS", None)
+    if class_thresholds is None:
+        return None
+    if isinstance(class_thresholds, (str, Path)):
+        return load_thresholds(class_thresholds, max_peaks, tta_patterns, refine)["per_class"]
+    return class_threshold_vector(class_thresholds)
 
 
 # ------------------------------------------------------------------------------------------------------ events
@@ -654,7 +953,8 @@ def segment_names(dataset):
 # ------------------------------------------------------------------------------------------------------ entry point
 
 def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_threshold_deg=None, events_dir=None,
-                    names=None, patterns=None, track=None, refine=None) -> dict:
+                    names=None, patterns=None, track=None, refine=None, sweep=None, class_thresholds=None,
+                    thresholds_out=None) -> dict:
     """Decode + score for any iterator of logit batches [B, 250, 648, 14] that covers ``dataset``'s windows in order.
     ``dataset``: an SELDDataset (``segments``, ``metadata_rows``, ``total_frames``, ``I``, ``J``, ``device``).  Defaults
     come from Config (SELD_THRESHOLD, SELD_MAX_PEAKS, SELD_DOA_THRESHOLD_DEG).  Returns F20, ER20, LE_CD, LR_CD, TP, FP,
@@ -672,32 +972,79 @@ def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_thresh
     ``grid_decode_refine``, scores the detections' refined directions (seld_doa_match_dirs) and writes their nearest
     integer degrees to the CSVs in place of the cell centres.  With ``track`` the linking itself stays on cells; a
     surviving emission takes the refined direction of the detection it is, a filled one its cell centre
-    (``track_dirs``).  The result's "refine" says which."""
+    (``track_dirs``).  The result's "refine" says which.
+    ``sweep``: a threshold sweep.  None reads Config.SELD_SWEEP_THRESHOLDS (() = off); else a
+    sequence of thresholds or a spelling ``parse_sweep`` takes ("0.05:0.95:0.05").  The timeline is decoded ONCE, at the
+    lowest of the swept thresholds and ``threshold``; the main result is still the one at ``threshold``
+    (``apply_thresholds``) and gains "sweep": score's keys with lists over the thresholds, "thresholds", "precision",
+    "recall" and "best" (``sweep``) -- row t is what evaluate_logits(threshold=t) returns.  With ``track`` the link
+    depends on the threshold, so each row is cut, linked and matched in turn.
+    ``class_thresholds``: one detection threshold per class in place of ``threshold`` (giving both raises ValueError).
+    None reads Config.SELD_CLASS_THRESHOLDS; else 13 numbers or the path of a thresholds file.  The timeline is decoded at
+    their minimum and cut per class before tracking, matching and the CSVs; the result carries "class_thresholds".
+    ``thresholds_out``: with a sweep, write its best global / per-class thresholds, the settings and the swept grid to
+    this file (``write_thresholds``; None reads Config.SELD_THRESHOLDS_OUT), listed under "thresholds_file"."""
     from config import Config
     tracking = track_settings(track)
     refine = refine_setting(refine)
     patterns = tuple(int(p) for p in patterns) if patterns is not None else ()
-    threshold = Config.SELD_THRESHOLD if threshold is None else threshold
     max_peaks = Config.SELD_MAX_PEAKS if max_peaks is None else max_peaks
+    swept = sweep_setting(sweep)
+    if thresholds_out is not None and not swept:
+        raise ValueError("thresholds_out needs a sweep (sweep=... or Config.SELD_SWEEP_THRESHOLDS)")
+    if thresholds_out is None and swept:
+        thresholds_out = getattr(Config, "SELD_THRESHOLDS_OUT", None)
+    if class_thresholds is not None and threshold is not None:
+        raise ValueError("give either threshold or class_thresholds, not both")
+    # (an explicit threshold wins over Config.SELD_CLASS_THRESHOLDS)
+    per_class = class_thresholds_setting(class_thresholds, max_peaks, patterns, refine) if threshold is None else None
+    threshold = Config.SELD_THRESHOLD if threshold is None else threshold
+    # the cut thresholds, fp32 as the decode compares them; None: the decode itself runs at ``threshold``, as ever
+    cut = per_class if per_class is not None else [_f32(threshold)] * NUM_EVENT_CLASSES if swept else None
+    decode_threshold = threshold if cut is None else min(list(swept) + cut)
     doa_threshold_deg = Config.SELD_DOA_THRESHOLD_DEG if doa_threshold_deg is None else doa_threshold_deg
     if (dataset.I, dataset.J) != (GRID_I, GRID_J):
         raise NotImplementedError(f"the decode kernel is built for the {GRID_I} x {GRID_J} grid, got "
                                   f"{dataset.I} x {dataset.J}")
     table = meta_frame_table(dataset.segments, dataset.total_frames)
-    decoded = decode(batches, table, threshold, max_peaks, device=dataset.device, patterns=patterns, refine=refine)
-    det_cell, det_count, det_dir = decoded[0], decoded[2], decoded[4] if refine else None
-    ids = linked = None
-    if tracking is not None:
-        linked = _track_link(det_cell, det_count, table, tracking["gate_deg"], tracking["max_gap"], tracking["min_len"],
-                             dataset.I, dataset.J)
-        if refine:
-            det_dir = track_dirs(linked[0], linked[2], det_cell, det_count, det_dir, dataset.I, dataset.J)
-        det_cell, ids, det_count = linked[:3]
-        tracking = {**tracking, **track_summary(linked[2], linked[3], linked[4])}
-    result = match_and_score(det_cell, det_count, table, dataset.metadata_rows, doa_threshold_deg, dataset.I, dataset.J,
-                             det_dir=det_dir, refine=refine)
+    decoded = decode(batches, table, decode_threshold, max_peaks, device=dataset.device, patterns=patterns, refine=refine)
+    low = (decoded[0], decoded[1], decoded[2]) + ((decoded[4],) if refine else ())      # as decoded, at decode_threshold
+    settings = tracking
+    refs = device_references(table, dataset.metadata_rows, low[0].device) if swept else None
+
+    def link_and_score(dets):
+        """Detections (cell, score, count[, dir]) -> (record, cell, ids, count, dir, linked, tracking)."""
+        cell, count, dirs = dets[0], dets[2], dets[3] if refine else None
+        ids = linked = None
+        summary = settings
+        if settings is not None:
+            linked = _track_link(cell, count, table, settings["gate_deg"], settings["max_gap"], settings["min_len"],
+                                 dataset.I, dataset.J)
+            if refine:
+                dirs = track_dirs(linked[0], linked[2], cell, count, dirs, dataset.I, dataset.J)
+            cell, ids, count = linked[:3]
+            summary = {**settings, **track_summary(linked[2], linked[3], linked[4])}
+        record = match_and_score(cell, count, table, dataset.metadata_rows, doa_threshold_deg, dataset.I, dataset.J,
+                                 det_dir=dirs, refine=refine, refs=refs)
+        return record, cell, ids, count, dirs, linked, summary
+
+    result, det_cell, ids, det_count, det_dir, linked, tracking = link_and_score(
+        low if cut is None else apply_thresholds(low[0], low[1], low[2], cut, low[3] if refine else None))
     result.update(threshold=float(threshold), max_peaks=int(max_peaks), doa_threshold_deg=float(doa_threshold_deg),
                   tta_patterns=list(patterns), tracking=tracking, refine=refine)
+    if per_class is not None:
+        result["class_thresholds"] = list(per_class)
+    if swept:
+        if settings is None:
+            result["sweep"] = _sweep(low[0], low[1], low[2], table, dataset.metadata_rows, swept, doa_threshold_deg,
+                                     dataset.I, dataset.J, det_dir=low[3] if refine else None, refs=refs)
+        else:
+            rows = [link_and_score(apply_thresholds(low[0], low[1], low[2], [t] * NUM_EVENT_CLASSES,
+                                                    low[3] if refine else None))[0] for t in swept]
+            result["sweep"] = _sweep_result(swept, rows)
+        if thresholds_out is not None:
+            result["thresholds_file"] = str(write_thresholds(thresholds_out, result["sweep"], max_peaks, doa_threshold_deg,
+                                                             patterns, refine, settings))
     if events_dir is not None:
         names = segment_names(dataset) if names is None else list(names)
         cells, counts = det_cell.cpu().numpy(), det_count.cpu().numpy()

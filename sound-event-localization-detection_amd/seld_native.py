@@ -148,7 +148,11 @@ def _declare(lib):
     lib.seld_grid_decode_refine.argtypes = [_ptr, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _pi32, _int,
                                             ctypes.c_float, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]
     lib.seld_doa_match_dirs.argtypes = [_ptr, _ptr, _int, _ptr, _ptr, _i64, ctypes.c_double, _ptr, _ptr, _ptr]
-    lib.seld_resample_plan.argtypes = [_i64, _i64, _pi32, _pi32, _pi32, _pi32]
+    lib.seld_doa_match_prefix.argtypes = [_ptr, _ptr, _ptr, _int, _ptr, _ptr, _i64, _int, _int, ctypes.c_double, _ptr, _ptr,
+                                          _ptr]
+    lib.seld_sweep_score.argtypes = [_ptr, _ptr, _ptr, _ptr, _int, _ptr, _i64, ctypes.POINTER(ctypes.c_float), _int, _i64,
+                                     _ptr, _ptr, _ptr, _ptr]
+    lib.seld_resample_plan.argtypes =[_i64, _i64, _pi32, _pi32, _pi32, _pi32]
     lib.seld_resample_table_host.argtypes = [_i64, _i64, _ptr, _ptr]
     for fn in (lib.seld_resample_f32, lib.seld_resample_i16):
         fn.argtypes = [_ptr, _i64, _i64, _i64, _ptr, _int, _int, _int, _int, _ptr, _i64, _ptr]

@@ -1108,7 +1108,8 @@ def _tta_logits(model, dataset, batch_size, device, patterns):
 
 
 def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, threshold=None, max_peaks=None,
-                  doa_threshold_deg=None, events_dir=None, use_ema=None, tta=None, track=None, refine=None):
+                  doa_threshold_deg=None, events_dir=None, use_ema=None, tta=None, track=None, refine=None, sweep=None,
+                  class_thresholds=None, thresholds_out=None):
     """Evaluate a checkpoint on what it detects: the windows of ``test_loader.dataset`` (an SELDDataset) run through the
     model in timeline order, the overlapping grid maps are decoded into DOA events on the GPU and scored against the
     dataset's CSV rows.  Returns F20, ER20, LE_CD, LR_CD, TP, FP, FN, N, per_class (seld_eval.evaluate_logits); with
@@ -1120,7 +1121,12 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
     ``track``: track linking of the detections (seld_eval.evaluate_logits: None reads Config.SELD_TRACK, True or a dict
     of gate_deg / max_gap / min_len switches it on); the result's "tracking" holds its counts.
     ``refine``: sub-cell DOA refinement of the detections (seld_eval.evaluate_logits: None reads Config.SELD_REFINE;
-    DESIGN.md section 15); the result's "refine" says whether the scored and written directions are refined."""
+    DESIGN.md section 15); the result's "refine" says whether the scored and written directions are refined.
+    ``sweep`` / ``class_thresholds`` / ``thresholds_out``: the threshold sweep, per-class detection thresholds and the
+    thresholds file of seld_eval.evaluate_logits (None reads Config.SELD_SWEEP_THRESHOLDS /
+    SELD_CLASS_THRESHOLDS / SELD_THRESHOLDS_OUT).  ``sweep`` also takes the spelling "0.05:0.95:0.05" (start:stop:step,
+    inclusive) or a comma list; the one forward pass and the one decode serve every threshold, the result's "sweep"
+    holds a record per threshold and the best global / per-class operating points."""
     import seld_eval
     test_dataset = test_loader.dataset
     patterns = seld_augment.tta_patterns(getattr(config, "SELD_TTA_PATTERNS", ()) if tta is None else tta)
@@ -1146,8 +1152,15 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
     results = seld_eval.evaluate_logits(timeline_logits(model, test_dataset, batch_size, device, patterns=patterns),
                                         test_dataset, threshold=threshold, max_peaks=max_peaks,
                                         doa_threshold_deg=doa_threshold_deg, events_dir=events_dir, patterns=patterns,
-                                        track=track, refine=refine)
+                                        track=track, refine=refine, sweep=sweep, class_thresholds=class_thresholds,
+                                        thresholds_out=thresholds_out)
     results["checkpoint_epoch"] = checkpoint["epoch"]
+    if results.get("sweep"):
+        sw = results["sweep"]
+        for t, f, e in zip(sw["thresholds"], sw["F20"], sw["ER20"]):
+            logger.info(f"threshold {t:.4g}: F20 {f:.4f}  ER20 {e:.4f}")
+        logger.info(f"best threshold {sw['best']['global']}, per class {sw['best']['per_class']}"
+                    + (f" -> {results['thresholds_file']}" if results.get("thresholds_file") else ""))
     if results.get("tracking"):
         tr = results["tracking"]
         logger.info(f"track linking (gate {tr['gate_deg']:g} deg, gap {tr['max_gap']}, min length {tr['min_len']}): "
