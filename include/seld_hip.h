@@ -628,6 +628,61 @@ int seld_sweep_score(const int32_t* ptp, const double* pcost, const float* det_s
                      const int32_t* ref_offsets, int64_t nq, const float* thresholds, int T, int64_t chunk,
                      int64_t* counts, int64_t* sdi, double* cost, void* stream);
 
+/* ---- segment-based, class-macro metrics with jackknife replicates (csrc/seld_segment.hip) ---------
+ * No reference counterpart; the definitions are DESIGN.md section 18.1 (after the DCASE 2022/23 segment-based metric).
+ *
+ * seld_doa_assign: the minimum-cost assignment of seld_doa_match (det_dir NULL: det_cell, I, J name the detections) or
+ * seld_doa_match_dirs (det_dir f32 [nq][13][K][2], 8-byte aligned, in place of det_cell, I, J) itself, not only its cost.
+ * Rows are the smaller side (the references when R <= P), k = rows; the dp runs over the sets of used columns in ascending
+ * mask order, the row of a mask being popcount - 1: dp[mask] = the minimum over its set bits b, ascending, strict <, of
+ * dp[mask ^ bit b] + d[row][b], choice[mask] = the b that set it; the final mask is the first of popcount k whose dp is
+ * strictly smallest; the pairs are read back through choice.  The distances and additions are seld_doa_match's in its
+ * order, so the assigned distances, added in row order, are its cost bit for bit.
+ *   pair_dist f64 [nq][13][8]: slot r = the distance in degrees of reference r (its position in the CSR list of (q, c)) to
+ *   the detection assigned to it; NaN when reference r is unassigned or r >= R, and throughout for an entry seld_doa_match
+ *   refuses (more than 8 references, a count outside 0..K).
+ * thr_deg does not enter the assignment (it is checked, >= 0, and otherwise unused: the argument list is
+ * seld_doa_match_prefix's).  One thread per (q, c); no allocation, no synchronise.  -1, launching nothing, for K outside
+ * 1..8, bad extents or a null pointer. */
+int seld_doa_assign(const int32_t* det_cell, const float* det_dir, const int32_t* det_count, int K,
+                    const int32_t* ref_offsets, const int32_t* ref_dirs, int64_t nq, int I, int J, double thr_deg,
+                    double* pair_dist, void* stream);
+
+/* seld_segment_score: the counts of every (1 s block, class) from pair_dist, then every recording's blocks folded.
+ * Recording s holds meta-frames seg_offsets[s] .. seg_offsets[s+1] - 1 (int64 [S+1], device); its block x covers its
+ * meta-frames 10 x .. min(10 x + 10, M_s) - 1 and is row block_offsets[s] + x (int64 [S+1], device: the exclusive prefix
+ * sum of ceil(M_s / 10); NB = block_offsets[S]).  Per (block, class), over the block's frames in ascending order with
+ * R_m = the references and P_m = det_count clamped to 0..K:  nref = max R_m, npred = max P_m;  in a frame with R_m > 0 and
+ * P_m > 0 every non-NaN slot r adds its distance to sum_r and 1 to cnt_r;  a slot with cnt_r > 0, in ascending r:
+ * avg = sum_r / cnt_r, de += avg, DE_TP += 1, TP += 1 when avg <= thr_deg else FPs += 1.  Then
+ *   nref > 0 and npred > 0, some slot matched:  FP = max(0, npred - nref), FN = max(0, nref - npred)
+ *   nref > 0 and npred > 0, no slot matched:    FN = nref, FP = npred
+ *   npred = 0: FN = nref;  nref = 0: FP = npred;  DE_FN = FN throughout.
+ *   seg_stats  int32 [NB][13][8]  = (nref, npred, TP, FPs, FP, FN, DE_TP, DE_FN),  seg_de f64 [NB][13] = de
+ *   rec_counts int64 [S][13][11]  = the eight summed over the recording's blocks, then S_c, D_c, I_c = the sums of
+ *                                   min(locFP, locFN), max(0, locFN - locFP), max(0, locFP - locFN) with
+ *                                   locFP = FPs + FP and locFN = FN of the (block, class)
+ *   rec_sdi    int64 [S][3]       = the same three terms with locFP / locFN summed over the block's 13 classes first
+ *   rec_de     f64   [S][13]      = seg_de summed over the recording's blocks in ascending order
+ * Two launches, one workgroup per recording each; plain stores in a fixed order: a repeated run is bit-identical.  No
+ * allocation, no synchronise.  -1, launching nothing, for K outside 1..8, S < 0, thr_deg < 0 or a null pointer. */
+int seld_segment_score(const double* pair_dist, const int32_t* det_count, int K, const int32_t* ref_offsets,
+                       const int64_t* seg_offsets, const int64_t* block_offsets, int64_t S, double thr_deg,
+                       int32_t* seg_stats, double* seg_de, int64_t* rec_counts, int64_t* rec_sdi, double* rec_de,
+                       void* stream);
+
+/* seld_jackknife_score: the metrics of every leave-one-recording-out replicate.  Replicate j = 0..S-1 sums rec_counts,
+ * rec_sdi and rec_de over every recording but j, replicate S over all of them; recordings in ascending order, per class.
+ * From a set of counts:  F = TP / (TP + FPs + (FP + FN) / 2),  ER = (S + D + I) / Nref,  LE = de / DE_TP (180 when
+ * DE_TP = 0),  LR = DE_TP / (DE_TP + DE_FN),  SELD = (ER + (1 - F) + LE / 180 + (1 - LR)) / 4;  an empty denominator is NaN.
+ *   out f64 [S+1][2][5]: row 0 micro = the figures of the counts summed over the classes (de: the class sums added in
+ *   ascending class order) with rec_sdi's S, D, I; row 1 macro = each figure's plain mean, in ascending class order, over
+ *   the classes with Nref > 0 in that replicate, from the class's own counts and S_c, D_c, I_c (NaN when there is none).
+ *   out_class f64 [13][5]: the per-class figures of replicate S.
+ * One lane per replicate; no allocation, no synchronise.  -1, launching nothing, for S < 1 or a null pointer. */
+int seld_jackknife_score(const int64_t* rec_counts, const int64_t* rec_sdi, const double* rec_de, int64_t S, double* out,
+                         double* out_class, void* stream);
+
 /* ---- sample-rate conversion in front of the 24 kHz feature kernels (csrc/resample.hip) ---------
  * No reference counterpart (dataset.py:27-58 hands the file's rate to MelSpectrogram).  A windowed-sinc polyphase FIR with
  * zero delay and zero extension: with g = gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g,

@@ -192,6 +192,10 @@ class Config:
     SELD_CLASS_THRESHOLDS = None  # 13 detection thresholds, one per class, or the path of a thresholds.json that a sweep
                                 # wrote (thresholds_out); takes the place of SELD_THRESHOLD.  None = one threshold for all
     SELD_THRESHOLDS_OUT = None  # evaluate_seld writes the swept grid and its best global / per-class thresholds to this file
+    # Segment-based, class-macro metrics (seld_eval.segment_metrics, csrc/seld_segment.hip)
+    SELD_SEGMENT_METRICS = False  # evaluate_seld also reports F / ER / LE / LR and the SELD score per 1 s block and class,
+                                # micro- and macro-averaged: the figures published SELD results are given in
+    SELD_JACKKNIFE = False      # with SELD_SEGMENT_METRICS: 95 % confidence intervals from a jackknife over the recordings
     # Sample-rate conversion of the input (seld_native.resample, csrc/resample.hip)
     RESAMPLE_INPUT = False      # SELDDataset / audio_to_mel_spectrogram / infer.py convert recordings whose rate is not SR (48 kHz,
                                 # 44.1 kHz, ...) to SR on the GPU before the feature kernels; off: such a recording raises

@@ -29,12 +29,20 @@ evaluate_logits decode once at the lowest threshold involved -- the detections a
   seld_doa_match_prefix    seld_doa_match / seld_doa_match_dirs for every prefix of every (meta-frame, class) at once
   seld_sweep_score         the sums behind the metrics for up to 64 thresholds from those tables, one lane per threshold
 
+Segment-based, class-macro metrics with jackknife intervals (csrc/seld_segment.hip): ``segment`` /
+``jackknife`` on evaluate_logits add the figures published SELD results are given in, from
+
+  seld_doa_assign          the assignment behind seld_doa_match's cost: per reference the distance to its detection
+  seld_segment_score       the counts of every (1 s block, class), folded per recording
+  seld_jackknife_score     micro and macro F / ER / LE / LR / SELD of every leave-one-recording-out replicate
+
 The host side here builds the tables (meta-frames, reference CSR), drives the decode batch by batch as the windows are
 computed, reduces the match counts on the device and writes event CSVs.  There is no CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 from pathlib import Path
 
@@ -892,6 +900,233 @@ def class_thresholds_setting(class_thresholds, max_peaks=None, tta_patterns=None
     return class_threshold_vector(class_thresholds)
 
 
+# ------------------------------------------------------------------------------------------------------ segment metrics
+
+BLOCK_FRAMES = 10          # meta-frames per block of the segment-based metrics: 1 s
+SEG_STATS = ("Nref", "Npred", "TP", "FPs", "FP", "FN", "DE_TP", "DE_FN")      # seg_stats / the first eight of rec_counts
+FIGURES = ("F", "ER", "LE", "LR", "SELD")
+
+
+def block_table(table: MetaFrameTable) -> np.ndarray:
+    """block_offsets int64 [S + 1] of a timeline: recording s has ceil(M_s / 10) blocks of 10 meta-frames (the last may be
+    shorter), numbered block_offsets[s] .. block_offsets[s + 1] - 1."""
+    frames = np.diff(table.seg_offsets)
+    return np.concatenate([[0], np.cumsum((frames + BLOCK_FRAMES - 1) // BLOCK_FRAMES)]).astype(np.int64)
+
+
+def doa_assign(det_cell: torch.Tensor, det_count: torch.Tensor, ref_offsets: torch.Tensor, ref_dirs: torch.Tensor,
+               doa_threshold_deg: float, I: int = GRID_I, J: int = GRID_J, det_dir: torch.Tensor | None = None):
+    """seld_doa_assign: pair_dist f64 [Q, 13, 8]; slot r of (q, c) is the distance of its reference r to the detection the
+    minimum-cost assignment of ``doa_match`` (``doa_match_dirs`` given ``det_dir`` f32 [Q, 13, K, 2]) gives it, NaN when
+    the reference is unassigned, absent or the entry refused."""
+    device = det_count.device
+    if not det_count.is_cuda:
+        raise SeldNativeError("doa_assign: detections must live on the GPU (no CPU fallback)")
+    q = int(det_count.shape[0])
+    if det_dir is not None:
+        if det_dir.dim() != 4 or det_dir.shape[1] != NUM_EVENT_CLASSES or det_dir.shape[3] != 2 or \
+                tuple(det_count.shape) != tuple(det_dir.shape[:2]):
+            raise ValueError("doa_assign: det_dir must be [Q, 13, K, 2] and det_count [Q, 13]")
+        det_dir, k = det_dir.to(torch.float32).contiguous(), int(det_dir.shape[2])
+        det_cell = None
+    else:
+        det_cell, k = det_cell.to(torch.int32).contiguous(), int(det_cell.shape[-1])
+    if ref_offsets.numel() != q * NUM_EVENT_CLASSES + 1:
+        raise ValueError("doa_assign: ref_offsets must have Q * 13 + 1 entries")
+    index = ensure_init(device)
+    pair_dist = torch.empty((q, NUM_EVENT_CLASSES, MAX_REFS), dtype=torch.float64, device=device)
+    dirs = ref_dirs if ref_dirs.numel() else torch.zeros((1, 2), dtype=torch.int32, device=device)
+    det_count = det_count.to(torch.int32).contiguous()
+    ref_offsets, dirs = ref_offsets.to(torch.int32).contiguous(), dirs.to(torch.int32).contiguous()
+    with _device_guard(index):
+        check(load_library().seld_doa_assign(_p(det_cell), _p(det_dir), _p(det_count), k, _p(ref_offsets), _p(dirs), q,
+                                             int(I), int(J), float(doa_threshold_deg) + DOA_MARGIN_DEG, _p(pair_dist),
+                                             _stream_ptr(device)), "seld_doa_assign")
+    return pair_dist
+
+
+def segment_score(pair_dist: torch.Tensor, det_count: torch.Tensor, max_peaks: int, ref_offsets: torch.Tensor,
+                  table: MetaFrameTable, doa_threshold_deg: float):
+    """seld_segment_score over the timeline of ``table``: (seg_stats int32 [NB, 13, 8] = SEG_STATS per (block, class),
+    seg_de f64 [NB, 13], rec_counts int64 [S, 13, 11] = SEG_STATS and S_c, D_c, I_c per (recording, class), rec_sdi int64
+    [S, 3], rec_de f64 [S, 13]).  ``max_peaks``: the K the counts are clamped to.  A slot counts as a true positive when its
+    average distance over the block is <= doa_threshold_deg + DOA_MARGIN_DEG."""
+    device = pair_dist.device
+    if not pair_dist.is_cuda:
+        raise SeldNativeError("segment_score: the assignment must live on the GPU (no CPU fallback)")
+    q = len(table)
+    if tuple(pair_dist.shape) != (q, NUM_EVENT_CLASSES, MAX_REFS) or tuple(det_count.shape) != (q, NUM_EVENT_CLASSES):
+        raise ValueError(f"segment_score: expected pair_dist [{q}, 13, 8] and det_count [{q}, 13] for the timeline")
+    if ref_offsets.numel() != q * NUM_EVENT_CLASSES + 1:
+        raise ValueError("segment_score: ref_offsets must have Q * 13 + 1 entries")
+    index = ensure_init(device)
+    blocks = block_table(table)
+    n_seg, n_blocks = len(blocks) - 1, int(blocks[-1])
+    key = ("blocks", str(device))
+    if key not in table._device:
+        table._device[key] = torch.from_numpy(blocks).to(device)
+    seg_offsets, block_offsets = table.device_segments(device)[0], table._device[key]
+    seg_stats = torch.empty((n_blocks, NUM_EVENT_CLASSES, len(SEG_STATS)), dtype=torch.int32, device=device)
+    seg_de = torch.empty((n_blocks, NUM_EVENT_CLASSES), dtype=torch.float64, device=device)
+    rec_counts = torch.empty((n_seg, NUM_EVENT_CLASSES, len(SEG_STATS) + 3), dtype=torch.int64, device=device)
+    rec_sdi = torch.empty((n_seg, 3), dtype=torch.int64, device=device)
+    rec_de = torch.empty((n_seg, NUM_EVENT_CLASSES), dtype=torch.float64, device=device)
+    pair_dist, det_count = pair_dist.to(torch.float64).contiguous(), det_count.to(torch.int32).contiguous()
+    ref_offsets = ref_offsets.to(torch.int32).contiguous()
+    with _device_guard(index):
+        check(load_library().seld_segment_score(_p(pair_dist), _p(det_count), int(max_peaks), _p(ref_offsets),
+                                                _p(seg_offsets), _p(block_offsets), n_seg,
+                                                float(doa_threshold_deg) + DOA_MARGIN_DEG, _p(seg_stats), _p(seg_de),
+                                                _p(rec_counts), _p(rec_sdi), _p(rec_de), _stream_ptr(device)),
+              "seld_segment_score")
+    return seg_stats, seg_de, rec_counts, rec_sdi, rec_de
+
+
+def jackknife_score(rec_counts: torch.Tensor, rec_sdi: torch.Tensor, rec_de: torch.Tensor):
+    """seld_jackknife_score: (out f64 [S + 1, 2, 5] = (micro, macro) x FIGURES, row j the metrics of every recording but
+    j and row S those of all; out_class f64 [13, 5], the per-class figures of all recordings)."""
+    device = rec_counts.device
+    if not rec_counts.is_cuda:
+        raise SeldNativeError("jackknife_score: the counts must live on the GPU (no CPU fallback)")
+    n_seg = int(rec_counts.shape[0])
+    if tuple(rec_counts.shape) != (n_seg, NUM_EVENT_CLASSES, len(SEG_STATS) + 3) or tuple(rec_sdi.shape) != (n_seg, 3) or \
+            tuple(rec_de.shape) != (n_seg, NUM_EVENT_CLASSES):
+        raise ValueError("jackknife_score: expected rec_counts [S, 13, 11], rec_sdi [S, 3], rec_de [S, 13]")
+    index = ensure_init(device)
+    out = torch.empty((n_seg + 1, 2, len(FIGURES)), dtype=torch.float64, device=device)
+    out_class = torch.empty((NUM_EVENT_CLASSES, len(FIGURES)), dtype=torch.float64, device=device)
+    rec_counts, rec_sdi = rec_counts.to(torch.int64).contiguous(), rec_sdi.to(torch.int64).contiguous()
+    rec_de = rec_de.to(torch.float64).contiguous()
+    with _device_guard(index):
+        check(load_library().seld_jackknife_score(_p(rec_counts), _p(rec_sdi), _p(rec_de), n_seg, _p(out), _p(out_class),
+                                                  _stream_ptr(device)), "seld_jackknife_score")
+    return out, out_class
+
+
+def _betacf(a: float, b: float, x: float) -> float:
+    """The continued fraction of the regularised incomplete beta function (modified Lentz)."""
+    tiny = 1e-300
+    qab, qap, qam = a + b, a + 1.0, a - 1.0
+    c, d = 1.0, 1.0 - qab * x / qap
+    d = 1.0 / (d if abs(d) > tiny else tiny)
+    h = d
+    for m in range(1, 10000):
+        m2 = 2 * m
+        for num in (m * (b - m) * x / ((qam + m2) * (a + m2)), -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2))):
+            d = 1.0 + num * d
+            d = 1.0 / (d if abs(d) > tiny else tiny)
+            c = 1.0 + num / c
+            c = c if abs(c) > tiny else tiny
+            h *= d * c
+        if abs(d * c - 1.0) < 1e-16:
+            break
+    return h
+
+
+def _betainc(a: float, b: float, x: float) -> float:
+    """The regularised incomplete beta function I_x(a, b)."""
+    if x <= 0.0:
+        return 0.0
+    if x >= 1.0:
+        return 1.0
+    front = math.exp(math.lgamma(a + b) - math.lgamma(a) - math.lgamma(b) + a * math.log(x) + b * math.log1p(-x))
+    if x < (a + 1.0) / (a + b + 2.0):
+        return front * _betacf(a, b, x) / a
+    return 1.0 - front * _betacf(b, a, 1.0 - x) / b
+
+
+@functools.lru_cache(maxsize=None)
+def student_t_975(df) -> float:
+    """The 0.975 quantile of Student's t with ``df`` >= 1 degrees of freedom, in plain Python: the distribution function
+    through the incomplete beta function, inverted by bisection (about a millisecond; kept per ``df``)."""
+    df = float(df)
+    if not df >= 1.0:
+        raise ValueError(f"student_t_975: df must be at least 1, got {df}")
+    if df == 1.0:
+        return math.tan(math.pi * 0.475)
+    if df == 2.0:
+        return 0.95 * math.sqrt(2.0 / (1.0 - 0.95 * 0.95))
+    lo, hi = 1.9, 13.0                           # the quantile falls from 12.71 (df = 1) to 1.96 (df -> inf)
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid in (lo, hi):
+            break
+        upper_tail = 0.5 * _betainc(0.5 * df, 0.5, df / (df + mid * mid))
+        lo, hi = (mid, hi) if upper_tail > 0.025 else (lo, mid)
+    return 0.5 * (lo + hi)
+
+
+def jackknife(values) -> dict:
+    """The delete-one jackknife of one figure, float64.  ``values``: the n replicates theta_(i),
+    then theta-hat of all recordings last (a row of ``jackknife_score``'s output).  nan replicates are dropped and n
+    reduced with them.  Returns {estimate, bias, se, low, high, n}: bias = (n - 1)(mean - theta-hat), estimate =
+    theta-hat - bias, se = sqrt((n - 1) / n * sum (theta_(i) - mean)^2), the interval estimate -+ t se with t the 0.975
+    quantile of Student's t with n - 1 degrees of freedom.  Fewer than 2 usable replicates: estimate = theta-hat, the
+    rest nan."""
+    values = np.asarray(values, dtype=np.float64).reshape(-1)
+    if values.size < 1:
+        raise ValueError("jackknife: expected the replicates and the all-recordings figure")
+    full, rep = float(values[-1]), values[:-1]
+    rep = rep[~np.isnan(rep)]
+    n = int(rep.size)
+    if n < 2:
+        return {"estimate": full, "bias": math.nan, "se": math.nan, "low": math.nan, "high": math.nan, "n": n}
+    mean = float(rep.mean())
+    bias = (n - 1) * (mean - full)
+    se = math.sqrt((n - 1) / n * float(((rep - mean) ** 2).sum()))
+    estimate, t = full - bias, student_t_975(n - 1)
+    return {"estimate": estimate, "bias": bias, "se": se, "low": estimate - t * se, "high": estimate + t * se, "n": n}
+
+
+_jackknife = jackknife     # (segment_metrics and evaluate_logits have a parameter of that name)
+
+
+def segment_setting(segment, jackknife) -> tuple:
+    """``segment`` / ``jackknife`` as evaluate_logits takes them -> (bool, bool); None reads Config.SELD_SEGMENT_METRICS /
+    Config.SELD_JACKKNIFE.  ValueError for the jackknife without the segment metrics."""
+    from config import Config
+    segment = bool(getattr(Config, "SELD_SEGMENT_METRICS", False)) if segment is None else bool(segment)
+    jackknife = bool(getattr(Config, "SELD_JACKKNIFE", False)) if jackknife is None else bool(jackknife)
+    if jackknife and not segment:
+        raise ValueError("jackknife needs the segment metrics (segment=True or Config.SELD_SEGMENT_METRICS)")
+    return segment, jackknife
+
+
+def segment_metrics(det_cell: torch.Tensor, det_count: torch.Tensor, table: MetaFrameTable, metadata_rows,
+                    doa_threshold_deg: float, I: int = GRID_I, J: int = GRID_J, det_dir: torch.Tensor | None = None,
+                    refs=None, jackknife: bool = False) -> dict:
+    """The segment-based metrics of DESIGN.md section 18 for the detections of a timeline: seld_doa_assign,
+    seld_segment_score, seld_jackknife_score, one copy of the small results to the host.  Returns "micro" and "macro"
+    ({F, ER, LE, LR, SELD}), "per_class" (the figures and the counts as lists over the classes), "counts" (SEG_STATS and the
+    micro S, D, I over all recordings), "classes" (those with references, which the macro average runs over), "blocks",
+    "recordings" and "block_seconds"; with ``jackknife`` also "ci": per average and figure ``jackknife``'s record over the
+    recordings.  ``det_dir``: the detections' refined directions, matched in place of the cell centres.  ``refs``: as
+    match_and_score."""
+    n_seg = len(table.seg_offsets) - 1
+    if n_seg < 1:
+        raise ValueError("segment_metrics: the timeline has no recordings")
+    offsets, dirs = device_references(table, metadata_rows, det_count.device) if refs is None else refs
+    k = int(det_dir.shape[2] if det_dir is not None else det_cell.shape[-1])
+    pair_dist = doa_assign(det_cell, det_count, offsets, dirs, doa_threshold_deg, I, J, det_dir=det_dir)
+    seg_stats, _, rec_counts, rec_sdi, rec_de = segment_score(pair_dist, det_count, k, offsets, table, doa_threshold_deg)
+    out, out_class = jackknife_score(rec_counts, rec_sdi, rec_de)
+    out, out_class = out.cpu().numpy(), out_class.cpu().numpy()
+    counts, sdi = rec_counts.sum(0).cpu().numpy(), rec_sdi.sum(0).cpu().numpy()        # [13, 11], [3]
+    names = SEG_STATS + ("S", "D", "I")
+    per_class = {name: [float(v) for v in out_class[:, i]] for i, name in enumerate(FIGURES)}
+    per_class.update({name: [int(v) for v in counts[:, i]] for i, name in enumerate(names)})
+    totals = {name: int(counts[:, i].sum()) for i, name in enumerate(SEG_STATS)}
+    totals.update(S=int(sdi[0]), D=int(sdi[1]), I=int(sdi[2]))
+    result = {"micro": {name: float(out[-1, 0, i]) for i, name in enumerate(FIGURES)},
+              "macro": {name: float(out[-1, 1, i]) for i, name in enumerate(FIGURES)},
+              "per_class": per_class, "counts": totals, "classes": [c for c in range(NUM_EVENT_CLASSES) if counts[c, 0] > 0],
+              "blocks": int(seg_stats.shape[0]), "recordings": n_seg, "block_seconds": BLOCK_FRAMES * 0.1}
+    if jackknife:
+        result["ci"] = {avg: {name: _jackknife(out[:, a, i]) for i, name in enumerate(FIGURES)}
+                        for a, avg in enumerate(("micro", "macro"))}
+    return result
+
+
 # ------------------------------------------------------------------------------------------------------ events
 
 def events_for_segment(det_cell, det_count, table: MetaFrameTable, segment: int, I: int = GRID_I, J: int = GRID_J,
@@ -954,7 +1189,7 @@ def segment_names(dataset):
 
 def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_threshold_deg=None, events_dir=None,
                     names=None, patterns=None, track=None, refine=None, sweep=None, class_thresholds=None,
-                    thresholds_out=None) -> dict:
+                    thresholds_out=None, segment=None, jackknife=None) -> dict:
     """Decode + score for any iterator of logit batches [B, 250, 648, 14] that covers ``dataset``'s windows in order.
     ``dataset``: an SELDDataset (``segments``, ``metadata_rows``, ``total_frames``, ``I``, ``J``, ``device``).  Defaults
     come from Config (SELD_THRESHOLD, SELD_MAX_PEAKS, SELD_DOA_THRESHOLD_DEG).  Returns F20, ER20, LE_CD, LR_CD, TP, FP,
@@ -983,8 +1218,15 @@ def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_thresh
     None reads Config.SELD_CLASS_THRESHOLDS; else 13 numbers or the path of a thresholds file.  The timeline is decoded at
     their minimum and cut per class before tracking, matching and the CSVs; the result carries "class_thresholds".
     ``thresholds_out``: with a sweep, write its best global / per-class thresholds, the settings and the swept grid to
-    this file (``write_thresholds``; None reads Config.SELD_THRESHOLDS_OUT), listed under "thresholds_file"."""
+    this file (``write_thresholds``; None reads Config.SELD_THRESHOLDS_OUT), listed under "thresholds_file".
+    ``segment``: the segment-based, class-macro metrics of DESIGN.md section 18 (one decision per class and 1 s block,
+    macro-averaged over the classes, one SELD score).  None reads Config.SELD_SEGMENT_METRICS; True adds "segment"
+    (``segment_metrics``) for the detections the main result scores: after the class thresholds and tracking, on the
+    refined directions with ``refine``.  The frame-wise keys are computed as ever; sweep rows do not gain it.
+    ``jackknife``: with ``segment``, 95 % confidence intervals from the delete-one jackknife over the recordings, under
+    "segment"["ci"] (None reads Config.SELD_JACKKNIFE; without ``segment`` ValueError)."""
     from config import Config
+    segment, jackknife = segment_setting(segment, jackknife)
     tracking = track_settings(track)
     refine = refine_setting(refine)
     patterns = tuple(int(p) for p in patterns) if patterns is not None else ()
@@ -1010,7 +1252,7 @@ def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_thresh
     decoded = decode(batches, table, decode_threshold, max_peaks, device=dataset.device, patterns=patterns, refine=refine)
     low = (decoded[0], decoded[1], decoded[2]) + ((decoded[4],) if refine else ())      # as decoded, at decode_threshold
     settings = tracking
-    refs = device_references(table, dataset.metadata_rows, low[0].device) if swept else None
+    refs = device_references(table, dataset.metadata_rows, low[0].device) if swept or segment else None
 
     def link_and_score(dets):
         """Detections (cell, score, count[, dir]) -> (record, cell, ids, count, dir, linked, tracking)."""
@@ -1034,6 +1276,10 @@ def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_thresh
                   tta_patterns=list(patterns), tracking=tracking, refine=refine)
     if per_class is not None:
         result["class_thresholds"] = list(per_class)
+    if segment:
+        result["segment"] = segment_metrics(det_cell, det_count, table, dataset.metadata_rows, doa_threshold_deg,
+                                            dataset.I, dataset.J, det_dir=det_dir if refine else None, refs=refs,
+                                            jackknife=jackknife)
     if swept:
         if settings is None:
             result["sweep"] = _sweep(low[0], low[1], low[2], table, dataset.metadata_rows, swept, doa_threshold_deg,

@@ -152,6 +152,10 @@ def _declare(lib):
                                           _ptr]
     lib.seld_sweep_score.argtypes = [_ptr, _ptr, _ptr, _ptr, _int, _ptr, _i64, ctypes.POINTER(ctypes.c_float), _int, _i64,
                                      _ptr, _ptr, _ptr, _ptr]
+    lib.seld_doa_assign.argtypes = [_ptr, _ptr, _ptr, _int, _ptr, _ptr, _i64, _int, _int, ctypes.c_double, _ptr, _ptr]
+    lib.seld_segment_score.argtypes = [_ptr, _ptr, _int, _ptr, _ptr, _ptr, _i64, ctypes.c_double, _ptr, _ptr, _ptr, _ptr,
+                                       _ptr, _ptr]
+    lib.seld_jackknife_score.argtypes = [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr]
     lib.seld_resample_plan.argtypes =[_i64, _i64, _pi32, _pi32, _pi32, _pi32]
     lib.seld_resample_table_host.argtypes = [_i64, _i64, _ptr, _ptr]
     for fn in (lib.seld_resample_f32, lib.seld_resample_i16):

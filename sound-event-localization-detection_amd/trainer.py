@@ -1109,7 +1109,7 @@ def _tta_logits(model, dataset, batch_size, device, patterns):
 
 def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, threshold=None, max_peaks=None,
                   doa_threshold_deg=None, events_dir=None, use_ema=None, tta=None, track=None, refine=None, sweep=None,
-                  class_thresholds=None, thresholds_out=None):
+                  class_thresholds=None, thresholds_out=None, segment=None, jackknife=None):
     """Evaluate a checkpoint on what it detects: the windows of ``test_loader.dataset`` (an SELDDataset) run through the
     model in timeline order, the overlapping grid maps are decoded into DOA events on the GPU and scored against the
     dataset's CSV rows.  Returns F20, ER20, LE_CD, LR_CD, TP, FP, FN, N, per_class (seld_eval.evaluate_logits); with
@@ -1126,8 +1126,12 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
     thresholds file of seld_eval.evaluate_logits (None reads Config.SELD_SWEEP_THRESHOLDS /
     SELD_CLASS_THRESHOLDS / SELD_THRESHOLDS_OUT).  ``sweep`` also takes the spelling "0.05:0.95:0.05" (start:stop:step,
     inclusive) or a comma list; the one forward pass and the one decode serve every threshold, the result's "sweep"
-    holds a record per threshold and the best global / per-class operating points."""
+    holds a record per threshold and the best global / per-class operating points.
+    ``segment`` / ``jackknife``: the segment-based, class-macro metrics of seld_eval.evaluate_logits (DESIGN.md section 18;
+    None reads Config.SELD_SEGMENT_METRICS / SELD_JACKKNIFE): the result's "segment" holds micro and macro F, ER, LE, LR and
+    the SELD score per 1 s block and class, with ``jackknife`` also their 95 % confidence intervals over the recordings."""
     import seld_eval
+    seld_eval.segment_setting(segment, jackknife)          # (jackknife without segment: raise before the checkpoint is read)
     test_dataset = test_loader.dataset
     patterns = seld_augment.tta_patterns(getattr(config, "SELD_TTA_PATTERNS", ()) if tta is None else tta)
     seld_augment.check_tta(patterns, getattr(config, "FEATURE_SET", "logmel"), getattr(test_dataset, "n_channels", 0))
@@ -1153,7 +1157,7 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
                                         test_dataset, threshold=threshold, max_peaks=max_peaks,
                                         doa_threshold_deg=doa_threshold_deg, events_dir=events_dir, patterns=patterns,
                                         track=track, refine=refine, sweep=sweep, class_thresholds=class_thresholds,
-                                        thresholds_out=thresholds_out)
+                                        thresholds_out=thresholds_out, segment=segment, jackknife=jackknife)
     results["checkpoint_epoch"] = checkpoint["epoch"]
     if results.get("sweep"):
         sw = results["sweep"]
@@ -1168,6 +1172,14 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
     logger.info(f"F20 {results['F20']:.4f}  ER20 {results['ER20']:.4f}  LE_CD {results['LE_CD']:.2f} deg  "
                 f"LR_CD {results['LR_CD']:.4f}  (TP {results['TP']}, FP {results['FP']}, FN {results['FN']}, "
                 f"N {results['N']})")
+    if results.get("segment"):
+        sg = results["segment"]
+        for avg in ("micro", "macro"):
+            m = sg[avg]
+            logger.info(f"segment-based {avg}: F {m['F']:.4f}  ER {m['ER']:.4f}  LE {m['LE']:.2f} deg  LR {m['LR']:.4f}  "
+                        f"SELD {m['SELD']:.4f}"
+                        + (f"  (95 % CI of SELD {sg['ci'][avg]['SELD']['low']:.4f} .. {sg['ci'][avg]['SELD']['high']:.4f}, "
+                           f"{sg['ci'][avg]['SELD']['n']} recordings)" if "ci" in sg else ""))
     return results
 
 

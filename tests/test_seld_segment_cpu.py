@@ -1,0 +1,283 @@
+"""CPU checks of the segment-based, class-macro SELD metrics: the float64 restatement
+(tests/seld_segment_ref.py) against the brute-force matcher and against blocks and counts worked by hand, the host side of
+seld_eval (jackknife, student_t_975, block_table, the switches and their argument errors), the three exports in header,
+binding and library, and the compiler's resource report of the new kernels."""
+import math
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import seld_eval_ref as ref
+import seld_segment_ref as sg
+
+ROOT = Path(__file__).resolve().parent.parent
+CSRC = ROOT / "sound-event-localization-detection_amd" / "csrc"
+NAN = float("nan")
+EXPORTS = ("seld_doa_assign", "seld_segment_score", "seld_jackknife_score")
+
+
+def _slots(*values):
+    return list(values) + [NAN] * (sg.SLOTS - len(values))
+
+
+# ---------------------------------------------------------------------------------------------- per-frame assignment
+
+def test_reference_assignment_totals_equal_the_brute_force_cost():
+    """On random entries of every shape 0..8 x 0..8 the dp's total is the minimum over all injections, the slots are the
+    assigned pairs' distances (each reference and detection used once) and add up to the total in row order."""
+    rng = np.random.default_rng(5)
+    shapes = [(r, p) for r in range(0, 9) for p in range(0, 9)]
+    for r, p in shapes + [shapes[int(i)] for i in rng.integers(0, len(shapes), size=40)]:
+        if max(r, p) > 6 and min(r, p) > 4:
+            continue                                                     # (the brute force enumerates 8!/(8-k)! injections)
+        refs = np.stack([rng.integers(-180, 181, size=r), rng.integers(-90, 91, size=r)], -1)
+        dets = sg.cell_dirs(rng.choice(648, size=p, replace=False))
+        dist = sg.distances(refs, dets)
+        slots, total, pairs = sg.assign(dist)
+        k, _, cost = ref.match_dist(dist)
+        assert len(pairs) == k == min(r, p)
+        assert abs(total - cost) <= 1e-12 * abs(cost)
+        assert len({a for a, _ in pairs}) == k and len({b for _, b in pairs}) == k
+        assert [i for i in range(sg.SLOTS) if not math.isnan(slots[i])] == sorted(a for a, _ in pairs)
+        assert all(slots[a] == dist[a, b] for a, b in pairs)
+        assert sg.row_order_sum(slots, pairs) == total                   # the dp's own additions, in its order
+        rows = [a for a, _ in pairs] if r <= p else [b for _, b in pairs]
+        assert rows == sorted(rows)
+
+
+def test_reference_tie_rule_on_an_exact_tie():
+    """Two identical references, two different detections: both assignments cost the same to the bit; the rule (masks
+    ascending, candidates ascending, strict <) gives reference 0 detection 1.  With the detections as rows (three identical
+    references, two detections) the first detection takes reference 1, the second reference 0."""
+    dist = sg.distances([(10, 0), (10, 0)], [(-15.0, 5.0), (45.0, 15.0)])
+    assert dist[0, 0] == dist[1, 0] and dist[0, 1] == dist[1, 1] and dist[0, 0] != dist[0, 1]
+    slots, total, pairs = sg.assign(dist)
+    # mask 0b11, row 1: bit 0 -> dp[0b10] + d[1][0] = d[0][1] + d[1][0]; bit 1 -> d[0][0] + d[1][1]: equal, bit 0 stays
+    assert pairs == [(0, 1), (1, 0)] and slots[0] == dist[0, 1] and slots[1] == dist[1, 0]
+    dist = sg.distances([(10, 0)] * 3, [(-15.0, 5.0), (45.0, 15.0)])
+    slots, total, pairs = sg.assign(dist)
+    # final mask: the first of popcount 2 = 0b011 (all three cost the same); row 1 (detection 1) takes bit 0
+    assert pairs == [(1, 0), (0, 1)] and math.isnan(slots[2])
+    assert sg.assignment_gap(dist) == 0.0
+
+
+def test_reference_refuses_what_the_matcher_refuses():
+    cell = np.zeros((1, 13, 4), np.int32)
+    count = np.zeros((1, 13), np.int32)
+    count[0, 0], count[0, 1], count[0, 2] = 5, -1, 1
+    refs = [[(0, 0)] for _ in range(13)]
+    refs[2] = [(i, 0) for i in range(9)]
+    out, totals, pairs, _ = sg.pair_dist(refs, sg.cell_dirs(cell), count, 4)
+    assert np.isnan(out[0, :3]).all() and np.isnan(totals[0, :3]).all() and pairs[:3] == [None] * 3
+    assert totals[0, 3] == 0.0 and np.isnan(out[0, 3]).all()             # no detections: nothing assigned
+
+
+# ---------------------------------------------------------------------------------------------- blocks by hand
+
+BLOCKS = {
+    # frames (R_m, P_m, slots)                                             (Nref, Npred, TP, FPs, FP, FN, DE_TP, DE_FN), de
+    "matched, fewer predictions": ([(2, 1, _slots(5.0)), (2, 1, _slots(15.0))], (2, 1, 1, 0, 0, 1, 1, 1), 10.0),
+    "matched beyond the threshold, more predictions": ([(1, 3, _slots(30.0)), (1, 2, _slots(40.0))],
+                                                       (1, 3, 0, 1, 2, 0, 1, 0), 35.0),
+    "both active, never in the same frame": ([(2, 0, _slots()), (0, 3, _slots())], (2, 3, 0, 0, 3, 2, 0, 2), 0.0),
+    "no predictions": ([(1, 0, _slots()), (3, 0, _slots())], (3, 0, 0, 0, 0, 3, 0, 3), 0.0),
+    "no references": ([(0, 2, _slots()), (0, 1, _slots())], (0, 2, 0, 0, 2, 0, 0, 0), 0.0),
+    "average within the threshold although one frame is not": ([(1, 1, _slots(30.0)), (1, 1, _slots(5.0)), (1, 1, _slots(10.0))],
+                                                               (1, 1, 1, 0, 0, 0, 1, 0), 15.0),
+    "two slots, one each side of the threshold": ([(2, 2, _slots(4.0, 50.0)), (2, 2, _slots(NAN, 30.0)), (1, 2, _slots(8.0))],
+                                                  (2, 2, 1, 1, 0, 0, 2, 0), 46.0),
+    "exactly the threshold the host hands over": ([(1, 1, _slots(sg.THR))], (1, 1, 1, 0, 0, 0, 1, 0), sg.THR),
+    "empty": ([(0, 0, _slots())] * 10, (0, 0, 0, 0, 0, 0, 0, 0), 0.0),
+}
+
+
+@pytest.mark.parametrize("name", list(BLOCKS))
+def test_reference_block_counts_by_hand(name):
+    frames, stats, de = BLOCKS[name]
+    got_stats, got_de, _ = sg.block_class(frames)
+    assert got_stats == stats and got_de == de
+
+
+def test_reference_partial_last_block_and_sdi():
+    """M_s = 23: three blocks, the last of 3 meta-frames.  One reference and one detection of class 4 at meta-frame 22
+    only, a lone reference of class 5 in block 0 and two lone detections of class 6 in block 0."""
+    seg_offsets = np.array([0, 23])
+    assert sg.block_offsets(seg_offsets).tolist() == [0, 3] and sg.block_offsets(sg.SEG_OFFSETS).tolist() == [0, 3, 4, 5]
+    pairs = np.full((23, 13, 8), NAN)
+    refs, dets = np.zeros((23, 13), np.int64), np.zeros((23, 13), np.int64)
+    refs[22, 4], dets[22, 4], pairs[22, 4, 0] = 1, 1, 7.0
+    refs[3, 5] = 1
+    dets[4, 6] = 2
+    seg_stats, seg_de, rec_counts, rec_sdi, rec_de, averages = sg.segment_score(pairs, refs, dets, 4, seg_offsets)
+    assert seg_stats.shape == (3, 13, 8) and averages == [7.0]
+    assert seg_stats[2, 4].tolist() == [1, 1, 1, 0, 0, 0, 1, 0] and seg_de[2, 4] == 7.0
+    assert seg_stats[0, 5].tolist() == [1, 0, 0, 0, 0, 1, 0, 1] and seg_stats[0, 6].tolist() == [0, 2, 0, 0, 2, 0, 0, 0]
+    assert not seg_stats[1].any()
+    # block 0: locFN = 1 (class 5), locFP = 2 (class 6): per class D_5 = 1, I_6 = 2; micro S = 1, I = 1
+    assert rec_counts[0, 5, 8:].tolist() == [0, 1, 0] and rec_counts[0, 6, 8:].tolist() == [0, 0, 2]
+    assert rec_sdi[0].tolist() == [1, 0, 1]
+    assert rec_counts[0, 4, :8].tolist() == [1, 1, 1, 0, 0, 0, 1, 0] and rec_de[0, 4] == 7.0
+
+
+# ---------------------------------------------------------------------------------------------- metrics by hand
+
+def _planted_counts():
+    """Two recordings.  Recording 0: class 0 (matched) and class 2 (detections only); recording 1: class 1 (missed only)."""
+    rec_counts = np.zeros((2, 13, 11), np.int64)
+    rec_de = np.zeros((2, 13))
+    rec_counts[0, 0] = [10, 9, 6, 1, 2, 3, 7, 3, 2, 1, 1]
+    rec_de[0, 0] = 70.0
+    rec_counts[0, 2] = [0, 5, 0, 0, 5, 0, 0, 0, 0, 0, 5]
+    rec_counts[1, 1] = [4, 0, 0, 0, 0, 4, 0, 4, 0, 4, 0]
+    rec_sdi = np.array([[3, 0, 3], [0, 2, 0]], np.int64)
+    return rec_counts, rec_sdi, rec_de
+
+
+def test_reference_micro_and_macro_by_hand():
+    rec_counts, rec_sdi, rec_de = _planted_counts()
+    micro, macro, per_class = sg.metrics(rec_counts, rec_sdi, rec_de, [0, 1])
+    f0, er0, le0, lr0 = 6 / (7 + 2.5), 4 / 10, 70.0 / 7, 7 / 10
+    seld0 = (er0 + (1 - f0) + le0 / 180 + (1 - lr0)) / 4
+    assert per_class[0] == pytest.approx([f0, er0, le0, lr0, seld0], rel=1e-15)
+    assert per_class[1] == [0.0, 1.0, 180.0, 0.0, 1.0]                   # nothing localised: LE = 180, SELD = 1
+    assert per_class[2][0] == 0.0 and math.isnan(per_class[2][1]) and per_class[2][2] == 180.0 and math.isnan(per_class[2][3])
+    assert all(math.isnan(v) for v in (per_class[3][0], per_class[3][1], per_class[3][3], per_class[3][4]))
+    # macro: the classes with references are 0 and 1; SELD_c is averaged, not recomputed
+    assert macro == pytest.approx([f0 / 2, (er0 + 1) / 2, (le0 + 180) / 2, lr0 / 2, (seld0 + 1) / 2], rel=1e-15)
+    # micro: Nref 14, TP 6, FPs 1, FP 7, FN 7, DE_TP 7, DE_FN 7, S + D + I = 8
+    f, er, le, lr = 6 / (7 + 7.0), 8 / 14, 10.0, 0.5
+    assert micro == pytest.approx([f, er, le, lr, (er + (1 - f) + le / 180 + (1 - lr)) / 4], rel=1e-15)
+    out, out_class = sg.jackknife_rows(rec_counts, rec_sdi, rec_de)
+    assert out.shape == (3, 2, 5) and np.array_equal(out[2, 0], micro) and np.array_equal(out[2, 1], macro)
+    assert out[0, 1].tolist() == [0.0, 1.0, 180.0, 0.0, 1.0]              # without recording 0: class 1 alone
+    assert out[1, 1].tolist() == pytest.approx([f0, er0, le0, lr0, seld0], rel=1e-15)
+    assert out[1, 0, 1] == 6 / 10                                        # micro ER without recording 1: (3 + 0 + 3) / 10
+    one = sg.jackknife_rows(rec_counts[:1], rec_sdi[:1], rec_de[:1])[0]   # a single recording: the replicate is empty
+    assert one.shape == (2, 2, 5) and np.isnan(one[0, :, [0, 1, 3, 4]]).all() and (one[0, 0, 2] == 180.0)
+    assert np.isnan(one[0, 1]).all()                                     # no class with references: macro nan
+
+
+# ---------------------------------------------------------------------------------------------- jackknife, Student's t
+
+def test_jackknife_by_hand_and_nan_replicates():
+    import seld_eval
+    want = {"estimate": 2.5 + 1 / 3, "bias": -1 / 3, "se": math.sqrt(28 / 9), "n": 3}
+    want["low"] = want["estimate"] - sg.T975[2] * want["se"]
+    want["high"] = want["estimate"] + sg.T975[2] * want["se"]
+    for values in ([1.0, 2.0, 4.0, 2.5], [1.0, NAN, 2.0, 4.0, NAN, 2.5]):
+        got = seld_eval.jackknife(values)
+        assert set(got) == set(want) and got["n"] == 3
+        assert all(got[key] == pytest.approx(want[key], rel=1e-9) for key in want)
+        theirs = sg.jackknife(values[:-1], values[-1], sg.T975[2])
+        assert [got[key] for key in ("estimate", "bias", "se", "low", "high", "n")] == pytest.approx(list(theirs), rel=1e-9)
+    for values, n in (([1.0, NAN, NAN, 2.5], 1), ([2.5], 0), ([NAN, NAN, 2.5], 0)):
+        got = seld_eval.jackknife(values)
+        assert got["estimate"] == 2.5 and got["n"] == n
+        assert all(math.isnan(got[key]) for key in ("bias", "se", "low", "high"))
+    flat = seld_eval.jackknife([0.5, 0.5, 0.5, 0.5])
+    assert flat["se"] == 0.0 and flat["bias"] == 0.0 and flat["low"] == flat["high"] == 0.5
+    with pytest.raises(ValueError):
+        seld_eval.jackknife([])
+
+
+@pytest.mark.parametrize("df", list(sg.T975))
+def test_student_t_quantile(df):
+    import seld_eval
+    assert abs(seld_eval.student_t_975(df) - sg.T975[df]) <= 1e-9 * sg.T975[df]
+
+
+def test_student_t_quantile_is_monotone_and_refuses_df_below_one():
+    import seld_eval
+    values = [seld_eval.student_t_975(df) for df in (1, 2, 3, 4, 7, 20, 50, 1000, 100000)]
+    assert values == sorted(values, reverse=True) and abs(values[-1] - 1.959963984540054) < 1e-4
+    for bad in (0, -1, 0.5, NAN):
+        with pytest.raises(ValueError):
+            seld_eval.student_t_975(bad)
+
+
+# ---------------------------------------------------------------------------------------------- host side, switches
+
+def test_block_table_of_a_timeline():
+    import seld_eval
+    table = seld_eval.meta_frame_table(np.array([[0, 113], [113, 50], [163, 33]]))     # 23, 10 and 7 meta-frames
+    assert np.diff(table.seg_offsets).tolist() == list(sg.META)
+    blocks = seld_eval.block_table(table)
+    assert blocks.dtype == np.int64 and blocks.tolist() == sg.block_offsets(sg.SEG_OFFSETS).tolist() == [0, 3, 4, 5]
+    assert seld_eval.block_table(seld_eval.meta_frame_table(np.array([[0, 50], [50, 0], [50, 5]]))).tolist() == [0, 1, 1, 2]
+
+
+def test_config_defaults_are_off():
+    import config
+    import seld_eval
+    assert config.Config.SELD_SEGMENT_METRICS is False and config.Config.SELD_JACKKNIFE is False
+    assert seld_eval.segment_setting(None, None) == (False, False)
+    assert seld_eval.segment_setting(True, None) == (True, False) and seld_eval.segment_setting(True, True) == (True, True)
+
+
+def test_argument_errors_raise_before_anything_runs():
+    import seld_eval
+    import trainer
+    with pytest.raises(ValueError, match="jackknife needs"):
+        seld_eval.evaluate_logits(iter(()), None, jackknife=True)
+    with pytest.raises(ValueError, match="jackknife needs"):
+        seld_eval.evaluate_logits(iter(()), None, segment=False, jackknife=True)
+    with pytest.raises(ValueError, match="jackknife needs"):
+        trainer.evaluate_seld(None, jackknife=True)
+    with pytest.raises(ValueError, match="no recordings"):
+        seld_eval.segment_metrics(None, None, seld_eval.meta_frame_table(np.zeros((0, 2), np.int64)), [], 20.0)
+    import config
+    try:                                                                 # the Config switches: jackknife alone raises too
+        config.Config.SELD_JACKKNIFE = True
+        with pytest.raises(ValueError, match="jackknife needs"):
+            seld_eval.evaluate_logits(iter(()), None)
+        config.Config.SELD_SEGMENT_METRICS = True
+        assert seld_eval.segment_setting(None, None) == (True, True) and seld_eval.segment_setting(None, False) == (True, False)
+    finally:
+        config.Config.SELD_JACKKNIFE = config.Config.SELD_SEGMENT_METRICS = False
+
+
+def test_evaluate_seld_takes_the_segment_arguments():
+    import inspect
+    import seld_eval
+    import trainer
+    for fn in (trainer.evaluate_seld, seld_eval.evaluate_logits):
+        params = inspect.signature(fn).parameters
+        assert all(params[name].default is None for name in ("segment", "jackknife"))
+
+
+# ---------------------------------------------------------------------------------------------- exports, resources
+
+def test_header_binding_and_library_agree_on_the_segment_exports():
+    import ctypes
+    import seld_native
+    header = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "seld_hip.h").read_text(), flags=re.S)
+    lib = seld_native.load_library()
+    for name in EXPORTS:
+        proto = re.search(rf"int {name}\((.*?)\);", header, flags=re.S)
+        assert proto, f"{name} is not declared in include/seld_hip.h"
+        assert len(getattr(lib, name).argtypes) == len(proto.group(1).split(","))
+        assert hasattr(ctypes.CDLL(str(seld_native.LIB_PATH)), name)
+
+
+def test_segment_kernels_do_not_spill():
+    """The compiler's own resource report of the five kernels (both assignment instantiations, the block and fold launches
+    of the segment score, the jackknife) shows no scratch."""
+    run = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
+                          f"-I{ROOT / 'include'}", "-Rpass-analysis=kernel-resource-usage", "-c",
+                          str(CSRC / "seld_segment.hip"), "-o", "/dev/null"], capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr[-2000:]
+    found, current = {}, None
+    for line in run.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            current = m.group(1)
+        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and current:
+            found[current] = int(m.group(1))
+    assert len([k for k in found if "doa_assign_kernel" in k]) == 2
+    for kernel in ("segment_blocks_kernel", "segment_fold_kernel", "jackknife_kernel"):
+        assert any(kernel in k for k in found), (kernel, found)
+    assert all(v == 0 for v in found.values()), found
