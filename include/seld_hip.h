@@ -161,7 +161,7 @@ int seld_window_gather(const void* src, int64_t total_rows, int64_t row_bytes, c
  *       (az -> az + 90 k), then elevation flip e = p & 1 (el -> -el)
  *   [1] [2] time mask 0 (first frame of the window, length)      [3] [4] time mask 1
  *   [5] [6] frequency mask 0 (first of the 64 bins, length)      [7] [8] frequency mask 1
- *   [9] .. [11] padding.
+ *   [9] azimuth step r of the rotating gathers further down (these two entry points ignore it)      [10] [11] padding.
  * The kernels reduce p modulo 16 and only compare the mask fields with coordinates they generate themselves: no row can
  * make them read or write out of bounds.  Neither entry point allocates or synchronises (graph-capture safe); a window's
  * output depends on (source, starts[b], params[b]) only. */
@@ -184,6 +184,38 @@ int seld_window_gather_augment(const float* src, int64_t total_rows, int channel
  * Labels are never masked.  J % 4 != 0 (a quarter turn is not a whole number of cells) or I*J % 8 != 0: -4. */
 int seld_window_permute_mask(const uint16_t* src, int64_t total_rows, int I, int J, const int64_t* starts,
                              const int32_t* params, int64_t B, int64_t window, uint16_t* dst, void* stream);
+
+/* ---- windows with rotation augmentation in azimuth steps (csrc/rotate.hip) ------------------ */
+/* Slot [9] of the parameter row above is the azimuth step r (reduced to 0..J-1 by a non-negative modulo; the two entry
+ * points above ignore it).  A window's transform: mirror m, then s = (k J/4 + r) mod J cells of azimuth (phi = 2 pi s / J),
+ * then elevation flip e, with m, k, e from the pattern.  With c = cos phi, sn = sin phi, sigma = -1 after a mirror else +1:
+ *   X' = c X - sn sigma Y,  Y' = sn X + c sigma Y.
+ *
+ * Rotation terms of a recording, once at construction: spectra [N][4][F][481] complex64 (seld_stft_*, channel 0 = W; ch_x and
+ * ch_y in 1..3 name the channels that carry X and Y) ->
+ *   out[n*sN + c*sC + m*sM + t*sT], c = 0..2:  P_X = mel |X|^2,  P_Y = mel |Y|^2,  C = mel Re(X conj Y)   (linear fp32),
+ * the library's mel filterbank.  No allocation, no synchronisation. */
+#define SELD_ROTATE_MAX_STEPS 72
+int seld_foa_rotation_terms(const float* spec_complex, int64_t N, int64_t F, int ch_x, int ch_y, float* out, int64_t sN,
+                            int64_t sC, int64_t sM, int64_t sT, void* stream);
+
+/* Features: src float32 [total_rows][channels][64] (channels = 4: log-mel W + XYZ in the order ch_x / ch_y / ch_z name;
+ * 7: + the three intensity vectors, channel 3 + c pairing W with input channel c) and rot float32 [total_rows][3][64] (the
+ * terms above, time-major) -> dst float32 [B][window][channels][64].
+ *   4 s % J == 0 (a whole number of quarter turns): bit-identical to seld_window_gather_augment under (m, 4 s / J, e).
+ *   otherwise: W and Z log-mel copied, IV_z copied with the flip's sign,
+ *     X' log-mel = power_to_db(c^2 P_X + sn^2 P_Y - 2 c sn sigma C),  Y' = power_to_db(sn^2 P_X + c^2 P_Y + 2 c sn sigma C)
+ *     (10 log10, floor exactly -100 dB),  IV_x' = c IV_x - sn sigma IV_y,  IV_y' = sn IV_x + c sigma IV_y.
+ * (cos, sin) come from a [J][2] fp32 table built here in double precision (exact 0 / +-1 at quarter turns) and passed in the
+ * kernel's arguments.  Masks and zero rows as seld_window_gather_augment; channel_table as there, not NULL.
+ * J: a multiple of 4, 4..SELD_ROTATE_MAX_STEPS; channels other than 4 and 7: -4. */
+int seld_window_gather_rotate(const float* src, const float* rot, int64_t total_rows, int channels, int freq_channels,
+                              int ch_x, int ch_y, int ch_z, int J, const int64_t* starts, const int32_t* params, int64_t B,
+                              int64_t window, const uint8_t* channel_table, float mask_value, float* dst, void* stream);
+
+/* Labels: seld_window_permute_mask with j' = ((m ? J-1-j : j) + s) mod J. */
+int seld_window_permute_mask_rotate(const uint16_t* src, int64_t total_rows, int I, int J, const int64_t* starts,
+                                    const int32_t* params, int64_t B, int64_t window, uint16_t* dst, void* stream);
 
 /* ---- loss: loss.py:43-54 class_mse_loss (+ its backward) ---------------------------------- */
 /* logits [n_cells][14] (fp32, or bf16 when logits_is_bf16), labels as EITHER the compact mask

@@ -157,6 +157,10 @@ class Config:
     # DataLoader path refuses to run with a switch on: there is no CPU fallback)
     AUGMENT_SPATIAL = False     # FOA audio channel swapping: one of the 16 sign-and-swap transforms per window and epoch, DOA
                                 # labels moved to match ('logmel' with 4 channels and 'logmel_iv' only)
+    AUGMENT_ROTATE = False      # rotation about the vertical axis in steps of one grid cell (10 degrees) on top of mirror and
+                                # elevation flip: 144 transforms instead of 16 (csrc/rotate.hip).  Implies the
+                                # spatial draw; needs DEVICE_FEED and a dataset constructed with the switch on (three extra mel
+                                # rows per frame of the timeline); 'logmel' with 4 channels and 'logmel_iv' only
     AUGMENT_TIME_MASKS = 0      # SpecAugment: time masks per window, 0..2, every channel
     AUGMENT_TIME_MASK_MAX = 0   # longest time mask in frames (a length is uniform in [0, max])
     AUGMENT_FREQ_MASKS = 0      # frequency masks per window, 0..2, log-mel and intensity-vector channels (not GCC-PHAT lags)

@@ -211,8 +211,9 @@ class _WindowTable:
                 "end_frame": min(start + ds.window_length_frames, ds.total_frames)}
 
 
-def save_compact_features(path, spec, mask):
-    """Write one recording's compact features to ``path`` so that a concurrent reader sees nothing or the whole file.
+def save_compact_features(path, spec, mask, rot=None):
+    """Write one recording's compact features (``rot``: its rotation terms, stored under a third key when given) to ``path``
+    so that a concurrent reader sees nothing or the whole file.
     Data-parallel runs construct the dataset on every rank at once: each writer gets its OWN temporary file (same
     directory, so the rename stays on one file system) and renames it into place; the loser of the race replaces the
     winner's file with identical bytes."""
@@ -223,7 +224,10 @@ def save_compact_features(path, spec, mask):
     fd, tmp = tempfile.mkstemp(prefix=path.stem + ".", suffix=".tmp.npz", dir=path.parent)
     try:
         with os.fdopen(fd, "wb") as handle:
-            np.savez(handle, spec=spec, mask=mask)
+            if rot is None:
+                np.savez(handle, spec=spec, mask=mask)
+            else:
+                np.savez(handle, spec=spec, mask=mask, rot=rot)
         os.replace(tmp, path)
     except BaseException:
         if os.path.exists(tmp):
@@ -282,18 +286,21 @@ class SELDDataset(Dataset):
         return Path(root) / f"{a.stem}.{hashlib.sha1(key.encode()).hexdigest()[:16]}.npz"
 
     def _file_features(self, audio_path, metadata_path):
-        """One recording -> (spec_tm [T, C, 64] f32, mask [T, 648] u16) on the device, cropped to the
-        common frame count (dataset.py:224-249).  With Config.FEATURE_CACHE_DIR the pair is kept on disk in its COMPACT
-        form (1 KB of features + 1.3 KB of label mask per frame; the reference's dense tensors are 37 KB per frame) and a
-        later construction uploads it instead of decoding and transforming the recording again."""
+        """One recording -> (spec_tm [T, C, 64] f32, mask [T, 648] u16, rotation terms [T, 3, 64] f32 or None) on the
+        device, cropped to the common frame count (dataset.py:224-249).  With Config.FEATURE_CACHE_DIR they are kept on disk
+        in their COMPACT form (1 KB of features + 1.3 KB of label mask per frame; the reference's dense tensors are 37 KB per
+        frame) and a later construction uploads them instead of decoding and transforming the recording again.  With
+        Config.AUGMENT_ROTATE a cache file without the rotation terms counts as a miss and is replaced."""
         cached = self._cache_path(audio_path, metadata_path)
         if cached is not None and cached.exists():
             with np.load(cached) as z:
-                return torch.from_numpy(z["spec"]).to(self.device), torch.from_numpy(z["mask"]).to(self.device)
-        spec, mask = self._file_features_uncached(audio_path, metadata_path)
-        if cached is not None and not cached.exists():
-            save_compact_features(cached, spec.cpu().numpy(), mask.cpu().numpy())
-        return spec, mask
+                if not self.with_rotation or "rot" in z.files:
+                    rot = torch.from_numpy(z["rot"]).to(self.device) if self.with_rotation else None
+                    return torch.from_numpy(z["spec"]).to(self.device), torch.from_numpy(z["mask"]).to(self.device), rot
+        spec, mask, rot = self._file_features_uncached(audio_path, metadata_path)
+        if cached is not None and (rot is not None or not cached.exists()):
+            save_compact_features(cached, spec.cpu().numpy(), mask.cpu().numpy(), None if rot is None else rot.cpu().numpy())
+        return spec, mask, rot
 
     def _file_features_uncached(self, audio_path, metadata_path):
         data, rate, bits = _read_wav(audio_path)
@@ -325,21 +332,30 @@ class SELDDataset(Dataset):
         else:
             mask, _, _ = metadata_to_mask(rows, audio_duration, self.I, self.J, device=self.device)
         frames = min(spec.shape[0], mask.shape[0])                             # dataset.py:243-249
-        return spec[:frames], mask[:frames]
+        rot = None
+        if self.with_rotation:
+            # Config.AUGMENT_ROTATE: the three mel rows per frame the rotating gather needs (csrc/rotate.hip), from the
+            # recording's complex STFT -- one recording at a time (a 60 s clip's spectra are 46 MB), freed right after
+            seld_augment.check_settings(config, getattr(config, "FEATURE_SET", "logmel"), int(spec.shape[1]))
+            rot = seld_native.foa_rotation_terms(seld_native.stft(signal.contiguous()),
+                                                 getattr(config, "FOA_CHANNEL_ORDER", "WYZX"))[:frames]
+        return spec[:frames], mask[:frames], rot
 
     def _build_timeline(self):
-        specs, masks, rows = [], [], []
+        specs, masks, rots, rows = [], [], [], []
         for idx, (audio_path, metadata_path) in enumerate(zip(self.audio_files, self.metadata_files)):
             try:
-                spec, mask = self._file_features(audio_path, metadata_path)
+                spec, mask, rot = self._file_features(audio_path, metadata_path)
             except Exception as exc:
                 logger.error(f"Error processing file {idx} ({audio_path}): {exc}")
                 raise
             specs.append(spec)
             masks.append(mask)
+            rots.append(rot)
             rows.append(_read_metadata_rows(metadata_path))
         self._set_segments([int(s.shape[0]) for s in specs], rows)
-        self._set_timeline(torch.cat(specs, dim=0), torch.cat(masks, dim=0))
+        self._set_timeline(torch.cat(specs, dim=0), torch.cat(masks, dim=0),
+                           torch.cat(rots, dim=0) if self.with_rotation else None)
 
     def _set_segments(self, frame_counts, rows):
         """Evaluation bookkeeping (seld_eval.py): ``segments`` int64 [n_files, 2] = (first frame, cropped frame count) of
@@ -350,9 +366,11 @@ class SELDDataset(Dataset):
         self.metadata_rows = [np.asarray(r, dtype=np.int64).reshape(len(r), -1)[:, :5].copy() if len(r)
                               else np.zeros((0, 5), dtype=np.int64) for r in rows]
 
-    def _set_timeline(self, spec_tm, mask_tm):
+    def _set_timeline(self, spec_tm, mask_tm, rot_tm=None):
         self.spec_tm = spec_tm.contiguous()            # [total, C, 64] float32 (device)
         self.mask_tm = mask_tm.contiguous()            # [total, 648]  uint16  (device)
+        # [total, 3, 64] float32 (device): rotation terms, only when constructed with Config.AUGMENT_ROTATE
+        self.rot_tm = rot_tm.contiguous() if rot_tm is not None and self.keep_on_device else None
         self.total_frames = int(self.spec_tm.shape[0])
         self.n_channels = int(self.spec_tm.shape[1])
         # host mirrors for the stock DataLoader path (worker processes must not touch the GPU)
@@ -377,14 +395,16 @@ class SELDDataset(Dataset):
         SELDDataset._init_fields(self, num_classes, device)
         if use_gaussian_augmentation is not None:
             self.use_gaussian_augmentation = bool(use_gaussian_augmentation)
-        specs, masks, kept = [], [], []
+        specs, masks, rots, kept = [], [], [], []
         for pcm, rows in zip(clips, metadata_rows):
-            spec, mask = self._features_from_pcm(pcm.to(self.device), sample_rate, np.asarray(rows))
+            spec, mask, rot = self._features_from_pcm(pcm.to(self.device), sample_rate, np.asarray(rows))
             specs.append(spec)
             masks.append(mask)
+            rots.append(rot)
             kept.append(np.asarray(rows))
         self._set_segments([int(s.shape[0]) for s in specs], kept)
-        self._set_timeline(torch.cat(specs, dim=0), torch.cat(masks, dim=0))
+        self._set_timeline(torch.cat(specs, dim=0), torch.cat(masks, dim=0),
+                           torch.cat(rots, dim=0) if self.with_rotation else None)
         self._build_window_table()
         return self
 
@@ -403,6 +423,8 @@ class SELDDataset(Dataset):
         self.keep_on_device = True
         self._label_rng = np.random.RandomState(config.SEED) if config.SEED is not None else None
         self.use_gaussian_augmentation = bool(config.GAUSSIAN_AUGMENT)
+        self.with_rotation = bool(getattr(config, "AUGMENT_ROTATE", False))   # as of construction: decides whether rot_tm exists
+        self.rot_tm = None
 
     # -- reference-shaped views ---------------------------------------------------------------
     @property
@@ -440,7 +462,9 @@ class SELDDataset(Dataset):
         ``out``: callable (spec_shape, spec_dtype, mask_shape, mask_dtype) -> (spec_buffer, mask_buffer) or None --
         the static input buffers of a captured training step (seld_graph.GraphedTrainStep.static_inputs).
         ``augment``: None, or the windows' parameter table (int32 [B, 12], ``seld_augment.draw``): the batch is then
-        produced by the augmenting gathers (csrc/augment.hip) -- channel swap + label cell permutation + masks."""
+        produced by the augmenting gathers (csrc/augment.hip) -- channel swap + label cell permutation + masks; on a dataset
+        constructed with Config.AUGMENT_ROTATE (``rot_tm`` exists) by the rotating pair (csrc/rotate.hip), which also honours
+        the azimuth step in slot [9] of a row."""
         if self.spec_tm is None:
             raise RuntimeError("device_batch needs keep_on_device=True")
         starts = torch.as_tensor(self.window_starts[np.asarray(indices, dtype=np.int64)])
@@ -452,6 +476,14 @@ class SELDDataset(Dataset):
         if augment is not None:
             table, freq_channels, mask_value = self._augment_tables()
             starts = starts.to(self.device, non_blocking=True)
+            if getattr(self, "rot_tm", None) is not None:
+                params = seld_native.augment_params(augment, len(starts), w, self.device, steps=self.J)
+                spec = seld_native.gather_windows_rotate(self.spec_tm, self.rot_tm, starts, w, params, table,
+                                                         getattr(config, "FOA_CHANNEL_ORDER", "WYZX"), self.J, freq_channels,
+                                                         mask_value, out=bufs[0] if bufs else None)
+                mask = seld_native.gather_windows_permute_rotate(self.mask_tm, starts, w, params, self.I, self.J,
+                                                                 out=bufs[1] if bufs else None)
+                return spec, mask
             params = seld_native.augment_params(augment, len(starts), w, self.device)     # one more small async copy
             spec = seld_native.gather_windows_augment(self.spec_tm, starts, w, params, table, freq_channels, mask_value,
                                                       out=bufs[0] if bufs else None)

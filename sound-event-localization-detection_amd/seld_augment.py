@@ -12,9 +12,16 @@ first-order-Ambisonics channels ("audio channel swapping"); on the 10-degree gri
 cells, so features AND labels of the transformed sound field are gathers of the stored ones.
 
 Parameter row of one window (int32 x 12, ``include/seld_hip.h``):
-    [0] pattern   [1] [2] [3] [4] two time masks (first frame, length)   [5] [6] [7] [8] two frequency masks   [9..11] 0
+    [0] pattern   [1] [2] [3] [4] two time masks (first frame, length)   [5] [6] [7] [8] two frequency masks
+    [9] azimuth step r   [10] [11] 0
+
+Rotation in azimuth steps (``csrc/rotate.hip``): on the I x J grid a rotation about the vertical axis by
+a multiple of one cell (10 degrees) is still an exact cyclic shift of the label cells.  A window's transform is then
+mirror m, s = (k J/4 + r) mod J cells of azimuth (phi = 2 pi s / J), elevation flip e: 2 x J x 2 = 144 transforms.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 
@@ -23,7 +30,10 @@ PATTERNS = 16
 N_BINS = 64
 NEGATE = 0x80                     # channel-table flag: the output channel is MINUS its source channel
 
-SWITCHES = ("AUGMENT_SPATIAL", "AUGMENT_TIME_MASKS", "AUGMENT_FREQ_MASKS")
+STEP = 9                          # parameter-row slot of the azimuth step r
+MAX_STEPS = 72                    # SELD_ROTATE_MAX_STEPS
+
+SWITCHES = ("AUGMENT_SPATIAL", "AUGMENT_TIME_MASKS", "AUGMENT_FREQ_MASKS", "AUGMENT_ROTATE")
 
 
 def decode(p: int):
@@ -102,12 +112,54 @@ def cell_source(p: int, I: int = 18, J: int = 36) -> np.ndarray:
     return src
 
 
+# ------------------------------------------------------------------------------------------ rotation in azimuth steps
+
+def total_step(k: int, r: int, J: int = 36) -> int:
+    """Cells of azimuth a window is turned by: k quarter turns of the pattern plus the step r, modulo J."""
+    if J % 4:
+        raise ValueError("a quarter turn is a whole number of cells only when J % 4 == 0")
+    return (int(k) * (J // 4) + int(r)) % J
+
+
+def rotation_table(J: int = 36) -> np.ndarray:
+    """float32 [J, 2]: (cos, sin) of 2 pi s / J, evaluated in double precision and rounded once; exactly 0 / +-1 at the quarter
+    turns.  The table ``seld_window_gather_rotate`` builds for its kernel."""
+    if J % 4 or not 4 <= J <= MAX_STEPS:
+        raise ValueError(f"rotation steps: J must be a multiple of 4 in 4..{MAX_STEPS}, got {J}")
+    table = np.zeros((J, 2), dtype=np.float32)
+    for s in range(J):
+        if (4 * s) % J == 0:
+            table[s] = ((1, 0), (0, 1), (-1, 0), (0, -1))[4 * s // J]
+        else:
+            phi = 2.0 * math.pi * s / J
+            table[s] = (math.cos(phi), math.sin(phi))
+    return table
+
+
+def cell_dest_rot(m: int, s: int, e: int, I: int = 18, J: int = 36) -> np.ndarray:
+    """int64 [I*J]: the cell a set cell moves TO under mirror m, then s cells of azimuth, then elevation flip e:
+    (i, j) -> (e ? I-1-i : i, ((m ? J-1-j : j) + s) mod J).  ``cell_dest(p)`` is the case s = k J/4."""
+    i, j = np.divmod(np.arange(I * J, dtype=np.int64), J)
+    i2 = I - 1 - i if e else i
+    j2 = ((J - 1 - j if m else j) + int(s)) % J
+    return i2 * J + j2
+
+
+def cell_source_rot(m: int, s: int, e: int, I: int = 18, J: int = 36) -> np.ndarray:
+    """int64 [I*J]: the gather form, out[..., c] = in[..., cell_source_rot[c]] (the inverse of ``cell_dest_rot``)."""
+    dest = cell_dest_rot(m, s, e, I, J)
+    src = np.empty_like(dest)
+    src[dest] = np.arange(I * J, dtype=np.int64)
+    return src
+
+
 # ------------------------------------------------------------------------------------------ configuration
 
 def settings(cfg):
     """The augmentation switches of a Config as a plain dict (missing attributes = off)."""
     return {
         "spatial": bool(getattr(cfg, "AUGMENT_SPATIAL", False)),
+        "rotate": bool(getattr(cfg, "AUGMENT_ROTATE", False)),
         "time_masks": int(getattr(cfg, "AUGMENT_TIME_MASKS", 0)),
         "time_max": int(getattr(cfg, "AUGMENT_TIME_MASK_MAX", 0)),
         "freq_masks": int(getattr(cfg, "AUGMENT_FREQ_MASKS", 0)),
@@ -119,7 +171,7 @@ def settings(cfg):
 
 def enabled(cfg) -> bool:
     s = settings(cfg)
-    return s["spatial"] or s["time_masks"] > 0 or s["freq_masks"] > 0
+    return s["spatial"] or s["rotate"] or s["time_masks"] > 0 or s["freq_masks"] > 0
 
 
 def check_settings(cfg, feature_set: str | None = None, n_channels: int | None = None):
@@ -138,6 +190,11 @@ def check_settings(cfg, feature_set: str | None = None, n_channels: int | None =
             f"AUGMENT_SPATIAL is defined for 4-channel FOA features ('logmel' with 4 channels, 'logmel_iv'), not for "
             f"FEATURE_SET={feature_set!r} with {n_channels} feature channels: a microphone array's geometry is unknown here, "
             f"so no channel swap is defined (time / frequency masks work for every feature set)")
+    if s["rotate"] and feature_set is not None and not spatial_supported(feature_set, int(n_channels)):
+        raise ValueError(
+            f"AUGMENT_ROTATE is defined for 4-channel FOA features ('logmel' with 4 channels, 'logmel_iv'), not for "
+            f"FEATURE_SET={feature_set!r} with {n_channels} feature channels: a microphone array's geometry is unknown here, "
+            f"so no rotation is defined (time / frequency masks work for every feature set)")
     return s
 
 
@@ -195,23 +252,33 @@ def check_tta(patterns, feature_set: str, n_channels: int):
             f"array's geometry is unknown here, so no channel swap is defined")
 
 
-def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, bins: int = N_BINS) -> np.ndarray:
+def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, bins: int = N_BINS,
+         steps: int | None = None) -> np.ndarray:
     """int32 [B, 12] parameter rows for the windows ``window_indices`` (dataset window indices) of ``epoch``.
 
     A window's row is a function of (seed, epoch, window index) and the switches ONLY -- not of the rank, the batch size
     or the position in the batch -- so N-rank training sees the same augmented windows as one rank, and a window repeated
     by the data-parallel wrap padding gets the same transform both times.  The pattern is uniform over the 16; a mask
-    length is a uniform integer in [0, max] (max clipped to the axis), its start uniform over the positions that fit."""
+    length is a uniform integer in [0, max] (max clipped to the axis), its start uniform over the positions that fit.
+
+    With AUGMENT_ROTATE the spatial part is drawn over the 4 J transforms instead: mirror and elevation flip uniform, no
+    quarter turns in the pattern (m << 3 | e), the azimuth step [9] uniform in 0..steps-1 (``steps``: the grid's J, default
+    360 // GRID_CELL_DEGREES).  With it off the generator is asked exactly what it was asked before the switch existed."""
     s = check_settings(cfg)
+    if steps is None:
+        steps = int(360 // getattr(cfg, "GRID_CELL_DEGREES", 10))
     if window is None:
         window = int(int(cfg.WINDOW_LENGTH) / int(cfg.SPECTROGRAM_HOP_LENGTH))
     idx = np.asarray(window_indices, dtype=np.int64).reshape(-1)
     rows = identity_rows(len(idx))
-    if not (s["spatial"] or s["time_masks"] or s["freq_masks"]):
+    if not (s["spatial"] or s["rotate"] or s["time_masks"] or s["freq_masks"]):
         return rows
     for r, i in enumerate(idx):
         rng = np.random.default_rng([int(seed), int(epoch), int(i)])
-        if s["spatial"]:
+        if s["rotate"]:
+            rows[r, 0] = (int(rng.integers(0, 2)) << 3) | int(rng.integers(0, 2))
+            rows[r, STEP] = rng.integers(0, int(steps))
+        elif s["spatial"]:
             rows[r, 0] = rng.integers(0, PATTERNS)
         for first, count, longest, axis in ((1, s["time_masks"], s["time_max"], int(window)),
                                             (5, s["freq_masks"], s["freq_max"], int(bins))):

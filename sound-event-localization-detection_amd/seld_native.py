@@ -72,6 +72,10 @@ def _declare(lib):
     lib.seld_window_gather.argtypes = [_ptr, _i64, _i64, _ptr, _i64, _i64, _ptr, _ptr]
     lib.seld_window_gather_augment.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _i64, _i64, _ptr, ctypes.c_float, _ptr, _ptr]
     lib.seld_window_permute_mask.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _i64, _i64, _ptr, _ptr]
+    lib.seld_foa_rotation_terms.argtypes = [_ptr, _i64, _i64, _int, _int, _ptr, _i64, _i64, _i64, _i64, _ptr]
+    lib.seld_window_gather_rotate.argtypes = [_ptr, _ptr, _i64, _int, _int, _int, _int, _int, _int, _ptr, _ptr, _i64, _i64, _ptr,
+                                              ctypes.c_float, _ptr, _ptr]
+    lib.seld_window_permute_mask_rotate.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _i64, _i64, _ptr, _ptr]
     lib.seld_softmax_mse_workspace_bytes.restype = _i64
     lib.seld_softmax_mse_workspace_bytes.argtypes = []
     lib.seld_softmax_mse.argtypes = [_ptr, _int, _ptr, _ptr, _i64, _int, ctypes.c_float, _ptr, _ptr, _ptr, _ptr]
@@ -487,10 +491,11 @@ AUGMENT_PARAM_INTS = 12      # SELD_AUGMENT_PARAM_INTS: (pattern, 2 x (time star
 AUGMENT_PATTERNS = 16
 
 
-def augment_params(params, batch: int, window: int, device) -> torch.Tensor:
+def augment_params(params, batch: int, window: int, device, steps: int | None = None) -> torch.Tensor:
     """The per-window parameter table of the augmenting gathers as an int32 [batch, 12] device tensor.  A host table
-    (numpy array / CPU tensor) is validated here -- pattern in 0..15, every mask inside its axis -- and uploaded with one
-    asynchronous copy; a device tensor is trusted (no synchronise; the kernels clamp whatever they are given)."""
+    (numpy array / CPU tensor) is validated here -- pattern in 0..15, every mask inside its axis, and with ``steps`` (the J
+    of the rotating gathers) the azimuth step [9] in 0..steps-1 -- and uploaded with one asynchronous copy; a device tensor
+    is trusted (no synchronise; the kernels clamp whatever they are given)."""
     t = torch.as_tensor(params)
     if tuple(t.shape) != (batch, AUGMENT_PARAM_INTS):
         raise ValueError(f"augment parameters must be [{batch}, {AUGMENT_PARAM_INTS}], got {tuple(t.shape)}")
@@ -506,6 +511,8 @@ def augment_params(params, batch: int, window: int, device) -> torch.Tensor:
             start, length = t[:, first], t[:, first + 1]
             if int(start.min()) < 0 or int(length.min()) < 0 or int((start + length).max()) > axis:
                 raise ValueError(f"augment parameters: {what} mask outside [0, {axis})")
+        if steps is not None and (int(t[:, 9].min()) < 0 or int(t[:, 9].max()) >= int(steps)):
+            raise ValueError(f"augment parameters: azimuth step outside 0..{int(steps) - 1}")
     return t.to(device, non_blocking=True)
 
 
@@ -569,6 +576,103 @@ def gather_windows_permute(src: torch.Tensor, starts: torch.Tensor, window: int,
     with _device_guard(index):
         check(load_library().seld_window_permute_mask(_p(src), src.shape[0], I, J, _p(starts), _p(params), starts.numel(),
                                                       window, _p(out), _stream_ptr(src.device)), "seld_window_permute_mask")
+    return out
+
+
+def foa_channels(order: str = "WYZX"):
+    """(ch_x, ch_y, ch_z): the input channels that carry X, Y and Z under Config.FOA_CHANNEL_ORDER (W is channel 0)."""
+    order = str(order).upper()
+    if len(order) != 4 or order[0] != "W" or sorted(order[1:]) != ["X", "Y", "Z"]:
+        raise ValueError(f"FOA_CHANNEL_ORDER must be 'WYZX' or 'WXYZ', got {order!r}")
+    return order.index("X"), order.index("Y"), order.index("Z")
+
+
+def foa_rotation_terms(spec: torch.Tensor, order: str = "WYZX") -> torch.Tensor:
+    """Rotation terms of the rotating gather (csrc/rotate.hip) from the complex STFT of 4-channel FOA clips, ``stft(pcm)``:
+    complex64 [N, 4, F, 481] (or [4, F, 481]) -> float32 [N, F, 3, 64] time-major (or [F, 3, 64]):
+    P_X = mel |X|^2, P_Y = mel |Y|^2, C = mel Re(X conj Y), linear (not dB)."""
+    squeeze = spec.dim() == 3
+    if squeeze:
+        spec = spec.unsqueeze(0)
+    if not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 4 or spec.shape[1] != 4 or spec.shape[3] != N_BINS:
+        raise SeldNativeError("foa_rotation_terms: spec must be a complex64 GPU tensor [N, 4, F, 481]")
+    ch_x, ch_y, _ = foa_channels(order)
+    spec = spec.contiguous()
+    n, _, frames, _ = spec.shape
+    if n == 0 or frames == 0:
+        raise ValueError("foa_rotation_terms: empty input")
+    index = ensure_init(spec.device)
+    out = torch.empty((n, frames, 3, N_MELS), dtype=torch.float32, device=spec.device)
+    with _device_guard(index):
+        check(load_library().seld_foa_rotation_terms(_p(torch.view_as_real(spec)), n, frames, ch_x, ch_y, _p(out),
+                                                     frames * 3 * N_MELS, N_MELS, 1, 3 * N_MELS, _stream_ptr(spec.device)),
+              "seld_foa_rotation_terms")
+    return out[0] if squeeze else out
+
+
+def gather_windows_rotate(src: torch.Tensor, rot: torch.Tensor, starts: torch.Tensor, window: int, params: torch.Tensor,
+                          channel_table, order: str = "WYZX", J: int = GRID_J, freq_channels: int | None = None,
+                          mask_value: float = 0.0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gather_windows_augment`` with the azimuth step of ``params[:, 9]`` (csrc/rotate.hip): src [T, C, 64] with C = 4
+    ('logmel') or 7 ('logmel_iv'), rot [T, 3, 64] the timeline's rotation terms (``foa_rotation_terms``).  A window whose
+    total rotation is a whole number of quarter turns is the signed channel copy of ``gather_windows_augment``, bit for bit;
+    any other window gets X' / Y' log-mel and IV_x' / IV_y' computed from the terms."""
+    if not src.is_cuda or src.dtype != torch.float32 or src.dim() != 3 or src.shape[2] != N_MELS:
+        raise SeldNativeError("gather_windows_rotate: src must be a float32 GPU tensor [T, C, 64]")
+    src = src.contiguous()
+    channels = int(src.shape[1])
+    if src.shape[0] == 0:
+        raise ValueError("gather_windows_rotate: empty source")
+    if not rot.is_cuda or rot.dtype != torch.float32 or tuple(rot.shape) != (src.shape[0], 3, N_MELS) or rot.device != src.device:
+        raise SeldNativeError(f"gather_windows_rotate: rot must be a float32 tensor [{src.shape[0]}, 3, 64] on {src.device}")
+    rot = rot.contiguous()
+    ch_x, ch_y, ch_z = foa_channels(order)
+    freq_channels = channels if freq_channels is None else int(freq_channels)
+    index = ensure_init(src.device)
+    starts = starts.to(device=src.device, dtype=torch.int64).contiguous()
+    if not params.is_cuda or params.dtype != torch.int32 or tuple(params.shape) != (starts.numel(), AUGMENT_PARAM_INTS) \
+            or not params.is_contiguous():
+        raise ValueError("gather_windows_rotate: params must be a contiguous int32 [B, 12] GPU tensor (augment_params)")
+    import numpy as np
+    table = np.ascontiguousarray(channel_table, dtype=np.uint8)
+    if table.shape != (AUGMENT_PATTERNS, channels):
+        raise ValueError(f"gather_windows_rotate: channel_table must be [16, {channels}]")
+    shape = (starts.numel(), window, channels, N_MELS)
+    if out is None:
+        out = torch.empty(shape, dtype=src.dtype, device=src.device)
+    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
+        raise ValueError(f"gather_windows_rotate: out must be a contiguous float32 tensor of shape {shape} on {src.device}")
+    with _device_guard(index):
+        check(load_library().seld_window_gather_rotate(
+            _p(src), _p(rot), src.shape[0], channels, freq_channels, ch_x, ch_y, ch_z, int(J), _p(starts), _p(params),
+            starts.numel(), window, ctypes.c_void_p(table.ctypes.data), float(mask_value), _p(out), _stream_ptr(src.device)),
+            "seld_window_gather_rotate")
+    return out
+
+
+def gather_windows_permute_rotate(src: torch.Tensor, starts: torch.Tensor, window: int, params: torch.Tensor, I: int = GRID_I,
+                                  J: int = GRID_J, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gather_windows_permute`` with the azimuth index of every cell shifted by the window's total step
+    (k J/4 + params[:, 9]) mod J after the mirror (csrc/rotate.hip)."""
+    if not src.is_cuda or src.dtype != torch.uint16 or src.dim() != 2 or src.shape[1] != I * J:
+        raise SeldNativeError("gather_windows_permute_rotate: src must be a uint16 GPU tensor [T, I*J]")
+    src = src.contiguous()
+    if src.shape[0] == 0:
+        raise ValueError("gather_windows_permute_rotate: empty source")
+    index = ensure_init(src.device)
+    starts = starts.to(device=src.device, dtype=torch.int64).contiguous()
+    if not params.is_cuda or params.dtype != torch.int32 or tuple(params.shape) != (starts.numel(), AUGMENT_PARAM_INTS) \
+            or not params.is_contiguous():
+        raise ValueError("gather_windows_permute_rotate: params must be a contiguous int32 [B, 12] GPU tensor (augment_params)")
+    shape = (starts.numel(), window, I * J)
+    if out is None:
+        out = torch.empty(shape, dtype=src.dtype, device=src.device)
+    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
+        raise ValueError(f"gather_windows_permute_rotate: out must be a contiguous uint16 tensor of shape {shape} on {src.device}")
+    with _device_guard(index):
+        check(load_library().seld_window_permute_mask_rotate(_p(src), src.shape[0], I, J, _p(starts), _p(params),
+                                                             starts.numel(), window, _p(out), _stream_ptr(src.device)),
+              "seld_window_permute_mask_rotate")
     return out
 
 

@@ -307,6 +307,9 @@ class DeviceFeed:
         # a spatial swap the feature set does not define is refused when the feed is built, not at the first batch
         if seld_augment.enabled(config):
             seld_augment.check_settings(config, getattr(config, "FEATURE_SET", "logmel"), self.dataset.n_channels)
+            if seld_augment.settings(config)["rotate"] and getattr(self.dataset, "rot_tm", None) is None:
+                raise ValueError("AUGMENT_ROTATE needs a dataset constructed with the switch on and kept on the device: the "
+                                 "rotating gather reads three extra mel rows per frame of the timeline (SELDDataset.rot_tm)")
 
     def _order(self, epoch):
         return shard_indices(epoch_order(len(self.dataset), self.shuffle, self.seed, epoch), self.rank, self.world)
