@@ -15,7 +15,7 @@
 namespace seld {
 namespace eval {
 
-// One workgroup per meta-frame q0 + blockIdx.x (the body, shared with seld_tta.hip: seld_eval_core.h).
+// One workgroup per meta-frame q0 + blockIdx.x (the body, shared with seld_tta.hip and seld_refine.hip: seld_eval_core.h).
 template <bool kBf16>
 __global__ __launch_bounds__(kThreads) void grid_decode_kernel(
     const uint4* __restrict__ logits, long w0, long nw, long W, long total, const int64_t* __restrict__ meta_first,
@@ -44,34 +44,14 @@ int seld_grid_decode(const void* logits, int is_bf16, int64_t w0, int64_t nw, in
                      int32_t* det_cell, float* det_score, int32_t* det_count, float* probs_out, void* stream_) {
   using namespace seld;
   using namespace seld::eval;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (K < 1 || K > kMaxK) return fail(kErrInvalidArgument, "seld_grid_decode: K must be in 1..8");
-  if (is_bf16 != 0 && is_bf16 != 1) return fail(kErrInvalidArgument, "seld_grid_decode: is_bf16 must be 0 or 1");
-  if (total < 1 || W != (total + eval::kHop - 1) / eval::kHop)
-    return fail(kErrInvalidArgument, "seld_grid_decode: W must be ceil(total / 50) for a timeline of total >= 1 frames");
-  if (w0 < 0 || nw < 1 || w0 + nw > W || q0 < 0 || nq < 0)
-    return fail(kErrInvalidArgument, "seld_grid_decode: bad window or meta-frame range");
-  if (nq == 0) return kOk;
-  if (!logits || !meta_first || !meta_len || !det_cell || !det_score || !det_count)
-    return fail(kErrInvalidArgument, "seld_grid_decode: null pointer");
-  if ((reinterpret_cast<uintptr_t>(logits) & 15u) != 0 || (probs_out && (reinterpret_cast<uintptr_t>(probs_out) & 15u) != 0))
-    return fail(kErrUnsupported, "seld_grid_decode: logits and probs_out must be 16-byte aligned");
-  if (nq > 0x7fffffffLL) return fail(kErrUnsupported, "seld_grid_decode: too many meta-frames for one launch");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const auto* src = static_cast<const uint4*>(logits);
-  if (is_bf16)
-    hipLaunchKernelGGL(grid_decode_kernel<true>, dim3(static_cast<unsigned>(nq)), dim3(kThreads), 0, stream, src,
-                       static_cast<long>(w0), static_cast<long>(nw), static_cast<long>(W), static_cast<long>(total),
-                       meta_first, meta_len, static_cast<long>(q0), threshold, K, det_cell, det_score, det_count,
-                       probs_out);
-  else
-    hipLaunchKernelGGL(grid_decode_kernel<false>, dim3(static_cast<unsigned>(nq)), dim3(kThreads), 0, stream, src,
-                       static_cast<long>(w0), static_cast<long>(nw), static_cast<long>(W), static_cast<long>(total),
-                       meta_first, meta_len, static_cast<long>(q0), threshold, K, det_cell, det_score, det_count,
-                       probs_out);
-  SELD_HIP_TRY(hipGetLastError());
-  return kOk;
+  const int rc = check_decode_args("seld_grid_decode", logits, is_bf16, w0, nw, W, total, meta_first, meta_len, q0, nq,
+                                   Patterns::kNone, nullptr, 0, nullptr, K, false, nullptr, det_cell, det_score, det_count,
+                                   nullptr, probs_out);
+  if (rc != kOk || nq == 0) return rc;
+  return launch_meta_frames(is_bf16 ? grid_decode_kernel<true> : grid_decode_kernel<false>, nq, stream_,
+                            static_cast<const uint4*>(logits), static_cast<long>(w0), static_cast<long>(nw),
+                            static_cast<long>(W), static_cast<long>(total), meta_first, meta_len, static_cast<long>(q0),
+                            threshold, K, det_cell, det_score, det_count, probs_out);
 }
 
 int seld_doa_match(const int32_t* det_cell, const int32_t* det_count, int K, const int32_t* ref_offsets,
@@ -79,19 +59,13 @@ int seld_doa_match(const int32_t* det_cell, const int32_t* det_count, int K, con
                    void* stream_) {
   using namespace seld;
   using namespace seld::eval;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (K < 1 || K > kMaxK) return fail(kErrInvalidArgument, "seld_doa_match: K must be in 1..8");
-  if (nq < 0 || I < 1 || J < 1) return fail(kErrInvalidArgument, "seld_doa_match: bad extents");
-  if (nq == 0) return kOk;
-  if (!det_cell || !det_count || !ref_offsets || !stats || !cost)
-    return fail(kErrInvalidArgument, "seld_doa_match: null pointer");
-  const long n_qc = static_cast<long>(nq) * kC;
-  const long blocks = (n_qc + kMatchThreads - 1) / kMatchThreads;
-  if (blocks > 0x7fffffffL) return fail(kErrUnsupported, "seld_doa_match: too many meta-frames for one launch");
-  hipLaunchKernelGGL(doa_match_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kMatchThreads), 0,
-                     static_cast<hipStream_t>(stream_), det_cell, det_count, K, ref_offsets, ref_dirs, n_qc, I, J,
-                     thr_deg, stats, cost);
+  long n_qc = 0;
+  unsigned blocks = 0;
+  const int rc = check_match_args("seld_doa_match", det_cell, nullptr, K, nq, I, J, true,
+                                  {det_count, ref_offsets, stats, cost}, false, &n_qc, &blocks);
+  if (rc != kOk || nq == 0) return rc;
+  hipLaunchKernelGGL(doa_match_kernel, dim3(blocks), dim3(kMatchThreads), 0, static_cast<hipStream_t>(stream_), det_cell,
+                     det_count, K, ref_offsets, ref_dirs, n_qc, I, J, thr_deg, stats, cost);
   SELD_HIP_TRY(hipGetLastError());
   return kOk;
 }

@@ -1,8 +1,11 @@
 // The grid-map decode shared by seld_grid_decode (seld_eval.hip), seld_grid_decode_tta (seld_tta.hip) and
-// seld_grid_decode_refine (seld_refine.hip): one meta-frame per workgroup of 512 threads, DESIGN.md sections 10, 13 and
-// 15.  decode_meta_frame<kBf16, kTta, kRefine> is the whole kernel body; with kTta = false every `if constexpr (kTta)`
-// drops out and what is left is the plain decode, and with kRefine = false so does the sub-cell DOA epilogue, so the
-// entry points cannot drift apart in summation order or arithmetic.
+// seld_grid_decode_refine (seld_refine.hip): one meta-frame per workgroup of 512 threads, DESIGN.md sections 10, 13, 15
+// and 20.  Shared by all three, so they cannot drift apart in summation order, arithmetic or a check:
+//   decode_meta_frame<kBf16, kTta, kRefine>  the whole kernel body; with kTta = false every `if constexpr (kTta)` drops out
+//                                            and what is left is the plain decode, and with kRefine = false so does the
+//                                            sub-cell DOA epilogue
+//   check_decode_args, pack_patterns         the host prologue of the three entry points
+//   launch_meta_frames                       their launch: one workgroup per meta-frame
 #pragma once
 
 #include "seld_common.h"
@@ -335,6 +338,71 @@ __device__ __forceinline__ void decode_meta_frame(
       det_count[qi * kC + c] = count;
     }
   }
+}
+
+// ---- the host prologue of the three entry points -----------------------------------------------------------------------
+// `patterns` [n] -> 4 bits each in *packed, pattern n at bits 4 n.  n must be in 1..16, or 0 with `allow_zero` (the plain
+// walk: `patterns` is then NULL, and only then); every pattern in 0..15 and none twice.
+inline int pack_patterns(const char* who, const int32_t* patterns, int n, bool allow_zero, uint64_t* packed) {
+  const std::string name(who);
+  if (n < (allow_zero ? 0 : 1) || n > kMaxPatterns)
+    return fail(kErrInvalidArgument, name + (allow_zero ? ": n_patterns must be 0 (the plain walk) or in 1..16"
+                                                        : ": n_patterns must be in 1..16"));
+  if (allow_zero ? (n == 0) != (patterns == nullptr) : !patterns)
+    return fail(kErrInvalidArgument, name + (allow_zero ? ": patterns must be NULL exactly when n_patterns is 0"
+                                                        : ": null pointer"));
+  unsigned seen = 0;
+  *packed = 0;
+  for (int i = 0; i < n; ++i) {
+    const int32_t p = patterns[i];
+    if (p < 0 || p >= kMaxPatterns) return fail(kErrInvalidArgument, name + ": pattern outside 0..15");
+    if (seen & (1u << p)) return fail(kErrInvalidArgument, name + ": duplicate pattern");
+    seen |= 1u << p;
+    *packed |= static_cast<uint64_t>(p) << (4 * i);
+  }
+  return kOk;
+}
+
+enum class Patterns { kNone, kOneOrMore, kAny };      // seld_grid_decode, _tta, _refine
+
+// In this order: the library's state, K, is_bf16, the patterns (pack_patterns, unless kNone), the timeline, the window
+// and meta-frame range, with `refine` cell_unit and det_dir, the empty call, the other pointers, the 16-byte alignment of
+// logits, probs_out and (refine) det_dir, the launch limit.  A caller launches nothing when the code is not kOk or nq is 0.
+inline int check_decode_args(const char* who, const void* logits, int is_bf16, int64_t w0, int64_t nw, int64_t W,
+                             int64_t total, const int64_t* meta_first, const int32_t* meta_len, int64_t q0, int64_t nq,
+                             Patterns mode, const int32_t* patterns, int n_patterns, uint64_t* packed, int K, bool refine,
+                             const float* cell_unit, const int32_t* det_cell, const float* det_score,
+                             const int32_t* det_count, const float* det_dir, const float* probs_out) {
+  const std::string name(who);
+  const auto misaligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) != 0; };
+  if (!current_state()) return kErrNotInitialised;
+  if (K < 1 || K > kMaxK) return fail(kErrInvalidArgument, name + ": K must be in 1..8");
+  if (is_bf16 != 0 && is_bf16 != 1) return fail(kErrInvalidArgument, name + ": is_bf16 must be 0 or 1");
+  if (mode != Patterns::kNone) {
+    const int rc = pack_patterns(who, patterns, n_patterns, mode == Patterns::kAny, packed);
+    if (rc != kOk) return rc;
+  }
+  if (total < 1 || W != (total + kHop - 1) / kHop)
+    return fail(kErrInvalidArgument, name + ": W must be ceil(total / 50) for a timeline of total >= 1 frames");
+  if (w0 < 0 || nw < 1 || w0 + nw > W || q0 < 0 || nq < 0)
+    return fail(kErrInvalidArgument, name + ": bad window or meta-frame range");
+  if (refine && (!cell_unit || !det_dir)) return fail(kErrInvalidArgument, name + ": null cell_unit or det_dir");
+  if (nq == 0) return kOk;
+  if (!logits || !meta_first || !meta_len || !det_cell || !det_score || !det_count)
+    return fail(kErrInvalidArgument, name + ": null pointer");
+  if (misaligned(logits) || (refine && misaligned(det_dir)) || (probs_out && misaligned(probs_out)))
+    return fail(kErrUnsupported, name + (refine ? ": logits, det_dir and probs_out must be 16-byte aligned"
+                                                : ": logits and probs_out must be 16-byte aligned"));
+  if (nq > 0x7fffffffLL) return fail(kErrUnsupported, name + ": too many meta-frames for one launch");
+  return kOk;
+}
+
+// One workgroup of kThreads per meta-frame; `kernel` is the instantiation the caller picked.
+template <class Kernel, class... Args>
+inline int launch_meta_frames(Kernel kernel, int64_t nq, void* stream, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nq)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), args...);
+  SELD_HIP_TRY(hipGetLastError());
+  return kOk;
 }
 
 }  // namespace eval

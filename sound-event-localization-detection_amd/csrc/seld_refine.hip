@@ -37,12 +37,6 @@ __global__ __launch_bounds__(kMatchThreads) void doa_match_dirs_kernel(
                     thr_deg, stats, cost);
 }
 
-template <bool kBf16, bool kTta, class... Args>
-void launch_refine(long nq, hipStream_t stream, Args... args) {
-  hipLaunchKernelGGL((refine_decode_kernel<kBf16, kTta>), dim3(static_cast<unsigned>(nq)), dim3(kThreads), 0, stream,
-                     args...);
-}
-
 }  // namespace eval
 }  // namespace seld
 
@@ -55,52 +49,17 @@ int seld_grid_decode_refine(const void* logits, int is_bf16, int64_t w0, int64_t
                             void* stream_) {
   using namespace seld;
   using namespace seld::eval;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (K < 1 || K > kMaxK) return fail(kErrInvalidArgument, "seld_grid_decode_refine: K must be in 1..8");
-  if (is_bf16 != 0 && is_bf16 != 1) return fail(kErrInvalidArgument, "seld_grid_decode_refine: is_bf16 must be 0 or 1");
-  if (n_patterns < 0 || n_patterns > kMaxPatterns)
-    return fail(kErrInvalidArgument, "seld_grid_decode_refine: n_patterns must be 0 (the plain walk) or in 1..16");
-  if ((n_patterns == 0) != (patterns == nullptr))
-    return fail(kErrInvalidArgument, "seld_grid_decode_refine: patterns must be NULL exactly when n_patterns is 0");
   uint64_t packed = 0;
-  unsigned seen = 0;
-  for (int n = 0; n < n_patterns; ++n) {
-    const int32_t p = patterns[n];
-    if (p < 0 || p >= kMaxPatterns) return fail(kErrInvalidArgument, "seld_grid_decode_refine: pattern outside 0..15");
-    if (seen & (1u << p)) return fail(kErrInvalidArgument, "seld_grid_decode_refine: duplicate pattern");
-    seen |= 1u << p;
-    packed |= static_cast<uint64_t>(p) << (4 * n);
-  }
-  if (total < 1 || W != (total + eval::kHop - 1) / eval::kHop)
-    return fail(kErrInvalidArgument,
-                "seld_grid_decode_refine: W must be ceil(total / 50) for a timeline of total >= 1 frames");
-  if (w0 < 0 || nw < 1 || w0 + nw > W || q0 < 0 || nq < 0)
-    return fail(kErrInvalidArgument, "seld_grid_decode_refine: bad window or meta-frame range");
-  if (!cell_unit || !det_dir) return fail(kErrInvalidArgument, "seld_grid_decode_refine: null cell_unit or det_dir");
-  if (nq == 0) return kOk;
-  if (!logits || !meta_first || !meta_len || !det_cell || !det_score || !det_count)
-    return fail(kErrInvalidArgument, "seld_grid_decode_refine: null pointer");
-  if ((reinterpret_cast<uintptr_t>(logits) & 15u) != 0 || (reinterpret_cast<uintptr_t>(det_dir) & 15u) != 0 ||
-      (probs_out && (reinterpret_cast<uintptr_t>(probs_out) & 15u) != 0))
-    return fail(kErrUnsupported, "seld_grid_decode_refine: logits, det_dir and probs_out must be 16-byte aligned");
-  if (nq > 0x7fffffffLL) return fail(kErrUnsupported, "seld_grid_decode_refine: too many meta-frames for one launch");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const auto* src = static_cast<const uint4*>(logits);
-  const long lw0 = static_cast<long>(w0), lnw = static_cast<long>(nw), lW = static_cast<long>(W);
-  const long ltotal = static_cast<long>(total), lq0 = static_cast<long>(q0), lnq = static_cast<long>(nq);
-  const int n_pat = n_patterns ? n_patterns : 1;
-#define SELD_REFINE_LAUNCH(BF16, TTA)                                                                                    \
-  launch_refine<BF16, TTA>(lnq, stream, src, lw0, lnw, lW, ltotal, meta_first, meta_len, lq0, packed, n_pat, threshold, \
-                           K, cell_unit, det_cell, det_score, det_count, det_dir, probs_out)
-  if (n_patterns) {
-    if (is_bf16) SELD_REFINE_LAUNCH(true, true); else SELD_REFINE_LAUNCH(false, true);
-  } else {
-    if (is_bf16) SELD_REFINE_LAUNCH(true, false); else SELD_REFINE_LAUNCH(false, false);
-  }
-#undef SELD_REFINE_LAUNCH
-  SELD_HIP_TRY(hipGetLastError());
-  return kOk;
+  const int rc = check_decode_args("seld_grid_decode_refine", logits, is_bf16, w0, nw, W, total, meta_first, meta_len, q0,
+                                   nq, Patterns::kAny, patterns, n_patterns, &packed, K, true, cell_unit, det_cell,
+                                   det_score, det_count, det_dir, probs_out);
+  if (rc != kOk || nq == 0) return rc;
+  const auto kernel = n_patterns ? (is_bf16 ? refine_decode_kernel<true, true> : refine_decode_kernel<false, true>)
+                                 : (is_bf16 ? refine_decode_kernel<true, false> : refine_decode_kernel<false, false>);
+  return launch_meta_frames(kernel, nq, stream_, static_cast<const uint4*>(logits), static_cast<long>(w0),
+                            static_cast<long>(nw), static_cast<long>(W), static_cast<long>(total), meta_first, meta_len,
+                            static_cast<long>(q0), packed, n_patterns ? n_patterns : 1, threshold, K, cell_unit, det_cell,
+                            det_score, det_count, det_dir, probs_out);
 }
 
 int seld_doa_match_dirs(const float* det_dir, const int32_t* det_count, int K, const int32_t* ref_offsets,
@@ -108,21 +67,13 @@ int seld_doa_match_dirs(const float* det_dir, const int32_t* det_count, int K, c
                         void* stream_) {
   using namespace seld;
   using namespace seld::eval;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (K < 1 || K > kMaxK) return fail(kErrInvalidArgument, "seld_doa_match_dirs: K must be in 1..8");
-  if (nq < 0) return fail(kErrInvalidArgument, "seld_doa_match_dirs: bad extents");
-  if (nq == 0) return kOk;
-  if (!det_dir || !det_count || !ref_offsets || !stats || !cost)
-    return fail(kErrInvalidArgument, "seld_doa_match_dirs: null pointer");
-  if ((reinterpret_cast<uintptr_t>(det_dir) & 7u) != 0)
-    return fail(kErrUnsupported, "seld_doa_match_dirs: det_dir must be 8-byte aligned");
-  const long n_qc = static_cast<long>(nq) * kC;
-  const long blocks = (n_qc + kMatchThreads - 1) / kMatchThreads;
-  if (blocks > 0x7fffffffL) return fail(kErrUnsupported, "seld_doa_match_dirs: too many meta-frames for one launch");
-  hipLaunchKernelGGL(doa_match_dirs_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kMatchThreads), 0,
-                     static_cast<hipStream_t>(stream_), det_dir, det_count, K, ref_offsets, ref_dirs, n_qc, thr_deg, stats,
-                     cost);
+  long n_qc = 0;
+  unsigned blocks = 0;
+  const int rc = check_match_args("seld_doa_match_dirs", nullptr, det_dir, K, nq, 1, 1, true,
+                                  {det_count, ref_offsets, stats, cost}, false, &n_qc, &blocks);
+  if (rc != kOk || nq == 0) return rc;
+  hipLaunchKernelGGL(doa_match_dirs_kernel, dim3(blocks), dim3(kMatchThreads), 0, static_cast<hipStream_t>(stream_),
+                     det_dir, det_count, K, ref_offsets, ref_dirs, n_qc, thr_deg, stats, cost);
   SELD_HIP_TRY(hipGetLastError());
   return kOk;
 }

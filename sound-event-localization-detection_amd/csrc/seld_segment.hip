@@ -2,7 +2,7 @@
 //
 // No reference counterpart; the definitions are this project's (section 18.1), after the DCASE 2022/23 segment-based metric.
 //   seld_doa_assign       per (q, c) the minimum-cost assignment ITSELF: match_entry's distances and dp (seld_match_core.h:
-//                         angle_deg and the kDirs switch are shared) plus a one-byte choice table and a backtrack
+//                         fill_distances and min_cost_assignment, shared) plus a one-byte choice table and a backtrack
 //   seld_segment_score    two launches: the counts of every (1 s block, class), then the blocks of a recording folded in
 //                         ascending order
 //   seld_jackknife_score  one lane per leave-one-recording-out replicate: micro and macro F / ER / LE / LR / SELD
@@ -23,77 +23,13 @@ constexpr int kJackThreads = 64;
 
 __device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
-// One lane's (q, c) entry of a workgroup of kMatchThreads lanes; the distances, the orientation (rows = the smaller side)
-// and the dp recurrence are match_entry's, statement for statement, so the assigned distances add up to its cost.
+// One lane per (q, c) (the body, next to match_entry: seld_match_core.h).
 template <bool kDirs>
 __global__ __launch_bounds__(kMatchThreads) void doa_assign_kernel(
     const int32_t* __restrict__ det_cell, const float2* __restrict__ det_dir, const int32_t* __restrict__ det_count, int K,
     const int32_t* __restrict__ ref_offsets, const int32_t* __restrict__ ref_dirs, long n_qc, int I, int J,
     double* __restrict__ pair_dist) {
-  __shared__ double dist[kMaxSide * kMaxSide][kMatchThreads];    // [row][col], lane-minor: no bank conflicts
-  __shared__ double dp[1 << kMaxSide][kMatchThreads];            // minimum cost per set of used columns
-  __shared__ uint8_t choice[1 << kMaxSide][kMatchThreads];       // the column that set dp[mask]
-  const int lane = threadIdx.x;
-  const long qc = static_cast<long>(blockIdx.x) * kMatchThreads + lane;
-  if (qc >= n_qc) return;                                         // (no barriers below)
-  double* out = pair_dist + qc * kMaxSide;
-#pragma unroll
-  for (int r = 0; r < kMaxSide; ++r) out[r] = quiet_nan();
-  const int r0 = ref_offsets[qc];
-  const int nr = ref_offsets[qc + 1] - r0;
-  const int np = det_count[qc];
-  if (nr < 0 || nr > kMaxSide || np < 0 || np > K) return;       // refused, as match_entry refuses it: all NaN
-  const bool refs_are_rows = nr <= np;
-  const int rows = refs_are_rows ? nr : np, cols = refs_are_rows ? np : nr;
-  [[maybe_unused]] const double cell_az = 360.0 / J, cell_el = 180.0 / I;
-  for (int r = 0; r < nr; ++r) {
-    const double raz = ref_dirs[2 * (r0 + r)], rel = ref_dirs[2 * (r0 + r) + 1];
-    for (int p = 0; p < np; ++p) {
-      double d;
-      if constexpr (kDirs) {
-        const float2 dir = det_dir[qc * K + p];
-        d = angle_deg(raz, rel, static_cast<double>(dir.x), static_cast<double>(dir.y));
-      } else {
-        const int cell = det_cell[qc * K + p];
-        const int ci = cell / J, cj = cell - ci * J;
-        d = angle_deg(raz, rel, -180.0 + (cj + 0.5) * cell_az, -90.0 + (ci + 0.5) * cell_el);
-      }
-      dist[refs_are_rows ? r * kMaxSide + p : p * kMaxSide + r][lane] = d;
-    }
-  }
-  const int k = rows;
-  if (k == 0) return;
-  const double inf = __longlong_as_double(0x7ff0000000000000LL);
-  double best = inf;
-  uint32_t best_mask = (1u << k) - 1u;                            // (kept when no candidate compares: NaN directions)
-  dp[0][lane] = 0.0;
-  for (uint32_t mask = 1; mask < (1u << cols); ++mask) {
-    const int pc = __popc(mask);
-    if (pc > k) continue;
-    const int r = pc - 1;
-    double v = inf;
-    int pick = __ffs(mask) - 1;                                   // (always a set bit, so the backtrack stays inside the mask)
-    for (int b = 0; b < cols; ++b) {
-      if (!((mask >> b) & 1u)) continue;
-      const double cand = dp[mask ^ (1u << b)][lane] + dist[r * kMaxSide + b][lane];
-      if (cand < v) {
-        v = cand;
-        pick = b;
-      }
-    }
-    dp[mask][lane] = v;
-    choice[mask][lane] = static_cast<uint8_t>(pick);
-    if (pc == k && v < best) {
-      best = v;
-      best_mask = mask;
-    }
-  }
-  uint32_t mask = best_mask;
-  for (int row = k - 1; row >= 0; --row) {
-    const int b = choice[mask][lane];
-    out[refs_are_rows ? row : b] = dist[row * kMaxSide + b][lane];
-    mask ^= 1u << b;
-  }
+  assign_entry<kDirs>(det_cell, det_dir, det_count, K, ref_offsets, ref_dirs, n_qc, I, J, pair_dist);
 }
 
 // Workgroup = recording s; its (block, class) pairs are dealt to the lanes.  Block x of the recording covers meta-frames
@@ -297,28 +233,14 @@ int seld_doa_assign(const int32_t* det_cell, const float* det_dir, const int32_t
                     double* pair_dist, void* stream_) {
   using namespace seld;
   using namespace seld::eval;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (K < 1 || K > kMaxK) return fail(kErrInvalidArgument, "seld_doa_assign: K must be in 1..8");
-  if (nq < 0 || (!det_dir && (I < 1 || J < 1)) || !(thr_deg >= 0.0))
-    return fail(kErrInvalidArgument, "seld_doa_assign: bad extents");
-  if ((!det_cell && !det_dir) || !det_count || !ref_offsets || !ref_dirs || !pair_dist)
-    return fail(kErrInvalidArgument, "seld_doa_assign: null pointer");
-  if (nq == 0) return kOk;
-  if (det_dir && (reinterpret_cast<uintptr_t>(det_dir) & 7u) != 0)
-    return fail(kErrUnsupported, "seld_doa_assign: det_dir must be 8-byte aligned");
-  const long n_qc = static_cast<long>(nq) * kC;
-  const long blocks = (n_qc + kMatchThreads - 1) / kMatchThreads;
-  if (blocks > 0x7fffffffL) return fail(kErrUnsupported, "seld_doa_assign: too many meta-frames for one launch");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (det_dir)
-    hipLaunchKernelGGL(doa_assign_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(kMatchThreads), 0, stream,
-                       det_cell, reinterpret_cast<const float2*>(det_dir), det_count, K, ref_offsets, ref_dirs, n_qc, 1, 1,
-                       pair_dist);
-  else
-    hipLaunchKernelGGL(doa_assign_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kMatchThreads), 0, stream,
-                       det_cell, reinterpret_cast<const float2*>(det_dir), det_count, K, ref_offsets, ref_dirs, n_qc, I, J,
-                       pair_dist);
+  long n_qc = 0;
+  unsigned blocks = 0;
+  const int rc = check_match_args("seld_doa_assign", det_cell, det_dir, K, nq, I, J, thr_deg >= 0.0,
+                                  {det_count, ref_offsets, ref_dirs, pair_dist}, true, &n_qc, &blocks);
+  if (rc != kOk || nq == 0) return rc;
+  hipLaunchKernelGGL(det_dir ? doa_assign_kernel<true> : doa_assign_kernel<false>, dim3(blocks), dim3(kMatchThreads), 0,
+                     static_cast<hipStream_t>(stream_), det_cell, reinterpret_cast<const float2*>(det_dir), det_count, K,
+                     ref_offsets, ref_dirs, n_qc, det_dir ? 1 : I, det_dir ? 1 : J, pair_dist);
   SELD_HIP_TRY(hipGetLastError());
   return kOk;
 }

@@ -105,25 +105,14 @@ int seld_doa_match_prefix(const int32_t* det_cell, const float* det_dir, const i
                           int32_t* ptp, double* pcost, void* stream_) {
   using namespace seld;
   using namespace seld::eval;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (K < 1 || K > kMaxK) return fail(kErrInvalidArgument, "seld_doa_match_prefix: K must be in 1..8");
-  if (nq < 0 || (!det_dir && (I < 1 || J < 1))) return fail(kErrInvalidArgument, "seld_doa_match_prefix: bad extents");
-  if (nq == 0) return kOk;
-  if ((!det_cell && !det_dir) || !det_count || !ref_offsets || !ptp || !pcost)
-    return fail(kErrInvalidArgument, "seld_doa_match_prefix: null pointer");
-  if (det_dir && (reinterpret_cast<uintptr_t>(det_dir) & 7u) != 0)
-    return fail(kErrUnsupported, "seld_doa_match_prefix: det_dir must be 8-byte aligned");
-  const long n_qc = static_cast<long>(nq) * kC;
-  const long blocks = (n_qc + kMatchThreads - 1) / kMatchThreads;
-  if (blocks > 0x7fffffffL) return fail(kErrUnsupported, "seld_doa_match_prefix: too many meta-frames for one launch");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (det_dir)
-    hipLaunchKernelGGL(doa_match_prefix_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(kMatchThreads), 0, stream,
-                       det_cell, det_dir, det_count, K, ref_offsets, ref_dirs, n_qc, 1, 1, thr_deg, ptp, pcost);
-  else
-    hipLaunchKernelGGL(doa_match_prefix_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kMatchThreads), 0, stream,
-                       det_cell, det_dir, det_count, K, ref_offsets, ref_dirs, n_qc, I, J, thr_deg, ptp, pcost);
+  long n_qc = 0;
+  unsigned blocks = 0;
+  const int rc = check_match_args("seld_doa_match_prefix", det_cell, det_dir, K, nq, I, J, true,
+                                  {det_count, ref_offsets, ptp, pcost}, false, &n_qc, &blocks);
+  if (rc != kOk || nq == 0) return rc;
+  hipLaunchKernelGGL(det_dir ? doa_match_prefix_kernel<true> : doa_match_prefix_kernel<false>, dim3(blocks),
+                     dim3(kMatchThreads), 0, static_cast<hipStream_t>(stream_), det_cell, det_dir, det_count, K,
+                     ref_offsets, ref_dirs, n_qc, det_dir ? 1 : I, det_dir ? 1 : J, thr_deg, ptp, pcost);
   SELD_HIP_TRY(hipGetLastError());
   return kOk;
 }

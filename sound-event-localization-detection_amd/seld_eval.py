@@ -44,6 +44,7 @@ from __future__ import annotations
 import ctypes
 import functools
 import math
+from collections import namedtuple
 from pathlib import Path
 
 import numpy as np
@@ -126,26 +127,30 @@ def meta_frame_table(segments, total=None) -> MetaFrameTable:
 
 # ------------------------------------------------------------------------------------------------------ kernels
 
-def grid_decode(logits: torch.Tensor, w0: int, table: MetaFrameTable, q0: int, nq: int, threshold: float, max_peaks: int,
-                out=None, probs: torch.Tensor | None = None):
-    """seld_grid_decode over meta-frames [q0, q0 + nq) from ``logits`` [nw, 250, 648, 14] (bf16 or fp32, GPU) holding
-    windows [w0, w0 + nw).  ``out``: contiguous (det_cell int32 [nq, 13, K], det_score f32 [nq, 13, K], det_count int32
-    [nq, 13]) to write, else allocated.  ``probs``: f32 [nq, 648, 13] to receive P_q, or None.
-    Raises SeldNativeError, launching nothing, when a window that covers one of the meta-frames is not in ``logits``."""
+def _grid_decode(name, logits, patterns, refine, w0, table, q0, nq, threshold, max_peaks, out, probs):
+    """The three decode wrappers: validation, the coverage check, the outputs and the one library call of the mode.
+    ``patterns`` None: the plain walk over logits [nw, 250, 648, 14]; else one stack per pattern, [P, nw, 250, 648, 14].
+    ``refine``: seld_grid_decode_refine (either walk) and a fourth output, det_dir; else seld_grid_decode[_tta]."""
+    stacked = patterns is not None
+    pats = np.asarray(list(patterns) if stacked else [], dtype=np.int32).reshape(-1)
     if not logits.is_cuda:
-        raise SeldNativeError("grid_decode: logits must live on the GPU (no CPU fallback)")
+        raise SeldNativeError(f"{name}: logits must live on the GPU (no CPU fallback)")
     if logits.dtype not in (torch.bfloat16, torch.float32):
-        raise TypeError("grid_decode: logits must be bfloat16 or float32")
-    if logits.dim() != 4 or tuple(logits.shape[1:]) != (WIN, GRID_I * GRID_J, NUM_EVENT_CLASSES + 1):
-        raise ValueError(f"grid_decode: logits must be [nw, {WIN}, 648, 14], got {tuple(logits.shape)}")
+        raise TypeError(f"{name}: logits must be bfloat16 or float32")
+    if logits.dim() != (5 if stacked else 4) or \
+            tuple(logits.shape[-3:]) != (WIN, GRID_I * GRID_J, NUM_EVENT_CLASSES + 1):
+        raise ValueError(f"{name}: logits must be {'[P, nw' if stacked else '[nw'}, {WIN}, 648, 14], got "
+                         f"{tuple(logits.shape)}")
+    if stacked and int(logits.shape[0]) != len(pats):
+        raise ValueError(f"{name}: {int(logits.shape[0])} stacks of logits for {len(pats)} patterns")
     logits = logits.contiguous()
-    nw = int(logits.shape[0])
+    nw = int(logits.shape[-4])
     if not (q0 >= 0 and nq >= 0 and q0 + nq <= len(table)):
-        raise ValueError("grid_decode: meta-frame range outside the table")
+        raise ValueError(f"{name}: meta-frame range outside the table")
     if nq:
         lo, hi = int(table.first_window[q0:q0 + nq].min()), int(table.last_window[q0:q0 + nq].max())
         if lo < w0 or hi >= w0 + nw:
-            raise SeldNativeError(f"grid_decode: meta-frames {q0}..{q0 + nq - 1} need windows {lo}..{hi}, the call "
+            raise SeldNativeError(f"{name}: meta-frames {q0}..{q0 + nq - 1} need windows {lo}..{hi}, the call "
                                   f"holds {w0}..{w0 + nw - 1}")
     device = logits.device
     index = ensure_init(device)
@@ -154,13 +159,33 @@ def grid_decode(logits: torch.Tensor, w0: int, table: MetaFrameTable, q0: int, n
         out = (torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.int32, device=device),
                torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.float32, device=device),
                torch.empty((nq, NUM_EVENT_CLASSES), dtype=torch.int32, device=device))
+        if refine:
+            out += (torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1), 2), dtype=torch.float32, device=device),)
     first, length = table.device(device)
+    lib = load_library()
+    head = (_p(logits), int(logits.dtype == torch.bfloat16), int(w0), nw, table.windows, table.total, _p(first),
+            _p(length), int(q0), int(nq))
+    pat = (pats.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if stacked else None, len(pats))
+    tail = (float(threshold), k) + ((_p(cell_unit_table(device)),) if refine else ()) + tuple(_p(t) for t in out) + \
+        (_p(probs), _stream_ptr(device))
     with _device_guard(index):
-        check(load_library().seld_grid_decode(_p(logits), int(logits.dtype == torch.bfloat16), int(w0), nw,
-                                              table.windows, table.total, _p(first), _p(length), int(q0), int(nq),
-                                              float(threshold), k, _p(out[0]), _p(out[1]), _p(out[2]), _p(probs),
-                                              _stream_ptr(device)), "seld_grid_decode")
+        if refine:
+            rc = lib.seld_grid_decode_refine(*head, *pat, *tail)
+        elif stacked:
+            rc = lib.seld_grid_decode_tta(*head, *pat, *tail)
+        else:
+            rc = lib.seld_grid_decode(*head, *tail)
+        check(rc, "seld_" + name)
     return out
+
+
+def grid_decode(logits: torch.Tensor, w0: int, table: MetaFrameTable, q0: int, nq: int, threshold: float, max_peaks: int,
+                out=None, probs: torch.Tensor | None = None):
+    """seld_grid_decode over meta-frames [q0, q0 + nq) from ``logits`` [nw, 250, 648, 14] (bf16 or fp32, GPU) holding
+    windows [w0, w0 + nw).  ``out``: contiguous (det_cell int32 [nq, 13, K], det_score f32 [nq, 13, K], det_count int32
+    [nq, 13]) to write, else allocated.  ``probs``: f32 [nq, 648, 13] to receive P_q, or None.
+    Raises SeldNativeError, launching nothing, when a window that covers one of the meta-frames is not in ``logits``."""
+    return _grid_decode("grid_decode", logits, None, False, w0, table, q0, nq, threshold, max_peaks, out, probs)
 
 
 def grid_decode_tta(logits: torch.Tensor, patterns, w0: int, table: MetaFrameTable, q0: int, nq: int, threshold: float,
@@ -169,61 +194,44 @@ def grid_decode_tta(logits: torch.Tensor, patterns, w0: int, table: MetaFrameTab
     [w0, w0 + nw) gathered with spatial pattern ``patterns[n]``; the stacks are averaged in the original frame
     (DESIGN.md section 13).  ``out`` / ``probs`` and the coverage check as ``grid_decode``; the pattern list itself is
     checked by the library (SeldNativeError)."""
-    if not logits.is_cuda:
-        raise SeldNativeError("grid_decode_tta: logits must live on the GPU (no CPU fallback)")
-    if logits.dtype not in (torch.bfloat16, torch.float32):
-        raise TypeError("grid_decode_tta: logits must be bfloat16 or float32")
-    if logits.dim() != 5 or tuple(logits.shape[2:]) != (WIN, GRID_I * GRID_J, NUM_EVENT_CLASSES + 1):
-        raise ValueError(f"grid_decode_tta: logits must be [P, nw, {WIN}, 648, 14], got {tuple(logits.shape)}")
-    pats = np.asarray(list(patterns), dtype=np.int32).reshape(-1)
-    if int(logits.shape[0]) != len(pats):
-        raise ValueError(f"grid_decode_tta: {int(logits.shape[0])} stacks of logits for {len(pats)} patterns")
-    logits = logits.contiguous()
-    nw = int(logits.shape[1])
-    if not (q0 >= 0 and nq >= 0 and q0 + nq <= len(table)):
-        raise ValueError("grid_decode_tta: meta-frame range outside the table")
-    if nq:
-        lo, hi = int(table.first_window[q0:q0 + nq].min()), int(table.last_window[q0:q0 + nq].max())
-        if lo < w0 or hi >= w0 + nw:
-            raise SeldNativeError(f"grid_decode_tta: meta-frames {q0}..{q0 + nq - 1} need windows {lo}..{hi}, the call "
-                                  f"holds {w0}..{w0 + nw - 1}")
-    device = logits.device
+    return _grid_decode("grid_decode_tta", logits, list(patterns), False, w0, table, q0, nq, threshold, max_peaks, out,
+                        probs)
+
+
+def _match_inputs(name, det_cell, det_dir, det_count, ref_offsets, ref_dirs):
+    """The prologue of the four matching wrappers.  The detections are ``det_dir`` f32 [Q, 13, K, 2] when given, else
+    ``det_cell`` int32 [Q, 13, K], with det_count [Q, 13] and ref_offsets of Q * 13 + 1 entries.  Returns (device index,
+    device, Q, K, det_cell or None, det_dir or None, det_count, ref_offsets, ref_dirs), the tensors cast and contiguous;
+    an empty ``ref_dirs`` is replaced by one row that nothing reads."""
+    dets, shape = (det_cell, "det_cell must be [Q, 13, K]") if det_dir is None else (det_dir, "det_dir must be [Q, 13, K, 2]")
+    if not (dets.is_cuda and det_count.is_cuda):
+        raise SeldNativeError(f"{name}: detections must live on the GPU (no CPU fallback)")
+    if dets.dim() != (3 if det_dir is None else 4) or dets.shape[1] != NUM_EVENT_CLASSES or \
+            (det_dir is not None and dets.shape[3] != 2) or tuple(det_count.shape) != tuple(dets.shape[:2]):
+        raise ValueError(f"{name}: {shape} and det_count [Q, 13]")
+    q, k, device = int(dets.shape[0]), int(dets.shape[2]), dets.device
+    if ref_offsets.numel() != q * NUM_EVENT_CLASSES + 1:
+        raise ValueError(f"{name}: ref_offsets must have Q * 13 + 1 entries")
     index = ensure_init(device)
-    k = int(max_peaks)
-    if out is None:
-        out = (torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.int32, device=device),
-               torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.float32, device=device),
-               torch.empty((nq, NUM_EVENT_CLASSES), dtype=torch.int32, device=device))
-    first, length = table.device(device)
-    with _device_guard(index):
-        check(load_library().seld_grid_decode_tta(_p(logits), int(logits.dtype == torch.bfloat16), int(w0), nw,
-                                                  table.windows, table.total, _p(first), _p(length), int(q0), int(nq),
-                                                  pats.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(pats),
-                                                  float(threshold), k, _p(out[0]), _p(out[1]), _p(out[2]), _p(probs),
-                                                  _stream_ptr(device)), "seld_grid_decode_tta")
-    return out
+    dirs = ref_dirs if ref_dirs.numel() else torch.zeros((1, 2), dtype=torch.int32, device=device)
+    dets = dets.to(torch.int32 if det_dir is None else torch.float32).contiguous()
+    return (index, device, q, k, dets if det_dir is None else None, None if det_dir is None else dets,
+            det_count.to(torch.int32).contiguous(), ref_offsets.to(torch.int32).contiguous(),
+            dirs.to(torch.int32).contiguous())
 
 
 def doa_match(det_cell: torch.Tensor, det_count: torch.Tensor, ref_offsets: torch.Tensor, ref_dirs: torch.Tensor,
               doa_threshold_deg: float, I: int = GRID_I, J: int = GRID_J):
     """seld_doa_match: (stats int32 [Q, 13, 4] = (R, P, k, tp), cost f64 [Q, 13]) on the detections' device.  A pair is
     within the threshold when d <= doa_threshold_deg + DOA_MARGIN_DEG."""
-    device = det_cell.device
-    if not det_cell.is_cuda:
-        raise SeldNativeError("doa_match: detections must live on the GPU (no CPU fallback)")
-    q = int(det_count.shape[0])
-    if ref_offsets.numel() != q * NUM_EVENT_CLASSES + 1:
-        raise ValueError("doa_match: ref_offsets must have Q * 13 + 1 entries")
-    index = ensure_init(device)
+    index, device, q, k, det_cell, _, det_count, ref_offsets, dirs = _match_inputs("doa_match", det_cell, None, det_count,
+                                                                                   ref_offsets, ref_dirs)
     stats = torch.empty((q, NUM_EVENT_CLASSES, 4), dtype=torch.int32, device=device)
     cost = torch.empty((q, NUM_EVENT_CLASSES), dtype=torch.float64, device=device)
-    dirs = ref_dirs if ref_dirs.numel() else torch.zeros((1, 2), dtype=torch.int32, device=device)
-    det_cell, det_count = det_cell.contiguous(), det_count.contiguous()
-    ref_offsets, dirs = ref_offsets.to(torch.int32).contiguous(), dirs.to(torch.int32).contiguous()
     with _device_guard(index):
-        check(load_library().seld_doa_match(_p(det_cell), _p(det_count), int(det_cell.shape[-1]), _p(ref_offsets),
-                                            _p(dirs), q, int(I), int(J), float(doa_threshold_deg) + DOA_MARGIN_DEG,
-                                            _p(stats), _p(cost), _stream_ptr(device)), "seld_doa_match")
+        check(load_library().seld_doa_match(_p(det_cell), _p(det_count), k, _p(ref_offsets), _p(dirs), q, int(I), int(J),
+                                            float(doa_threshold_deg) + DOA_MARGIN_DEG, _p(stats), _p(cost),
+                                            _stream_ptr(device)), "seld_doa_match")
     return stats, cost
 
 
@@ -253,69 +261,23 @@ def grid_decode_refine(logits: torch.Tensor, w0: int, table: MetaFrameTable, q0:
     ``grid_decode_tta`` (logits [P, nw, 250, 648, 14]) that also writes every detection's sub-cell direction (DESIGN.md
     section 15).  ``out``: contiguous (det_cell, det_score, det_count, det_dir f32 [nq, 13, K, 2] = (az, el) degrees, 0
     past the count) to write, else allocated; the first three and ``probs`` are the un-refined call's bit for bit."""
-    pats = np.asarray(list(patterns) if patterns is not None else [], dtype=np.int32).reshape(-1)
-    tta = len(pats) > 0
-    if not logits.is_cuda:
-        raise SeldNativeError("grid_decode_refine: logits must live on the GPU (no CPU fallback)")
-    if logits.dtype not in (torch.bfloat16, torch.float32):
-        raise TypeError("grid_decode_refine: logits must be bfloat16 or float32")
-    rows = (WIN, GRID_I * GRID_J, NUM_EVENT_CLASSES + 1)
-    if logits.dim() != (5 if tta else 4) or tuple(logits.shape[-3:]) != rows:
-        raise ValueError(f"grid_decode_refine: logits must be {'[P, nw' if tta else '[nw'}, {WIN}, 648, 14], got "
-                         f"{tuple(logits.shape)}")
-    if tta and int(logits.shape[0]) != len(pats):
-        raise ValueError(f"grid_decode_refine: {int(logits.shape[0])} stacks of logits for {len(pats)} patterns")
-    logits = logits.contiguous()
-    nw = int(logits.shape[-4])
-    if not (q0 >= 0 and nq >= 0 and q0 + nq <= len(table)):
-        raise ValueError("grid_decode_refine: meta-frame range outside the table")
-    if nq:
-        lo, hi = int(table.first_window[q0:q0 + nq].min()), int(table.last_window[q0:q0 + nq].max())
-        if lo < w0 or hi >= w0 + nw:
-            raise SeldNativeError(f"grid_decode_refine: meta-frames {q0}..{q0 + nq - 1} need windows {lo}..{hi}, the call "
-                                  f"holds {w0}..{w0 + nw - 1}")
-    device = logits.device
-    index = ensure_init(device)
-    k = int(max_peaks)
-    if out is None:
-        out = (torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.int32, device=device),
-               torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1)), dtype=torch.float32, device=device),
-               torch.empty((nq, NUM_EVENT_CLASSES), dtype=torch.int32, device=device),
-               torch.empty((nq, NUM_EVENT_CLASSES, max(k, 1), 2), dtype=torch.float32, device=device))
-    first, length = table.device(device)
-    unit = cell_unit_table(device)
-    with _device_guard(index):
-        check(load_library().seld_grid_decode_refine(
-            _p(logits), int(logits.dtype == torch.bfloat16), int(w0), nw, table.windows, table.total, _p(first),
-            _p(length), int(q0), int(nq), pats.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if tta else None,
-            len(pats), float(threshold), k, _p(unit), _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _p(probs),
-            _stream_ptr(device)), "seld_grid_decode_refine")
-    return out
+    patterns = list(patterns) if patterns is not None else []
+    return _grid_decode("grid_decode_refine", logits, patterns or None, True, w0, table, q0, nq, threshold, max_peaks, out,
+                        probs)
 
 
 def doa_match_dirs(det_dir: torch.Tensor, det_count: torch.Tensor, ref_offsets: torch.Tensor, ref_dirs: torch.Tensor,
                    doa_threshold_deg: float):
     """seld_doa_match_dirs: ``doa_match`` with the detections' directions det_dir f32 [Q, 13, K, 2] = (az, el) degrees in
     place of their cells."""
-    device = det_dir.device
-    if not det_dir.is_cuda:
-        raise SeldNativeError("doa_match_dirs: detections must live on the GPU (no CPU fallback)")
-    if det_dir.dim() != 4 or det_dir.shape[1] != NUM_EVENT_CLASSES or det_dir.shape[3] != 2 or \
-            tuple(det_count.shape) != tuple(det_dir.shape[:2]):
-        raise ValueError("doa_match_dirs: det_dir must be [Q, 13, K, 2] and det_count [Q, 13]")
-    q = int(det_count.shape[0])
-    if ref_offsets.numel() != q * NUM_EVENT_CLASSES + 1:
-        raise ValueError("doa_match_dirs: ref_offsets must have Q * 13 + 1 entries")
-    index = ensure_init(device)
+    index, device, q, k, _, det_dir, det_count, ref_offsets, dirs = _match_inputs("doa_match_dirs", None, det_dir,
+                                                                                  det_count, ref_offsets, ref_dirs)
     stats = torch.empty((q, NUM_EVENT_CLASSES, 4), dtype=torch.int32, device=device)
     cost = torch.empty((q, NUM_EVENT_CLASSES), dtype=torch.float64, device=device)
-    dirs = ref_dirs if ref_dirs.numel() else torch.zeros((1, 2), dtype=torch.int32, device=device)
-    det_dir, det_count = det_dir.to(torch.float32).contiguous(), det_count.to(torch.int32).contiguous()
-    ref_offsets, dirs = ref_offsets.to(torch.int32).contiguous(), dirs.to(torch.int32).contiguous()
     with _device_guard(index):
-        check(load_library().seld_doa_match_dirs(_p(det_dir), _p(det_count), int(det_dir.shape[2]), _p(ref_offsets),
-                                                 _p(dirs), q, float(doa_threshold_deg) + DOA_MARGIN_DEG, _p(stats),
-                                                 _p(cost), _stream_ptr(device)), "seld_doa_match_dirs")
+        check(load_library().seld_doa_match_dirs(_p(det_dir), _p(det_count), k, _p(ref_offsets), _p(dirs), q,
+                                                 float(doa_threshold_deg) + DOA_MARGIN_DEG, _p(stats), _p(cost),
+                                                 _stream_ptr(device)), "seld_doa_match_dirs")
     return stats, cost
 
 
@@ -699,26 +661,10 @@ def doa_match_prefix(det_cell: torch.Tensor, det_count: torch.Tensor, ref_offset
     """seld_doa_match_prefix: (ptp int32 [Q, 13, K + 1], pcost f64 [Q, 13, K + 1]); entry p is the tp and cost of
     ``doa_match`` (``doa_match_dirs`` given ``det_dir`` f32 [Q, 13, K, 2]) with the entry's count replaced by p, entries
     past the count repeat the one at the count."""
-    device = det_count.device
-    if not det_count.is_cuda:
-        raise SeldNativeError("doa_match_prefix: detections must live on the GPU (no CPU fallback)")
-    q = int(det_count.shape[0])
-    if det_dir is not None:
-        if det_dir.dim() != 4 or det_dir.shape[1] != NUM_EVENT_CLASSES or det_dir.shape[3] != 2 or \
-                tuple(det_count.shape) != tuple(det_dir.shape[:2]):
-            raise ValueError("doa_match_prefix: det_dir must be [Q, 13, K, 2] and det_count [Q, 13]")
-        det_dir, k = det_dir.to(torch.float32).contiguous(), int(det_dir.shape[2])
-        det_cell = None
-    else:
-        det_cell, k = det_cell.to(torch.int32).contiguous(), int(det_cell.shape[-1])
-    if ref_offsets.numel() != q * NUM_EVENT_CLASSES + 1:
-        raise ValueError("doa_match_prefix: ref_offsets must have Q * 13 + 1 entries")
-    index = ensure_init(device)
+    index, device, q, k, det_cell, det_dir, det_count, ref_offsets, dirs = _match_inputs(
+        "doa_match_prefix", det_cell, det_dir, det_count, ref_offsets, ref_dirs)
     ptp = torch.empty((q, NUM_EVENT_CLASSES, k + 1), dtype=torch.int32, device=device)
     pcost = torch.empty((q, NUM_EVENT_CLASSES, k + 1), dtype=torch.float64, device=device)
-    dirs = ref_dirs if ref_dirs.numel() else torch.zeros((1, 2), dtype=torch.int32, device=device)
-    det_count = det_count.to(torch.int32).contiguous()
-    ref_offsets, dirs = ref_offsets.to(torch.int32).contiguous(), dirs.to(torch.int32).contiguous()
     with _device_guard(index):
         check(load_library().seld_doa_match_prefix(_p(det_cell), _p(det_dir), _p(det_count), k, _p(ref_offsets), _p(dirs),
                                                    q, int(I), int(J), float(doa_threshold_deg) + DOA_MARGIN_DEG, _p(ptp),
@@ -919,25 +865,9 @@ def doa_assign(det_cell: torch.Tensor, det_count: torch.Tensor, ref_offsets: tor
     """seld_doa_assign: pair_dist f64 [Q, 13, 8]; slot r of (q, c) is the distance of its reference r to the detection the
     minimum-cost assignment of ``doa_match`` (``doa_match_dirs`` given ``det_dir`` f32 [Q, 13, K, 2]) gives it, NaN when
     the reference is unassigned, absent or the entry refused."""
-    device = det_count.device
-    if not det_count.is_cuda:
-        raise SeldNativeError("doa_assign: detections must live on the GPU (no CPU fallback)")
-    q = int(det_count.shape[0])
-    if det_dir is not None:
-        if det_dir.dim() != 4 or det_dir.shape[1] != NUM_EVENT_CLASSES or det_dir.shape[3] != 2 or \
-                tuple(det_count.shape) != tuple(det_dir.shape[:2]):
-            raise ValueError("doa_assign: det_dir must be [Q, 13, K, 2] and det_count [Q, 13]")
-        det_dir, k = det_dir.to(torch.float32).contiguous(), int(det_dir.shape[2])
-        det_cell = None
-    else:
-        det_cell, k = det_cell.to(torch.int32).contiguous(), int(det_cell.shape[-1])
-    if ref_offsets.numel() != q * NUM_EVENT_CLASSES + 1:
-        raise ValueError("doa_assign: ref_offsets must have Q * 13 + 1 entries")
-    index = ensure_init(device)
+    index, device, q, k, det_cell, det_dir, det_count, ref_offsets, dirs = _match_inputs(
+        "doa_assign", det_cell, det_dir, det_count, ref_offsets, ref_dirs)
     pair_dist = torch.empty((q, NUM_EVENT_CLASSES, MAX_REFS), dtype=torch.float64, device=device)
-    dirs = ref_dirs if ref_dirs.numel() else torch.zeros((1, 2), dtype=torch.int32, device=device)
-    det_count = det_count.to(torch.int32).contiguous()
-    ref_offsets, dirs = ref_offsets.to(torch.int32).contiguous(), dirs.to(torch.int32).contiguous()
     with _device_guard(index):
         check(load_library().seld_doa_assign(_p(det_cell), _p(det_dir), _p(det_count), k, _p(ref_offsets), _p(dirs), q,
                                              int(I), int(J), float(doa_threshold_deg) + DOA_MARGIN_DEG, _p(pair_dist),
@@ -1187,6 +1117,10 @@ def segment_names(dataset):
 
 # ------------------------------------------------------------------------------------------------------ entry point
 
+# the detections of a timeline as evaluate_logits hands them on; dir (the refined directions) is None without refine
+Detections = namedtuple("Detections", "cell score count dir", defaults=(None,))
+
+
 def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_threshold_deg=None, events_dir=None,
                     names=None, patterns=None, track=None, refine=None, sweep=None, class_thresholds=None,
                     thresholds_out=None, segment=None, jackknife=None) -> dict:
@@ -1250,13 +1184,16 @@ def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_thresh
                                   f"{dataset.I} x {dataset.J}")
     table = meta_frame_table(dataset.segments, dataset.total_frames)
     decoded = decode(batches, table, decode_threshold, max_peaks, device=dataset.device, patterns=patterns, refine=refine)
-    low = (decoded[0], decoded[1], decoded[2]) + ((decoded[4],) if refine else ())      # as decoded, at decode_threshold
+    low = Detections(decoded[0], decoded[1], decoded[2], decoded[4] if refine else None)    # at decode_threshold
     settings = tracking
-    refs = device_references(table, dataset.metadata_rows, low[0].device) if swept or segment else None
+    refs = device_references(table, dataset.metadata_rows, low.cell.device) if swept or segment else None
+
+    def cut_to(thresholds):
+        return Detections(*apply_thresholds(low.cell, low.score, low.count, thresholds, low.dir))
 
     def link_and_score(dets):
-        """Detections (cell, score, count[, dir]) -> (record, cell, ids, count, dir, linked, tracking)."""
-        cell, count, dirs = dets[0], dets[2], dets[3] if refine else None
+        """Detections -> (record, cell, ids, count, dir, linked, tracking)."""
+        cell, count, dirs = dets.cell, dets.count, dets.dir
         ids = linked = None
         summary = settings
         if settings is not None:
@@ -1270,23 +1207,20 @@ def evaluate_logits(batches, dataset, threshold=None, max_peaks=None, doa_thresh
                                  det_dir=dirs, refine=refine, refs=refs)
         return record, cell, ids, count, dirs, linked, summary
 
-    result, det_cell, ids, det_count, det_dir, linked, tracking = link_and_score(
-        low if cut is None else apply_thresholds(low[0], low[1], low[2], cut, low[3] if refine else None))
+    result, det_cell, ids, det_count, det_dir, linked, tracking = link_and_score(low if cut is None else cut_to(cut))
     result.update(threshold=float(threshold), max_peaks=int(max_peaks), doa_threshold_deg=float(doa_threshold_deg),
                   tta_patterns=list(patterns), tracking=tracking, refine=refine)
     if per_class is not None:
         result["class_thresholds"] = list(per_class)
     if segment:
         result["segment"] = segment_metrics(det_cell, det_count, table, dataset.metadata_rows, doa_threshold_deg,
-                                            dataset.I, dataset.J, det_dir=det_dir if refine else None, refs=refs,
-                                            jackknife=jackknife)
+                                            dataset.I, dataset.J, det_dir=det_dir, refs=refs, jackknife=jackknife)
     if swept:
         if settings is None:
-            result["sweep"] = _sweep(low[0], low[1], low[2], table, dataset.metadata_rows, swept, doa_threshold_deg,
-                                     dataset.I, dataset.J, det_dir=low[3] if refine else None, refs=refs)
+            result["sweep"] = _sweep(low.cell, low.score, low.count, table, dataset.metadata_rows, swept,
+                                     doa_threshold_deg, dataset.I, dataset.J, det_dir=low.dir, refs=refs)
         else:
-            rows = [link_and_score(apply_thresholds(low[0], low[1], low[2], [t] * NUM_EVENT_CLASSES,
-                                                    low[3] if refine else None))[0] for t in swept]
+            rows = [link_and_score(cut_to([t] * NUM_EVENT_CLASSES))[0] for t in swept]
             result["sweep"] = _sweep_result(swept, rows)
         if thresholds_out is not None:
             result["thresholds_file"] = str(write_thresholds(thresholds_out, result["sweep"], max_peaks, doa_threshold_deg,

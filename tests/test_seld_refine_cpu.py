@@ -161,21 +161,9 @@ def test_track_dirs_maps_cells_to_directions():
 def test_refine_kernels_do_not_spill():
     """The compiler's own resource report of the refined decode (four instantiations) and the direction matcher shows no
     scratch -- the way test_eval_kernels_do_not_spill checks their parents."""
-    import re
-    import subprocess
     from pathlib import Path
+    import hip_resources
     csrc = Path(__file__).resolve().parent.parent / "sound-event-localization-detection_amd" / "csrc"
-    run = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
-                          f"-I{csrc.parent.parent / 'include'}", "-Rpass-analysis=kernel-resource-usage", "-c",
-                          str(csrc / "seld_refine.hip"), "-o", "/dev/null"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-2000:]
-    found, current = {}, None
-    for line in run.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            current = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and current:
-            found[current] = int(m.group(1))
+    found = {k: v["scratch"] for k, v in hip_resources.report(csrc / "seld_refine.hip").items()}
     assert len([k for k in found if "refine_decode_kernel" in k]) == 4 and any("doa_match_dirs_kernel" in k for k in found)
     assert all(v == 0 for v in found.values()), found

@@ -4,7 +4,6 @@ seld_eval (jackknife, student_t_975, block_table, the switches and their argumen
 binding and library, and the compiler's resource report of the new kernels."""
 import math
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -265,18 +264,8 @@ def test_header_binding_and_library_agree_on_the_segment_exports():
 def test_segment_kernels_do_not_spill():
     """The compiler's own resource report of the five kernels (both assignment instantiations, the block and fold launches
     of the segment score, the jackknife) shows no scratch."""
-    run = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
-                          f"-I{ROOT / 'include'}", "-Rpass-analysis=kernel-resource-usage", "-c",
-                          str(CSRC / "seld_segment.hip"), "-o", "/dev/null"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-2000:]
-    found, current = {}, None
-    for line in run.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            current = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and current:
-            found[current] = int(m.group(1))
+    import hip_resources
+    found = {k: v["scratch"] for k, v in hip_resources.report(CSRC / "seld_segment.hip").items()}
     assert len([k for k in found if "doa_assign_kernel" in k]) == 2
     for kernel in ("segment_blocks_kernel", "segment_fold_kernel", "jackknife_kernel"):
         assert any(kernel in k for k in found), (kernel, found)

@@ -4,7 +4,6 @@ rounding, apply_thresholds -- framework ops, so it runs here), and the compiler'
 import json
 import math
 import re
-import subprocess
 import warnings
 from pathlib import Path
 
@@ -276,18 +275,8 @@ def test_evaluate_seld_takes_the_sweep_arguments():
 def test_sweep_kernels_do_not_spill():
     """The compiler's own resource report of the sweep kernels (both prefix instantiations and the score kernel) shows
     no scratch."""
-    run = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
-                          f"-I{ROOT / 'include'}", "-Rpass-analysis=kernel-resource-usage", "-c",
-                          str(CSRC / "seld_sweep.hip"), "-o", "/dev/null"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-2000:]
-    found, current = {}, None
-    for line in run.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            current = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and current:
-            found[current] = int(m.group(1))
+    import hip_resources
+    found = {k: v["scratch"] for k, v in hip_resources.report(CSRC / "seld_sweep.hip").items()}
     assert len([k for k in found if "doa_match_prefix_kernel" in k]) == 2 and any("sweep_score_kernel" in k for k in found)
     assert all(v == 0 for v in found.values()), found
 

@@ -1,8 +1,6 @@
 """CPU checks of test-time augmentation in the SELD evaluation: the pattern-list parser and the
 parameter rows, the float64 restatement (tests/seld_tta_ref.py) on exact permuted copies, the planted cases the GPU test
 uses, the compiler's resource report of csrc/seld_tta.hip, and the refusal to run without a device timeline."""
-import re
-import subprocess
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -84,25 +82,8 @@ def test_planted_cases_have_few_near_ties(name):
 def test_tta_kernels_do_not_spill():
     """The compiler's own resource report of csrc/seld_tta.hip: both instantiations without scratch and with no more LDS
     than the plain decode kernels of csrc/seld_eval.hip (one staged row)."""
-    def report(name):
-        run = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
-                              f"-I{CSRC.parent.parent / 'include'}", "-Rpass-analysis=kernel-resource-usage", "-c",
-                              str(CSRC / name), "-o", "/dev/null"], capture_output=True, text=True)
-        assert run.returncode == 0, run.stderr[-2000:]
-        found, current = {}, None
-        for line in run.stderr.splitlines():
-            m = re.search(r"Function Name: (\S+)", line)
-            if m:
-                current = m.group(1)
-                found[current] = {}
-            for key, pattern in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"),
-                                 ("vgprs", r" VGPRs: (\d+)")):
-                m = re.search(pattern, line)
-                if m and current:
-                    found[current][key] = int(m.group(1))
-        return found
-
-    got, plain = report("seld_tta.hip"), report("seld_eval.hip")
+    from hip_resources import report
+    got, plain = report(CSRC / "seld_tta.hip"), report(CSRC / "seld_eval.hip")
     print(got)
     kernels = {k: v for k, v in got.items() if "tta_decode_kernel" in k}
     assert len(kernels) == 2 and len(got) == 2, sorted(got)
