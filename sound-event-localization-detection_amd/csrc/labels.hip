@@ -9,7 +9,7 @@
 // "class c active in this cell" (the reference's labels[t, cell, c] = 1.0, dataset.py:110).
 // The background one-hot (dataset.py:114-117) is implied by mask == 0 and materialised only
 // by seld_labels_expand (or consumed directly by the fused loss): 2 B per cell instead of 56 B.
-#include "seld_common.h"
+#include "augment_core.h"   // check_window_args
 
 namespace seld {
 
@@ -198,13 +198,11 @@ int seld_labels_expand(const uint16_t* mask, int64_t n_cells, int num_classes, f
 int seld_window_gather(const void* src, int64_t total_rows, int64_t row_bytes, const int64_t* starts, int64_t B,
                        int64_t window, void* dst, void* stream_) {
   using namespace seld;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (total_rows < 0 || row_bytes <= 0 || B < 0 || window <= 0)
-    return fail(kErrInvalidArgument, "seld_window_gather: bad extents");
-  if (row_bytes % 16 != 0) return fail(kErrUnsupported, "seld_window_gather: row_bytes must be a multiple of 16");
-  if (B == 0) return kOk;
-  if (!src || !starts || !dst) return fail(kErrInvalidArgument, "seld_window_gather: null pointer");
+  DeviceState* st;
+  const int rc = check_window_args("seld_window_gather", total_rows, B, window, row_bytes > 0,
+                                   {{row_bytes % 16 != 0, kErrUnsupported, "row_bytes must be a multiple of 16"}}, 0,
+                                   {src, starts, dst}, &st);
+  if (rc != kOk || B == 0) return rc;
   const long chunks = row_bytes / 16;
   const unsigned blocks = grid_for(B * window * chunks, 256, st->num_cus);
   hipLaunchKernelGGL(gather_rows_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_),

@@ -4,8 +4,9 @@
 // augment.hip gives a window one of the 16 sign-and-swap transforms: mirror m, k quarter turns, elevation flip e.  Here slot
 // [9] of the same parameter row is an azimuth step r, and the window's transform is
 //     mirror m,  then  s = (k J/4 + r) mod J  cells of azimuth  (phi = 2 pi s / J),  then  elevation flip e.
-// The labels stay an exact cell permutation (a cyclic shift of the azimuth index by s).  The features do not stay a channel
-// permutation: with c = cos phi, sn = sin phi and sigma = -1 after a mirror (else +1)
+// The labels stay an exact cell permutation (a cyclic shift of the azimuth index by s): permute_mask_kernel<true> of
+// augment.hip, behind seld_window_permute_mask_rotate.  The features do not stay a channel permutation: with c = cos phi,
+// sn = sin phi and sigma = -1 after a mirror (else +1)
 //     X' = c X - sn sigma Y,    Y' = sn X + c sigma Y,
 // and log-mel(X') is no function of the stored log-mel channels.  The mel filterbank acts on POWERS, so three more mel rows
 // per frame of the timeline -- P_X = mel |X|^2, P_Y = mel |Y|^2, C = mel Re(X conj Y), linear fp32, written once per
@@ -113,10 +114,7 @@ __global__ __launch_bounds__(kRtWaves * 64) void rotation_terms_kernel(RotTermAr
 }
 
 // ---------------------------------------------------------------------------------------- the rotating gathers
-// All three travel BY VALUE (kernel argument memory).
-struct alignas(8) ChannelTable8 {                     // (source channel | 0x80 when negated) per pattern: 4 or 7 channels
-  uint8_t e[kPatterns][8];
-};
+// Both travel BY VALUE (kernel argument memory), as the channel table (ChannelTable8 of augment_core.h) does.
 struct RotationTable {                                // (cos, sin) of 2 pi s / J
   float cs[kMaxSteps][2];
 };
@@ -124,34 +122,6 @@ struct UnitTable {                                    // byte n: the output chan
   unsigned long long first, second;
   int slots;
 };
-
-// row[9] reduced to 0..J-1 whatever it holds
-__device__ __forceinline__ int azimuth_step(const int32_t* __restrict__ params, long b, int J) {
-  const int r = params[b * kParamInts + 9] % J;
-  return r < 0 ? r + J : r;
-}
-
-__device__ __forceinline__ uint4 signed_copy(const uint4* __restrict__ row, unsigned long long packed, unsigned c, int fc) {
-  const unsigned entry = static_cast<unsigned>(packed >> (8 * c)) & 0xffu;
-  const unsigned flip = (entry & 0x80u) << 24;                      // sign bit
-  uint4 v = row[(entry & 0x7fu) * kChunksPerChannel + fc];          // host: source channel < channels
-  v.x ^= flip; v.y ^= flip; v.z ^= flip; v.w ^= flip;
-  return v;
-}
-
-// the time / frequency masks of augment.hip on one 16-byte chunk of output channel c
-__device__ __forceinline__ uint4 masked(uint4 v, int w, int c, int fc, const WindowParams& prm, int freq_channels,
-                                        unsigned mask_bits) {
-  if (in_span(w, prm.t0, prm.tl0) || in_span(w, prm.t1, prm.tl1)) return make_uint4(mask_bits, mask_bits, mask_bits, mask_bits);
-  if (c < freq_channels) {
-    const int f = fc * 4;
-    if (in_span(f + 0, prm.f0, prm.fl0) || in_span(f + 0, prm.f1, prm.fl1)) v.x = mask_bits;
-    if (in_span(f + 1, prm.f0, prm.fl0) || in_span(f + 1, prm.f1, prm.fl1)) v.y = mask_bits;
-    if (in_span(f + 2, prm.f0, prm.fl0) || in_span(f + 2, prm.f1, prm.fl1)) v.z = mask_bits;
-    if (in_span(f + 3, prm.f0, prm.fl0) || in_span(f + 3, prm.f1, prm.fl1)) v.w = mask_bits;
-  }
-  return v;
-}
 
 // power_to_db(a P_X + b P_Y + g): g is the rounded cross term; four roundings on the longest chain (coefficient, cross
 // product, two fused multiply-adds)
@@ -193,8 +163,8 @@ gather_rotate_kernel(const uint4* __restrict__ src, const uint4* __restrict__ ro
       if (srow >= 0 && srow < total_rows) {
         const uint4* __restrict__ row = src + srow * row_chunks;
         if (copy || !pair) {
-          va = signed_copy(row, packed, ca, fc);
-          if (pair) vb = signed_copy(row, packed, cb, fc);
+          va = signed_copy(row, packed_entry(packed, ca), fc);
+          if (pair) vb = signed_copy(row, packed_entry(packed, cb), fc);
         } else if (ca < 4) {                                        // X' and Y' log-mel from the three rotation terms
           const uint4* __restrict__ terms = rot + srow * kRotRowChunks + fc;
           const uint4 px = terms[0], py = terms[kChunksPerChannel], cx = terms[2 * kChunksPerChannel];
@@ -223,54 +193,6 @@ gather_rotate_kernel(const uint4* __restrict__ src, const uint4* __restrict__ ro
       uint4* __restrict__ out = to + w * row_chunks + fc;
       out[ca * kChunksPerChannel] = va;
       if (pair) out[cb * kChunksPerChannel] = vb;
-    }
-  }
-}
-
-// permute_mask_kernel of augment.hip with the azimuth shift s = (k J/4 + r) mod J: a set cell (i, j) moves to
-//   i' = e ? I-1-i : i,   j' = ((m ? J-1-j : j) + s) mod J.
-// Each thread builds 8 consecutive destination cells (one 16-byte store); the identity (and any transform on a row past the
-// timeline) keeps the 16-byte load of the plain gather.
-__global__ void __launch_bounds__(256)
-permute_mask_rotate_kernel(const uint16_t* __restrict__ src, long total_rows, int I, int J, const int64_t* __restrict__ starts,
-                           const int32_t* __restrict__ params, long B, int window, uint4* __restrict__ dst) {
-  const int cells = I * J;
-  const int row_chunks = cells / 8;
-  const int per_window = window * row_chunks;                       // host: < 2^31
-  const int quarter = J / 4;
-  for (long b = blockIdx.y; b < B; b += gridDim.y) {
-    const int p = params[b * kParamInts] & (kPatterns - 1);
-    const bool mirror = (p >> 3) != 0, flip = (p & 1) != 0;
-    const int shift = (((p >> 1) & 3) * quarter + azimuth_step(params, b, J)) % J;
-    const bool identity = !mirror && !flip && shift == 0;
-    const long start = starts[b];
-    uint4* __restrict__ to = dst + b * static_cast<long>(per_window);
-    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per_window; q += gridDim.x * blockDim.x) {
-      const int w = q / row_chunks;
-      const int chunk = q - w * row_chunks;
-      const long srow = start + w;
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (srow >= 0 && srow < total_rows) {
-        const uint16_t* __restrict__ row = src + srow * cells;
-        if (identity) {
-          v = reinterpret_cast<const uint4*>(row)[chunk];
-        } else {
-          int i2 = (chunk * 8) / J;                                 // destination cell (i2, j2)
-          int j2 = chunk * 8 - i2 * J;
-          unsigned h[8];
-#pragma unroll
-          for (int n = 0; n < 8; ++n) {
-            const int i = flip ? I - 1 - i2 : i2;
-            int jm = j2 - shift;
-            jm = jm < 0 ? jm + J : jm;
-            const int j = mirror ? J - 1 - jm : jm;
-            h[n] = row[i * J + j];
-            if (++j2 == J) { j2 = 0; ++i2; }
-          }
-          v = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
-        }
-      }
-      to[q] = v;
     }
   }
 }
@@ -324,32 +246,18 @@ int seld_window_gather_rotate(const float* src, const float* rot, int64_t total_
                               int ch_x, int ch_y, int ch_z, int J, const int64_t* starts, const int32_t* params, int64_t B,
                               int64_t window, const uint8_t* channel_table, float mask_value, float* dst, void* stream_) {
   using namespace seld;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (total_rows < 0 || B < 0 || window <= 0 || freq_channels < 0 || freq_channels > channels)
-    return fail(kErrInvalidArgument, "seld_window_gather_rotate: bad extents");
-  if (channels != 4 && channels != 7)
-    return fail(kErrUnsupported, "seld_window_gather_rotate: a rotation is defined for 4 (log-mel) or 7 (log-mel + intensity) FOA feature channels");
-  if (!is_xyz_permutation(ch_x, ch_y, ch_z))
-    return fail(kErrInvalidArgument, "seld_window_gather_rotate: ch_x, ch_y, ch_z must be a permutation of 1, 2, 3");
-  if (J < 4 || J > kMaxSteps || J % 4 != 0)
-    return fail(kErrUnsupported, "seld_window_gather_rotate: J must be a multiple of 4 in 4..SELD_ROTATE_MAX_STEPS");
-  if (window * channels * kChunksPerChannel >= (int64_t{1} << 31))
-    return fail(kErrUnsupported, "seld_window_gather_rotate: window too large");
-  if (B == 0) return kOk;
-  if (!src || !rot || !starts || !params || !channel_table || !dst)
-    return fail(kErrInvalidArgument, "seld_window_gather_rotate: null pointer");
+  const char* who = "seld_window_gather_rotate";
+  DeviceState* st;
+  const int rc = check_window_args(
+      who, total_rows, B, window, freq_channels >= 0 && freq_channels <= channels,
+      {{channels != 4 && channels != 7, kErrUnsupported,
+        "a rotation is defined for 4 (log-mel) or 7 (log-mel + intensity) FOA feature channels"},
+       {!is_xyz_permutation(ch_x, ch_y, ch_z), kErrInvalidArgument, "ch_x, ch_y, ch_z must be a permutation of 1, 2, 3"},
+       {J < 4 || J > kMaxSteps || J % 4 != 0, kErrUnsupported, "J must be a multiple of 4 in 4..SELD_ROTATE_MAX_STEPS"}},
+      static_cast<int64_t>(channels) * kChunksPerChannel, {src, rot, starts, params, channel_table, dst}, &st);
+  if (rc != kOk || B == 0) return rc;
   ChannelTable8 table;
-  for (int p = 0; p < kPatterns; ++p)
-    for (int c = 0; c < 8; ++c) {
-      uint8_t e = 0;
-      if (c < channels) {
-        e = channel_table[p * channels + c];
-        if ((e & 0x7f) >= channels)
-          return fail(kErrInvalidArgument, "seld_window_gather_rotate: channel table names a channel >= channels");
-      }
-      table.e[p][c] = e;
-    }
+  if (const int bad = fill_channel_table(who, channel_table, channels, &table)) return bad;
   // unit slots in output-channel order; the Y channel rides in the X channel's slot
   UnitTable units{0ull, 0ull, 0};
   auto add = [&units](int a, int b) {
@@ -365,38 +273,12 @@ int seld_window_gather_rotate(const float* src, const float* rot, int64_t total_
     }
   RotationTable angles;
   fill_rotation_table(J, angles);
-  unsigned mask_bits;
-  static_assert(sizeof(mask_bits) == sizeof(mask_value), "fp32 bit pattern");
-  __builtin_memcpy(&mask_bits, &mask_value, sizeof(mask_bits));
   const long per_window = window * units.slots * kChunksPerChannel;
   hipLaunchKernelGGL(gather_rotate_kernel, window_grid(per_window, B, st->num_cus), dim3(256), 0,
                      static_cast<hipStream_t>(stream_), reinterpret_cast<const uint4*>(src),
                      reinterpret_cast<const uint4*>(rot), static_cast<long>(total_rows), channels, freq_channels, J, starts,
-                     params, static_cast<long>(B), static_cast<int>(window), table, angles, units, mask_bits,
+                     params, static_cast<long>(B), static_cast<int>(window), table, angles, units, mask_bits(mask_value),
                      reinterpret_cast<uint4*>(dst));
-  SELD_HIP_TRY(hipGetLastError());
-  return kOk;
-}
-
-int seld_window_permute_mask_rotate(const uint16_t* src, int64_t total_rows, int I, int J, const int64_t* starts,
-                                    const int32_t* params, int64_t B, int64_t window, uint16_t* dst, void* stream_) {
-  using namespace seld;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (total_rows < 0 || B < 0 || window <= 0 || I <= 0 || J <= 0 || static_cast<int64_t>(I) * J > 65536)
-    return fail(kErrInvalidArgument, "seld_window_permute_mask_rotate: bad extents");
-  if (J % 4 != 0)
-    return fail(kErrUnsupported, "seld_window_permute_mask_rotate: a quarter turn is a whole number of cells only when J % 4 == 0");
-  if ((I * J) % 8 != 0)
-    return fail(kErrUnsupported, "seld_window_permute_mask_rotate: I*J must be a multiple of 8 (16-byte rows)");
-  if (window * (I * J / 8) >= (int64_t{1} << 31))
-    return fail(kErrUnsupported, "seld_window_permute_mask_rotate: window too large");
-  if (B == 0) return kOk;
-  if (!src || !starts || !params || !dst) return fail(kErrInvalidArgument, "seld_window_permute_mask_rotate: null pointer");
-  const long per_window = window * (I * J / 8);
-  hipLaunchKernelGGL(permute_mask_rotate_kernel, window_grid(per_window, B, st->num_cus), dim3(256), 0,
-                     static_cast<hipStream_t>(stream_), src, static_cast<long>(total_rows), I, J, starts, params,
-                     static_cast<long>(B), static_cast<int>(window), reinterpret_cast<uint4*>(dst));
   SELD_HIP_TRY(hipGetLastError());
   return kOk;
 }

@@ -25,8 +25,8 @@ import math
 
 import numpy as np
 
-PARAM_INTS = 12
-PATTERNS = 16
+PARAM_INTS = 12                   # SELD_AUGMENT_PARAM_INTS; seld_native takes both from here
+PATTERNS = 16                     # SELD_AUGMENT_PATTERNS
 N_BINS = 64
 NEGATE = 0x80                     # channel-table flag: the output channel is MINUS its source channel
 
@@ -95,13 +95,8 @@ def freq_mask_channels(feature_set: str, n_channels: int) -> int:
 
 def cell_dest(p: int, I: int = 18, J: int = 36) -> np.ndarray:
     """int64 [I*J]: the cell a set cell moves TO: (i, j) -> (e ? I-1-i : i, ((m ? J-1-j : j) + k J/4) mod J)."""
-    if J % 4:
-        raise ValueError("a quarter turn is a whole number of cells only when J % 4 == 0")
     m, k, e = decode(p)
-    i, j = np.divmod(np.arange(I * J, dtype=np.int64), J)
-    i2 = I - 1 - i if e else i
-    j2 = ((J - 1 - j if m else j) + k * (J // 4)) % J
-    return i2 * J + j2
+    return cell_dest_rot(m, total_step(k, 0, J), e, I, J)
 
 
 def cell_source(p: int, I: int = 18, J: int = 36) -> np.ndarray:

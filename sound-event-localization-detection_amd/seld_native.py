@@ -14,6 +14,10 @@ from pathlib import Path
 
 import torch
 
+# SELD_AUGMENT_PARAM_INTS (pattern, 2 x (time start, length), 2 x (frequency start, length), azimuth step, padding) and
+# SELD_AUGMENT_PATTERNS: defined once, in seld_augment (numpy only, so no import cycle)
+from seld_augment import PARAM_INTS as AUGMENT_PARAM_INTS, PATTERNS as AUGMENT_PATTERNS, check_channel_order
+
 _HERE = Path(__file__).resolve().parent
 # SELD_HIP_LIB: developer override to load an experimental build of the SAME library (A/B kernel experiments)
 LIB_PATH = Path(os.environ["SELD_HIP_LIB"]).resolve() if os.environ.get("SELD_HIP_LIB") else _HERE / "libseld_hip.so"
@@ -465,30 +469,54 @@ def expand_labels(mask: torch.Tensor, num_classes: int = NUM_CLASSES) -> torch.T
     return out
 
 
-def gather_windows(src: torch.Tensor, starts: torch.Tensor, window: int, out: torch.Tensor | None = None) -> torch.Tensor:
-    """dataset.py:267-317: src [T, ...] (time-major rows) -> [B, window, ...], zero padded past T.  ``out``: write into
-    this contiguous tensor of that shape (the static input buffer of a captured training step)."""
-    if not src.is_cuda:
-        raise SeldNativeError("gather_windows: src must be a GPU tensor")
+def _window_call(name: str, src: torch.Tensor, dtype, row, what: str, starts: torch.Tensor, window: int,
+                 params: torch.Tensor | None, out: torch.Tensor | None):
+    """The front of the five window gathers, every message opening with ``name``: the source (on the GPU; ``dtype`` unless
+    None; rows of shape ``row`` unless None, a None extent being free; at least one row -- ``what`` words the refusal),
+    ``starts`` as int64 on the source's device, ``params`` (None: the gather takes none) a contiguous int32 [B, 12] tensor
+    there, ``out`` allocated or checked as [B, window] + the row shape.  Returns (src, device index, starts, out)."""
+    ok = src.is_cuda and (dtype is None or src.dtype == dtype)
+    if ok and row is not None:
+        ok = src.dim() == len(row) + 1 and all(r is None or n == r for n, r in zip(src.shape[1:], row))
+    if not ok:
+        raise SeldNativeError(f"{name}: src must be {what}")
     src = src.contiguous()
-    row_bytes = src[0].numel() * src.element_size() if src.shape[0] else 0
+    if src.shape[0] == 0:
+        raise ValueError(f"{name}: empty source")
     index = ensure_init(src.device)
     starts = starts.to(device=src.device, dtype=torch.int64).contiguous()
+    if params is not None and (not params.is_cuda or params.dtype != torch.int32 or not params.is_contiguous()
+                               or tuple(params.shape) != (starts.numel(), AUGMENT_PARAM_INTS)):
+        raise ValueError(f"{name}: params must be a contiguous int32 [B, 12] GPU tensor (augment_params)")
     shape = (starts.numel(), window) + tuple(src.shape[1:])
     if out is None:
         out = torch.empty(shape, dtype=src.dtype, device=src.device)
     elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
-        raise ValueError(f"gather_windows: out must be a contiguous {src.dtype} tensor of shape {shape} on {src.device}")
+        kind = str(src.dtype).replace("torch.", "")
+        raise ValueError(f"{name}: out must be a contiguous {kind} tensor of shape {shape} on {src.device}")
+    return src, index, starts, out
+
+
+def _channel_table(name: str, channel_table, channels: int):
+    """The host's uint8 [16, channels] channel table as a contiguous numpy array."""
+    import numpy as np
+    table = np.ascontiguousarray(channel_table, dtype=np.uint8)
+    if table.shape != (AUGMENT_PATTERNS, channels):
+        raise ValueError(f"{name}: channel_table must be [16, {channels}]")
+    return table
+
+
+def gather_windows(src: torch.Tensor, starts: torch.Tensor, window: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """dataset.py:267-317: src [T, ...] (time-major rows) -> [B, window, ...], zero padded past T.  ``out``: write into
+    this contiguous tensor of that shape (the static input buffer of a captured training step)."""
+    src, index, starts, out = _window_call("gather_windows", src, None, None, "a GPU tensor", starts, window, None, out)
+    row_bytes = src[0].numel() * src.element_size()
     if row_bytes == 0:
         raise ValueError("gather_windows: empty source")
     with _device_guard(index):
         check(load_library().seld_window_gather(_p(src), src.shape[0], row_bytes, _p(starts), starts.numel(),
                                                 window, _p(out), _stream_ptr(src.device)), "seld_window_gather")
     return out
-
-
-AUGMENT_PARAM_INTS = 12      # SELD_AUGMENT_PARAM_INTS: (pattern, 2 x (time start, length), 2 x (frequency start, length), padding)
-AUGMENT_PATTERNS = 16
 
 
 def augment_params(params, batch: int, window: int, device, steps: int | None = None) -> torch.Tensor:
@@ -523,29 +551,11 @@ def gather_windows_augment(src: torch.Tensor, starts: torch.Tensor, window: int,
     (csrc/augment.hip): a signed channel permutation chosen by the window's spatial pattern, then time / frequency masks.
     ``params``: int32 [B, 12] on the device (``augment_params``); ``channel_table``: uint8 [16, C] host array, entry =
     source channel | 0x80 when negated (None: channels stay put); frequency masks touch channels < ``freq_channels``."""
-    if not src.is_cuda or src.dtype != torch.float32 or src.dim() != 3 or src.shape[2] != N_MELS:
-        raise SeldNativeError("gather_windows_augment: src must be a float32 GPU tensor [T, C, 64]")
-    src = src.contiguous()
+    src, index, starts, out = _window_call("gather_windows_augment", src, torch.float32, (None, N_MELS),
+                                           "a float32 GPU tensor [T, C, 64]", starts, window, params, out)
     channels = int(src.shape[1])
-    if src.shape[0] == 0:
-        raise ValueError("gather_windows_augment: empty source")
     freq_channels = channels if freq_channels is None else int(freq_channels)
-    index = ensure_init(src.device)
-    starts = starts.to(device=src.device, dtype=torch.int64).contiguous()
-    if not params.is_cuda or params.dtype != torch.int32 or tuple(params.shape) != (starts.numel(), AUGMENT_PARAM_INTS) \
-            or not params.is_contiguous():
-        raise ValueError("gather_windows_augment: params must be a contiguous int32 [B, 12] GPU tensor (augment_params)")
-    table = None
-    if channel_table is not None:
-        import numpy as np
-        table = np.ascontiguousarray(channel_table, dtype=np.uint8)
-        if table.shape != (AUGMENT_PATTERNS, channels):
-            raise ValueError(f"gather_windows_augment: channel_table must be [16, {channels}]")
-    shape = (starts.numel(), window, channels, N_MELS)
-    if out is None:
-        out = torch.empty(shape, dtype=src.dtype, device=src.device)
-    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
-        raise ValueError(f"gather_windows_augment: out must be a contiguous float32 tensor of shape {shape} on {src.device}")
+    table = None if channel_table is None else _channel_table("gather_windows_augment", channel_table, channels)
     with _device_guard(index):
         check(load_library().seld_window_gather_augment(
             _p(src), src.shape[0], channels, freq_channels, _p(starts), _p(params), starts.numel(), window,
@@ -558,21 +568,8 @@ def gather_windows_permute(src: torch.Tensor, starts: torch.Tensor, window: int,
                            J: int = GRID_J, out: torch.Tensor | None = None) -> torch.Tensor:
     """``gather_windows`` of the label timeline src [T, I*J] (uint16 class masks) with the grid cells moved by each
     window's spatial pattern (csrc/augment.hip); labels are never masked."""
-    if not src.is_cuda or src.dtype != torch.uint16 or src.dim() != 2 or src.shape[1] != I * J:
-        raise SeldNativeError("gather_windows_permute: src must be a uint16 GPU tensor [T, I*J]")
-    src = src.contiguous()
-    if src.shape[0] == 0:
-        raise ValueError("gather_windows_permute: empty source")
-    index = ensure_init(src.device)
-    starts = starts.to(device=src.device, dtype=torch.int64).contiguous()
-    if not params.is_cuda or params.dtype != torch.int32 or tuple(params.shape) != (starts.numel(), AUGMENT_PARAM_INTS) \
-            or not params.is_contiguous():
-        raise ValueError("gather_windows_permute: params must be a contiguous int32 [B, 12] GPU tensor (augment_params)")
-    shape = (starts.numel(), window, I * J)
-    if out is None:
-        out = torch.empty(shape, dtype=src.dtype, device=src.device)
-    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
-        raise ValueError(f"gather_windows_permute: out must be a contiguous uint16 tensor of shape {shape} on {src.device}")
+    src, index, starts, out = _window_call("gather_windows_permute", src, torch.uint16, (I * J,),
+                                           "a uint16 GPU tensor [T, I*J]", starts, window, params, out)
     with _device_guard(index):
         check(load_library().seld_window_permute_mask(_p(src), src.shape[0], I, J, _p(starts), _p(params), starts.numel(),
                                                       window, _p(out), _stream_ptr(src.device)), "seld_window_permute_mask")
@@ -581,9 +578,7 @@ def gather_windows_permute(src: torch.Tensor, starts: torch.Tensor, window: int,
 
 def foa_channels(order: str = "WYZX"):
     """(ch_x, ch_y, ch_z): the input channels that carry X, Y and Z under Config.FOA_CHANNEL_ORDER (W is channel 0)."""
-    order = str(order).upper()
-    if len(order) != 4 or order[0] != "W" or sorted(order[1:]) != ["X", "Y", "Z"]:
-        raise ValueError(f"FOA_CHANNEL_ORDER must be 'WYZX' or 'WXYZ', got {order!r}")
+    order = check_channel_order(order)
     return order.index("X"), order.index("Y"), order.index("Z")
 
 
@@ -617,31 +612,15 @@ def gather_windows_rotate(src: torch.Tensor, rot: torch.Tensor, starts: torch.Te
     ('logmel') or 7 ('logmel_iv'), rot [T, 3, 64] the timeline's rotation terms (``foa_rotation_terms``).  A window whose
     total rotation is a whole number of quarter turns is the signed channel copy of ``gather_windows_augment``, bit for bit;
     any other window gets X' / Y' log-mel and IV_x' / IV_y' computed from the terms."""
-    if not src.is_cuda or src.dtype != torch.float32 or src.dim() != 3 or src.shape[2] != N_MELS:
-        raise SeldNativeError("gather_windows_rotate: src must be a float32 GPU tensor [T, C, 64]")
-    src = src.contiguous()
+    src, index, starts, out = _window_call("gather_windows_rotate", src, torch.float32, (None, N_MELS),
+                                           "a float32 GPU tensor [T, C, 64]", starts, window, params, out)
     channels = int(src.shape[1])
-    if src.shape[0] == 0:
-        raise ValueError("gather_windows_rotate: empty source")
     if not rot.is_cuda or rot.dtype != torch.float32 or tuple(rot.shape) != (src.shape[0], 3, N_MELS) or rot.device != src.device:
         raise SeldNativeError(f"gather_windows_rotate: rot must be a float32 tensor [{src.shape[0]}, 3, 64] on {src.device}")
     rot = rot.contiguous()
     ch_x, ch_y, ch_z = foa_channels(order)
     freq_channels = channels if freq_channels is None else int(freq_channels)
-    index = ensure_init(src.device)
-    starts = starts.to(device=src.device, dtype=torch.int64).contiguous()
-    if not params.is_cuda or params.dtype != torch.int32 or tuple(params.shape) != (starts.numel(), AUGMENT_PARAM_INTS) \
-            or not params.is_contiguous():
-        raise ValueError("gather_windows_rotate: params must be a contiguous int32 [B, 12] GPU tensor (augment_params)")
-    import numpy as np
-    table = np.ascontiguousarray(channel_table, dtype=np.uint8)
-    if table.shape != (AUGMENT_PATTERNS, channels):
-        raise ValueError(f"gather_windows_rotate: channel_table must be [16, {channels}]")
-    shape = (starts.numel(), window, channels, N_MELS)
-    if out is None:
-        out = torch.empty(shape, dtype=src.dtype, device=src.device)
-    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
-        raise ValueError(f"gather_windows_rotate: out must be a contiguous float32 tensor of shape {shape} on {src.device}")
+    table = _channel_table("gather_windows_rotate", channel_table, channels)
     with _device_guard(index):
         check(load_library().seld_window_gather_rotate(
             _p(src), _p(rot), src.shape[0], channels, freq_channels, ch_x, ch_y, ch_z, int(J), _p(starts), _p(params),
@@ -654,21 +633,8 @@ def gather_windows_permute_rotate(src: torch.Tensor, starts: torch.Tensor, windo
                                   J: int = GRID_J, out: torch.Tensor | None = None) -> torch.Tensor:
     """``gather_windows_permute`` with the azimuth index of every cell shifted by the window's total step
     (k J/4 + params[:, 9]) mod J after the mirror (csrc/rotate.hip)."""
-    if not src.is_cuda or src.dtype != torch.uint16 or src.dim() != 2 or src.shape[1] != I * J:
-        raise SeldNativeError("gather_windows_permute_rotate: src must be a uint16 GPU tensor [T, I*J]")
-    src = src.contiguous()
-    if src.shape[0] == 0:
-        raise ValueError("gather_windows_permute_rotate: empty source")
-    index = ensure_init(src.device)
-    starts = starts.to(device=src.device, dtype=torch.int64).contiguous()
-    if not params.is_cuda or params.dtype != torch.int32 or tuple(params.shape) != (starts.numel(), AUGMENT_PARAM_INTS) \
-            or not params.is_contiguous():
-        raise ValueError("gather_windows_permute_rotate: params must be a contiguous int32 [B, 12] GPU tensor (augment_params)")
-    shape = (starts.numel(), window, I * J)
-    if out is None:
-        out = torch.empty(shape, dtype=src.dtype, device=src.device)
-    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
-        raise ValueError(f"gather_windows_permute_rotate: out must be a contiguous uint16 tensor of shape {shape} on {src.device}")
+    src, index, starts, out = _window_call("gather_windows_permute_rotate", src, torch.uint16, (I * J,),
+                                           "a uint16 GPU tensor [T, I*J]", starts, window, params, out)
     with _device_guard(index):
         check(load_library().seld_window_permute_mask_rotate(_p(src), src.shape[0], I, J, _p(starts), _p(params),
                                                              starts.numel(), window, _p(out), _stream_ptr(src.device)),

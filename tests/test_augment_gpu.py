@@ -31,8 +31,11 @@ def _timeline(seed, total, channels):
 
 
 def _params(rng, patterns, window=WINDOW):
-    """One row per pattern given, cycling through the mask shapes the issue lists: random, empty, full-width, end-touching."""
+    """One row per pattern given, cycling through the mask shapes the issue lists: random, empty, full-width, end-touching.
+    Slot [9], the azimuth step of the rotating entry points, holds a seeded value in 0..35: the restatement and the two
+    entry points under test here ignore it (a generator of its own, so the masks drawn from ``rng`` are what they were)."""
     rows = np.zeros((len(patterns), 12), dtype=np.int32)
+    steps = np.random.default_rng(len(patterns)).integers(0, 36, len(patterns))
     for r, p in enumerate(patterns):
         kind = r % 5
         if kind == 0:                                    # random
@@ -47,7 +50,7 @@ def _params(rng, patterns, window=WINDOW):
             t, tl, f, fl = [window - 30, window - 10], [30, 10], [64 - 7, 0], [7, 1]
         else:                                            # the whole window in time
             t, tl, f, fl = [0, 0], [window, 0], [3, 60], [2, 4]
-        rows[r] = (p, t[0], tl[0], t[1], tl[1], f[0], fl[0], f[1], fl[1], 0, 0, 0)
+        rows[r] = (p, t[0], tl[0], t[1], tl[1], f[0], fl[0], f[1], fl[1], steps[r], 0, 0)
     return rows
 
 

@@ -3,7 +3,6 @@ rasteriser, the group it forms, the two float64 identities the rotating gather r
 refusals, the C ABI and the compiler's resource report of csrc/rotate.hip."""
 import math
 import re
-import subprocess
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -280,25 +279,16 @@ def test_library_header_and_binding_carry_the_three_entry_points():
 
 
 def test_rotate_kernels_use_no_scratch_and_no_lds_in_the_gathers():
-    """Same method as test_augment_kernels_use_no_scratch: the compiler's own report for gfx950."""
-    run = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", f"-I{ROOT / 'include'}",
-                          "-Rpass-analysis=kernel-resource-usage", "-c", str(CSRC / "rotate.hip"), "-o", "/dev/null"],
-                         capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-2000:]
-    scratch, lds, current = {}, {}, None
-    for line in run.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            current = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and current:
-            scratch[current] = int(m.group(1))
-        m = re.search(r"LDS Size \[bytes/block\]: (\d+)", line)
-        if m and current:
-            lds[current] = int(m.group(1))
-    for kernel in ("gather_rotate_kernel", "permute_mask_rotate_kernel", "rotation_terms_kernel"):
-        hits = {k: v for k, v in scratch.items() if kernel in k}
-        assert hits, (kernel, sorted(scratch))
+    """Same method as test_augment_kernels_use_no_scratch: the compiler's own report for gfx950.  The label kernel of the
+    rotating pair is the kStep instantiation of permute_mask_kernel in csrc/augment.hip; both instantiations are held to it."""
+    import hip_resources
+    found = hip_resources.report(CSRC / "rotate.hip")
+    labels = {k: v for k, v in hip_resources.report(CSRC / "augment.hip").items() if "permute_mask_kernel" in k}
+    assert sorted("ILb1E" in k for k in labels) == [False, True], sorted(labels)      # <false> and <true>, nothing else
+    found.update(labels)
+    for kernel in ("gather_rotate_kernel", "permute_mask_kernel", "rotation_terms_kernel"):
+        hits = {k: v["scratch"] for k, v in found.items() if kernel in k}
+        assert hits, (kernel, sorted(found))
         assert all(v == 0 for v in hits.values()), hits
-    for kernel in ("gather_rotate_kernel", "permute_mask_rotate_kernel"):
-        assert all(v == 0 for k, v in lds.items() if kernel in k)
+    for kernel in ("gather_rotate_kernel", "permute_mask_kernel"):
+        assert all(v["lds"] == 0 for k, v in found.items() if kernel in k)

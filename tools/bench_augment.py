@@ -8,7 +8,7 @@
                                                      augmented pair of ONE case (identity | rotation | mirror | drawn), C = 4
 
 Kernels, at the training shape (B = 32 windows of 250 frames, C_total = 4 and 7): the augmented pair (gather_augment_kernel +
-permute_mask_kernel) against the plain pair (gather_rows_kernel twice) on the same starts, alternating in one process.  A
+permute_mask_kernel<false>) against the plain pair (gather_rows_kernel twice) on the same starts, alternating in one process.  A
 timed sample is a burst of launches captured as one HIP graph and replayed between two device events (one launch is a few
 microseconds: less than a Python launch costs the host), every launch of a burst with its own random starts; the timeline is
 larger than the Infinity Cache, so the reads come from HBM as they do in an epoch over hours of audio.  Bytes are the algorithm's: every output byte written once and read

@@ -5,9 +5,10 @@
   python tools/bench_rotate.py --skip-e2e           kernels only
 
 Kernels, at the training shape (B = 32 windows of 250 frames, C_total = 4 and 7): the rotating pair (gather_rotate_kernel +
-permute_mask_rotate_kernel) with the rows training draws under AUGMENT_ROTATE against the augmenting pair of csrc/augment.hip
-(gather_augment_kernel + permute_mask_kernel) with the rows it draws under AUGMENT_SPATIAL -- both with two time and two
-frequency masks -- on the same starts, alternating in one process.  Built the way tools/bench_augment.py is (its Burst is
+permute_mask_kernel<true>, the label kernel of csrc/augment.hip with the azimuth step) with the rows training draws under
+AUGMENT_ROTATE against the augmenting pair of csrc/augment.hip (gather_augment_kernel + permute_mask_kernel<false>) with the
+rows it draws under AUGMENT_SPATIAL -- both with two time and two frequency masks -- on the same starts, alternating in one
+process.  Built the way tools/bench_augment.py is (its Burst is
 used): a timed sample is a burst of launches captured as one HIP graph and replayed between two device events, every launch
 with its own random starts; the timeline is larger than the Infinity Cache.  Bytes are the algorithm's: every output byte
 written once and read once, and on the rotated path the three rotation-term rows read in place of the X and Y log-mel rows
