@@ -308,6 +308,8 @@ __global__ __launch_bounds__(kCfFinalThreads) void convfirst_stats_final_kernel(
     running_var[ch] = static_cast<float>((1.0 - momentum) * running_var[ch] + momentum * unbiased);
     const float meanf = static_cast<float>(mean);
     const float invstd = static_cast<float>(1.0 / sqrt(var + static_cast<double>(eps)));
+    // two roundings (the fp32 invstd, then the product): up to 1.5 ulp from weight / sigma, so up to 1 ulp from the `a` of
+    // csrc/convtail.hip, which rounds weight * the double invstd once; no test pins this path's `a` to the ulp
     const float a = weight[ch] * invstd;
     mean_invstd[ch] = meanf;
     mean_invstd[kCfCout + ch] = invstd;
