@@ -350,6 +350,14 @@ int seld_gru_bias_grads(const float* partial, int64_t tiles, int64_t H, float* d
 int seld_sum_chunks(const void* partial, int in_is_bf16, int64_t chunks, int64_t count, void* out, int out_is_bf16,
                     void* stream);
 
+/* seld_sum_chunks with the columns re-ordered on the way out: partial [chunks][rows][F][C], out [rows][C][F],
+ * out[row][c * F + f] = sum over chunks of partial[chunk][row][f * C + c].  The same accumulation per element (fp32,
+ * chunks in order, one rounding), so the result equals seld_sum_chunks followed by the column permutation bit for bit.
+ * dW_ih of the first GRU layer, whose input features are ordered (frequency, channel) while the parameter's columns are
+ * (channel, frequency) (model_crnn.py:114-116).  F in 2..4, C % 8 == 0, 16-byte aligned tensors. */
+int seld_sum_chunks_columns(const void* partial, int in_is_bf16, int64_t chunks, int64_t rows, int64_t C, int64_t F,
+                            void* out, int out_is_bf16, void* stream);
+
 /* out[n] = sum over r of g[r][n]: the bias gradient of an nn.Linear (autograd for trainer.py:178) from the [rows][n_cols]
  * output gradient, bf16 or fp32, n_cols % 8 == 0, 16-byte aligned.  Two launches: row blocks summed in parallel into
  * `partial` [seld_column_sums_blocks(rows, n_cols)][n_cols] fp32 (caller-owned), then added in a fixed order. */

@@ -7,18 +7,28 @@
 // encoder's shapes and finish with a split-K that adds with atomics into a zero-filled fp32 workspace, then a cast and
 // a copy.  Here:
 //
-//   * a workgroup (4 waves, 2 x 2) owns a 64-co x 64-ci tile for all nine taps and a K slab: a run of chunks, a chunk
-//     being kWgKc positions = TC consecutive time rows of one clip.  Per chunk it stages dy [kWgKc][64 co] and the x
-//     rows t0-1 .. t0+TC with zero rows outside [0, T) and a zero column on each frequency edge, [TC+2][F+2][64 ci],
+//   * a workgroup (8 waves, 2 co x 4 ci) owns a 64-co x 64-ci tile for all nine taps and a K slab: a run of chunks, a
+//     chunk being kWgKc positions = TC consecutive time rows of one clip.  Per chunk it stages dy [kWgKc][64 co] and the
+//     x rows t0-1 .. t0+TC with zero rows outside [0, T) and a zero column on each frequency edge, [TC+2][F+2][64 ci],
 //     in LDS once; the nine taps are nine shifted views of that x image (a constant row offset per tap).
 //   * both operands are position-major in memory (channels innermost), so the MFMA fragments, 8 positions of one
 //     channel, come from ds_read_b64_tr_b16.  A K-group of 32 positions is read as two 4-row halves; the MFMA's k
 //     numbering is a free relabelling of positions as long as both operands use the same one, so lanes 16g..16g+15
 //     take positions 4g..4g+3 and 16+4g..16+4g+3: a 32-lane half then reads 8 consecutive LDS rows, which the 160-byte
 //     row pitch spreads over all 64 banks (conflict-free).
-//   * v_mfma_f32_16x16x32_bf16, fp32 accumulators for 9 taps x 2 x 2 tiles per wave (144 registers).
-//   * two workgroups per CU (at most 254 of the 256 registers, no scratch): one stages while the other multiplies.  A
-//     register prefetch of the next chunk does not fit beside the 144 accumulators (it spills).
+//   * v_mfma_f32_16x16x32_bf16; a wave owns 32 co x 16 ci: fp32 accumulators for 9 taps x 2 tiles (72 registers), two
+//     dy fragments per K-group reused by all nine taps, one x fragment per tap.
+//   * ONE workgroup per CU on HALF of its registers: at most 128 per lane and no scratch
+//     (tests/test_conv_wgrad_occupancy_cpu.py), so its two waves per SIMD hold 256 of the 512 entries and waves of
+//     another kernel fit beside it for its whole run -- the weight gradients are side-stream work that only the optimiser
+//     waits for, and the HBM-bound BatchNorm tails of the main stream run beside them.  Alone the kernel
+//     is 4 - 6.5 % slower than the two-workgroup form at 128->256 and 256->512 channels; it is kept for
+//     what it does to the iteration.  The launch bound of 1024 threads is what gives the compiler that budget (a
+//     workgroup is launched with kWgThreads = 512; see kWgLaunchBound).
+//   * the workgroup hides its own staging: two LDS images (2 x 49 280 B at F = 8 / 16, 2 x 53 120 B at F = 32: more than
+//     half of the CU's 160 KB, so no second workgroup of this kernel shares the CU, and room for two 17 KB workgroups of
+//     the tail kernels beside it).  The next chunk is requested behind the first K-group's MFMAs, waits in registers
+//     (2 + at most 4 uint4 per thread) and is stored into the other image before the last K-group; one barrier per chunk.
 //   * each K slab writes its fp32 partial tile to its own workspace slot once (no atomics, no memset); a second launch
 //     adds the slots in a fixed order (conv3x3_wgrad_sum_kernel) and rounds once into dW in the parameter's own layout
 //     ([Cout][3][3][Cin]) and dtype.  Deterministic: the same inputs give the same bits on every call.
@@ -33,7 +43,7 @@ namespace {
 
 using namespace conv3x3;            // types, the staged image and the transposed reads (conv3x3_image.h)
 
-constexpr int kWgThreads = kThreads;
+constexpr int kWgThreads = 512;      // 8 waves: 2 (co) x 4 (ci)
 constexpr int kWgTile = 64;          // output channels and input channels per workgroup
 constexpr int kWgKc = 128;           // positions per staged chunk
 constexpr int kWgPitch = kPitch;
@@ -46,94 +56,143 @@ struct WgradGeom {
   static constexpr int TC = Img::TC;                         // time rows per chunk
   static constexpr int XR = Img::kRows;                      // x image rows (with halo rows and edge columns)
   static constexpr int kDyLoads = kWgKc * 8 / kWgThreads;    // 16-byte pieces per thread
-  static constexpr int kXLoads = Img::kLoads;
-  static constexpr int kLdsShorts = (kWgKc + XR) * kWgPitch;
-  static_assert(kLdsShorts * 2 <= 64 * 1024, "LDS image larger than the default limit");
+  static constexpr int kXLoads = (XR * 8 + kWgThreads - 1) / kWgThreads;
+  static constexpr int kRowsPerStep = 32 / F * (F + 2);       // image rows between positions p and p + 32
+  static constexpr int kHighHalf = F == 32 ? 16 : 16 / F * (F + 2);      // ... between positions p and p + 16 (p < 16)
+  static constexpr int kImageShorts = (kWgKc + XR) * kWgPitch;           // one chunk: dy, then the x image
+  static constexpr int kLdsShorts = 2 * kImageShorts;
+  // more than half of the CU's 160 KB (one workgroup of this kernel per CU), and room for two 17 KB workgroups beside it
+  static_assert(kLdsShorts * 2 > 80 * 1024 && kLdsShorts * 2 <= 124 * 1024, "LDS footprint outside its bracket");
 };
 
+// The launch bound is TWICE the workgroup the kernel is launched with (launch_wgrad: kWgThreads): a bound of 16 waves is 4
+// per SIMD, i.e. 512 / 4 = 128 registers per lane, which is the budget that leaves half of the register file free.
+// (With a bound of kWgThreads the compiler sizes the budget by the LDS occupancy, one workgroup = 2 waves per SIMD, and
+// takes up to 256; amdgpu_waves_per_eu is capped the same way.)  The budget also leans on the compiler: the piece and
+// lane addresses are re-derived per chunk behind an empty asm, the K-group loop is rolled, and sched_group_barrier
+// orders reads and MFMAs.  AFTER EVERY ROCm / compiler update run tests/test_conv_wgrad_occupancy_cpu.py (<= 128
+// registers, no scratch, LDS bracket) and tests/test_conv_wgrad_cpu.py: they are the only guard of this.
+constexpr int kWgLaunchBound = 2 * kWgThreads;
+static_assert(kWgLaunchBound == 1024 && kWgLaunchBound / 64 / 4 == 4, "the register budget is 512 / (bound waves per SIMD)");
+
 template <int F>
-__global__ __launch_bounds__(kWgThreads, 2) void conv3x3_wgrad_kernel(
+__global__ __launch_bounds__(kWgLaunchBound) void conv3x3_wgrad_kernel(
     const unsigned short* __restrict__ x, const unsigned short* __restrict__ dy, int T, int Cin, int Cout,
     int chunks_per_clip, int chunks, int per_slab, float* __restrict__ ws) {
   using G = WgradGeom<F>;
   __shared__ __attribute__((aligned(16))) unsigned short lds[G::kLdsShorts];
-  unsigned short* const ldy = lds;
-  unsigned short* const lx = lds + kWgKc * kWgPitch;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
+  const int wm = wave >> 2, wn = wave & 3;
   const int ci0 = blockIdx.x * kWgTile, co0 = blockIdx.y * kWgTile;
   const int c_begin = blockIdx.z * per_slab;
   const int c_end = min(c_begin + per_slab, chunks);
 
-  f32x4 acc[9][2][2];
+  f32x4 acc[9][2];
 #pragma unroll
   for (int k = 0; k < 9; ++k)
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n) acc[k][m][n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int m = 0; m < 2; ++m) acc[k][m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
-  // lane 4q+p of the 16-lane group g supplies row q, columns 4p..4p+3 of its 4-row block (ds_read_b64_tr_b16)
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const int lpos = 4 * g + q;                                   // position of the lane's row in the first half
-  const int a_col = wm * 32 + 4 * p, b_col = wn * 32 + 4 * p;
-
+  // The next chunk waits in registers during a chunk's MFMAs.  Loads without branches: a piece outside the map (a time
+  // row outside [0, T), an edge column, the image's tail) reads the chunk's first element instead and is replaced by
+  // zero when it is stored.  Addresses are a per-chunk uniform base (time row t0 of the clip, always inside) plus a
+  // 32-bit lane offset that is recomputed per chunk rather than kept in registers beside the accumulators.
   uint4 rdy[G::kDyLoads], rx[G::kXLoads];
+  bool in_dy[G::kDyLoads], in_x[G::kXLoads];
   auto load = [&](int c) {
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
     const int b = c / chunks_per_clip, t0 = (c - b * chunks_per_clip) * G::TC;
-    const long clip_row = static_cast<long>(b) * T;
+    const long row0 = (static_cast<long>(b) * T + t0) * F;
+    const unsigned short* const dy0 = dy + row0 * Cout + co0;
+    const unsigned short* const x0 = x + row0 * Cin + ci0;
+    const int ch8 = (tid & 7) * 8;
 #pragma unroll
     for (int i = 0; i < G::kDyLoads; ++i) {
-      const int piece = tid + i * kWgThreads, pos = piece >> 3, ch = piece & 7;
-      const int t = t0 + pos / F;
-      rdy[i] = make_uint4(0u, 0u, 0u, 0u);
-      if (t < T)
-        rdy[i] = *reinterpret_cast<const uint4*>(dy + ((clip_row + t) * F + pos % F) * Cout + co0 + ch * 8);
+      const int pos = (tid >> 3) + i * (kWgThreads / 8);
+      in_dy[i] = t0 + pos / F < T;
+      rdy[i] = *reinterpret_cast<const uint4*>(dy0 + (in_dy[i] ? pos * Cout + ch8 : 0));
     }
 #pragma unroll
     for (int i = 0; i < G::kXLoads; ++i) {
-      rx[i] = image_piece<F, kWgKc>(x, clip_row, t0, T, Cin, ci0, tid + i * kWgThreads);
+      const int r = (tid >> 3) + i * (kWgThreads / 8);                       // image row: (tr, f + 1)
+      const int tr = r / (F + 2), f = r - tr * (F + 2) - 1, t = t0 - 1 + tr;
+      in_x[i] = r < G::XR && t >= 0 && t < T && f >= 0 && f < F;
+      rx[i] = *reinterpret_cast<const uint4*>(x0 + (in_x[i] ? ((tr - 1) * F + f) * Cin + ch8 : 0));
+    }
+  };
+  auto store = [&](unsigned short* image) {
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    unsigned short* const ldy = image;
+    unsigned short* const lx = image + kWgKc * kWgPitch;
+    auto piece_or_zero = [](uint4 v, bool inside) {
+      return make_uint4(inside ? v.x : 0u, inside ? v.y : 0u, inside ? v.z : 0u, inside ? v.w : 0u);
+    };
+#pragma unroll
+    for (int i = 0; i < G::kDyLoads; ++i) {
+      const int piece = tid + i * kWgThreads;
+      *reinterpret_cast<uint4*>(ldy + (piece >> 3) * kWgPitch + (piece & 7) * 8) = piece_or_zero(rdy[i], in_dy[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < G::kXLoads; ++i) {
+      const int piece = tid + i * kWgThreads;
+      if (piece < G::XR * 8)
+        *reinterpret_cast<uint4*>(lx + (piece >> 3) * kWgPitch + (piece & 7) * 8) = piece_or_zero(rx[i], in_x[i]);
     }
   };
 
+  if (c_begin < c_end) {
+    load(c_begin);
+    store(lds);
+  }
   for (int c = c_begin; c < c_end; ++c) {
-    load(c);                                                    // in flight while the other waves finish chunk c-1
-    __syncthreads();                                            // the previous chunk's fragment reads are done
-#pragma unroll
-    for (int i = 0; i < G::kDyLoads; ++i) {
-      const int piece = tid + i * kWgThreads;
-      *reinterpret_cast<uint4*>(ldy + (piece >> 3) * kWgPitch + (piece & 7) * 8) = rdy[i];
-    }
-#pragma unroll
-    for (int i = 0; i < G::kXLoads; ++i) {
-      const int piece = tid + i * kWgThreads;
-      if (piece < G::XR * 8) *reinterpret_cast<uint4*>(lx + (piece >> 3) * kWgPitch + (piece & 7) * 8) = rx[i];
-    }
+    // chunk c's image is complete, and every wave is done reading the other image (chunk c-1)
     __syncthreads();
+    // lane 4q+p of the 16-lane group g supplies row q, columns 4p..4p+3 of its 4-row block (ds_read_b64_tr_b16):
+    // dy rows lpos and lpos + 16 of a K-group of 32, and the x image rows of the same positions.  lpos < 16 and F
+    // divides 32, so the image row of position 32 ks + lpos (+ 16) is that of lpos plus a constant: every fragment read
+    // below is one of two lane addresses (derived per chunk, not kept over the prefetch) plus a compile-time offset.
+    int lt = threadIdx.x;
+    asm volatile("" : "+v"(lt));
+    const int g = (lt >> 4) & 3, q = (lt >> 2) & 3, p = lt & 3, wv = lt >> 6;
+    const int lpos = 4 * g + q;
+    const unsigned short* const image = lds + ((c - c_begin) & 1) * G::kImageShorts;
+    const unsigned short* const pa = image + lpos * kWgPitch + (wv >> 2) * 32 + 4 * p;
+    const unsigned short* const pb = image + (kWgKc + image_row<F>(lpos)) * kWgPitch + (wv & 3) * 16 + 4 * p;
+    const bool more = c + 1 < c_end;
+    unsigned short* const other = lds + ((c + 1 - c_begin) & 1) * G::kImageShorts;
 
-#pragma unroll
+    // (a rolled loop: unrolled, the compiler shares fragment halves between K-groups and taps and keeps them and the
+    // next group's dy fragments live beside the accumulators and the prefetch, which then spills)
+#pragma unroll 1
     for (int ks = 0; ks < kWgKc / 32; ++ks) {
-      const int pos_lo = ks * 32 + lpos, pos_hi = pos_lo + 16;
+      const unsigned short* const ka = pa + ks * 32 * kWgPitch;
+      const unsigned short* const kb = pb + ks * G::kRowsPerStep * kWgPitch;
       bf16x8 a[2];
 #pragma unroll
-      for (int m = 0; m < 2; ++m)
-        a[m] = join(tr_read(ldy, pos_lo * kWgPitch + a_col + m * 16), tr_read(ldy, pos_hi * kWgPitch + a_col + m * 16));
-      const int xr_lo = image_row<F>(pos_lo), xr_hi = image_row<F>(pos_hi);
+      for (int m = 0; m < 2; ++m) a[m] = join(tr_read(ka, m * 16), tr_read(ka, 16 * kWgPitch + m * 16));
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
-        const int shift = tap_shift<F>(tap);
-        bf16x8 bfr[2];
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-          bfr[n] = join(tr_read(lx, (xr_lo + shift) * kWgPitch + b_col + n * 16),
-                        tr_read(lx, (xr_hi + shift) * kWgPitch + b_col + n * 16));
+        const int row = tap_shift<F>(tap);
+        const bf16x8 bfr = join(tr_read(kb, row * kWgPitch), tr_read(kb, (row + G::kHighHalf) * kWgPitch));
 #pragma unroll
         for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int n = 0; n < 2; ++n)
-            acc[tap][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m], bfr[n], acc[tap][m][n], 0, 0, 0);
+          acc[tap][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m], bfr, acc[tap][m], 0, 0, 0);
       }
+      // issue order: the dy fragments and two taps' x fragments, then per tap two MFMAs and the reads of a later tap
+      // (all reads first would hold every tap's fragments in registers at once)
+      __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+      }
+      // the next chunk: requested behind the first K-group's MFMAs (which start right after the barrier), in flight
+      // during the next two, stored into the other image before the last, whose MFMAs cover the stores
+      if (more && ks == 0) load(c + 1);
+      if (more && ks == kWgKc / 32 - 2) store(other);
     }
   }
 
@@ -146,9 +205,7 @@ __global__ __launch_bounds__(kWgThreads, 2) void conv3x3_wgrad_kernel(
       const int co = co0 + wm * 32 + m * 16 + 4 * (lane >> 4) + j;
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-          slot[(static_cast<long>(co) * 9 + tap) * Cin + ci0 + wn * 32 + n * 16 + (lane & 15)] = acc[tap][m][n][j];
+        slot[(static_cast<long>(co) * 9 + tap) * Cin + ci0 + wn * 16 + (lane & 15)] = acc[tap][m][j];
     }
 }
 
@@ -199,14 +256,14 @@ bool wgrad_supported(int64_t F, int64_t Cin, int64_t Cout) {
          Cout % kWgTile == 0;
 }
 
-// K slabs: enough workgroups for two per CU, each slab at least one chunk
+// K slabs: enough workgroups for one per CU, each slab at least one chunk
 WgradPlan wgrad_plan(int64_t B, int64_t T, int64_t F, int64_t Cin, int64_t Cout, int num_cus) {
   WgradPlan pl;
   const int tc = time_rows_per_chunk(F);
   pl.chunks_per_clip = static_cast<int>((T + tc - 1) / tc);
   pl.chunks = static_cast<int>(B) * pl.chunks_per_clip;
   const long tiles = (Cin / kWgTile) * (Cout / kWgTile);
-  const long want = (2L * (num_cus > 0 ? num_cus : 256) + tiles - 1) / tiles;
+  const long want = ((num_cus > 0 ? num_cus : 256) + tiles - 1) / tiles;
   const long slabs = want < 1 ? 1 : (want > pl.chunks ? pl.chunks : want);
   pl.per_slab = static_cast<int>((pl.chunks + slabs - 1) / slabs);
   pl.slabs = (pl.chunks + pl.per_slab - 1) / pl.per_slab;

@@ -128,6 +128,71 @@ __global__ __launch_bounds__(kGlueThreads) void sum_chunks_kernel(const void* __
     if (i0 + j < count) store_from_float(out, i0 + j, out_bf16 != 0, acc[j]);
 }
 
+// sum_chunks_kernel with the columns re-ordered on the way out: partial [chunks][rows][F][C], out [rows][C][F],
+//   out[row][c * F + f] = sum_chunk partial[chunk][row][f * C + c]
+// (dW_ih of GRU layer 0: the product is formed on (frequency, channel)-ordered features, the parameter's columns are
+// (channel, frequency); this replaces the chunk sum and the strided copy behind it).  Every element is accumulated as
+// sum_chunks_kernel does -- fp32, chunks in order, one rounding -- so the result has the same bits as sum + copy.
+// A thread owns 8 consecutive channels of one row for all F frequencies: F 16-byte loads per chunk (bf16; two for
+// fp32) along c, and 8 * F consecutive outputs written as 16-byte stores.  C % 8 == 0.
+template <int F>
+__global__ __launch_bounds__(kGlueThreads) void sum_chunks_columns_kernel(const void* __restrict__ partial, int in_bf16,
+                                                                          int chunks, long rows, int C,
+                                                                          void* __restrict__ out, int out_bf16) {
+  const long i = static_cast<long>(blockIdx.x) * kGlueThreads + threadIdx.x;     // over [rows][C / 8]
+  const int groups = C / 8;
+  if (i >= rows * groups) return;
+  const long row = i / groups;
+  const int c0 = static_cast<int>(i - row * groups) * 8;
+  const long count = rows * F * C;
+  float acc[F][8];
+#pragma unroll
+  for (int f = 0; f < F; ++f)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[f][j] = 0.0f;
+  for (int c = 0; c < chunks; ++c) {
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+      const long base = static_cast<long>(c) * count + (row * F + f) * C + c0;
+      if (in_bf16) {
+        const uint4 v = *reinterpret_cast<const uint4*>(static_cast<const unsigned short*>(partial) + base);
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          acc[f][2 * j] += __uint_as_float(w[j] << 16);
+          acc[f][2 * j + 1] += __uint_as_float(w[j] & 0xffff0000u);
+        }
+      } else {
+        const float4* q = reinterpret_cast<const float4*>(static_cast<const float*>(partial) + base);
+        const float4 lo = q[0], hi = q[1];
+        acc[f][0] += lo.x; acc[f][1] += lo.y; acc[f][2] += lo.z; acc[f][3] += lo.w;
+        acc[f][4] += hi.x; acc[f][5] += hi.y; acc[f][6] += hi.z; acc[f][7] += hi.w;
+      }
+    }
+  }
+  const long o0 = (row * C + c0) * F;                               // 8 * F outputs in (c, f) order
+  if (out_bf16) {
+    unsigned packed[4 * F];
+#pragma unroll
+    for (int k = 0; k < 4 * F; ++k) {
+      const int e0 = 2 * k, e1 = 2 * k + 1;
+      packed[k] = static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(acc[e0 % F][e0 / F]))) |
+                  (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(acc[e1 % F][e1 / F]))) << 16);
+    }
+    uint4* dst = reinterpret_cast<uint4*>(static_cast<unsigned short*>(out) + o0);
+#pragma unroll
+    for (int k = 0; k < F; ++k) dst[k] = make_uint4(packed[4 * k], packed[4 * k + 1], packed[4 * k + 2], packed[4 * k + 3]);
+  } else {
+    float4* dst = reinterpret_cast<float4*>(static_cast<float*>(out) + o0);
+#pragma unroll
+    for (int k = 0; k < 2 * F; ++k) {
+      const int e = 4 * k;
+      dst[k] = make_float4(acc[e % F][e / F], acc[(e + 1) % F][(e + 1) / F], acc[(e + 2) % F][(e + 2) / F],
+                           acc[(e + 3) % F][(e + 3) / F]);
+    }
+  }
+}
+
 // partial[y][n] = sum over the rows of row block y of g[r][n]: stage 1 of a column sum of a tall matrix (the bias
 // gradient of every nn.Linear: 8000 rows x 256..9072 columns).  The framework's reduce kernel takes 16 - 36 us for these
 // shapes whatever the width (few, long threads); here the rows are cut into blocks so that ~1000 workgroups stream the
@@ -454,6 +519,30 @@ int seld_sum_chunks(const void* partial, int in_is_bf16, int64_t chunks, int64_t
     hipLaunchKernelGGL(sum_chunks_kernel<1>, dim3(static_cast<unsigned>((count + kGlueThreads - 1) / kGlueThreads)),
                        dim3(kGlueThreads), 0, stream, partial, in_is_bf16, static_cast<int>(chunks),
                        static_cast<long>(count), out, out_is_bf16);
+  }
+  SELD_HIP_TRY(hipGetLastError());
+  return kOk;
+}
+
+int seld_sum_chunks_columns(const void* partial, int in_is_bf16, int64_t chunks, int64_t rows, int64_t C, int64_t F,
+                            void* out, int out_is_bf16, void* stream_) {
+  using namespace seld;
+  if (!current_state()) return kErrNotInitialised;
+  if (chunks <= 0 || rows <= 0 || C <= 0 || !partial || !out)
+    return fail(kErrInvalidArgument, "seld_sum_chunks_columns: bad argument");
+  if (F < 2 || F > 4 || C % 8 != 0 || rows * C * F >= (1L << 40))
+    return fail(kErrUnsupported, "seld_sum_chunks_columns: F in 2..4 and C % 8 == 0 required");
+  if (((reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(out)) & 15) != 0)
+    return fail(kErrInvalidArgument, "seld_sum_chunks_columns: 16-byte aligned tensors required");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const long threads = rows * (C / 8);
+  const dim3 grid(static_cast<unsigned>((threads + kGlueThreads - 1) / kGlueThreads));
+  const int n = static_cast<int>(chunks), c = static_cast<int>(C);
+  const long r = static_cast<long>(rows);
+  switch (F) {
+    case 2: hipLaunchKernelGGL(sum_chunks_columns_kernel<2>, grid, dim3(kGlueThreads), 0, stream, partial, in_is_bf16, n, r, c, out, out_is_bf16); break;
+    case 3: hipLaunchKernelGGL(sum_chunks_columns_kernel<3>, grid, dim3(kGlueThreads), 0, stream, partial, in_is_bf16, n, r, c, out, out_is_bf16); break;
+    default: hipLaunchKernelGGL(sum_chunks_columns_kernel<4>, grid, dim3(kGlueThreads), 0, stream, partial, in_is_bf16, n, r, c, out, out_is_bf16); break;
   }
   SELD_HIP_TRY(hipGetLastError());
   return kOk;

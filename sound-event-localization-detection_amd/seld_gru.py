@@ -101,12 +101,8 @@ class _BiGRULayer(torch.autograd.Function):
                 for db, full in zip((db_ih, db_hh), fp32):
                     if db is not full:
                         db.copy_(full)
-                if ctx.feature_cf is None:
-                    tall_product(dgi2, x2, out=dw_ih)                            # [6H, In]
-                else:                                                            # columns back to (channel, frequency)
-                    c, f = ctx.feature_cf
-                    perm = tall_product(dgi2, x2, out_dtype=t_wih)
-                    dw_ih.view(6 * h, c, f).copy_(perm.view(6 * h, f, c).transpose(1, 2))
+                # [6H, In]; with feature_cf the chunk sum writes the columns back in (channel, frequency) order
+                tall_product(dgi2, x2, out=dw_ih, columns_cf=ctx.feature_cf)
                 # h_{t-1} of the forward recurrence: y shifted by one step in each direction's own time order
                 hp = seld_native.gru_previous_state(y).view(n, 2 * h)
                 # d/d(gh) = (da_r, da_z, da_n * r).  Two well-shaped products instead of eight skinny ones: all of

@@ -52,18 +52,30 @@ def abandon_batch():
     _batch = None
 
 
-def tall_product(a, c, out_dtype=torch.float32, out=None, queue=False):
+def tall_product(a, c, out_dtype=torch.float32, out=None, queue=False, columns_cf=None):
     """a^T c for tall operands (a [N, G], c [N, K]) -> [G, K] in ``out_dtype``.  Row strides may be anything (column
     stride 1).  The library's transposed-A GEMM with an 8000-row reduction runs at a fraction of its usual rate, the
     more so the smaller the output (measured, bf16, N = 8000, tools/bench_tall_product.py: 9072 x 512 125 us as one
     GEMM vs 95 us in 5 row chunks; 1536 x 2048 93 vs 76; 512 x 512 52 vs 27 in 8): the rows are split into chunks
     multiplied as ONE batched GEMM on transposed views (no copies) and the partial products are added by a reduction
-    that accumulates in fp32 and writes ``out_dtype`` directly (into ``out`` if given)."""
+    that accumulates in fp32 and writes ``out_dtype`` directly (into ``out`` if given).
+    ``columns_cf = (C, F)``: c's K = F * C columns are ordered f * C + c; the result's are ordered c * F + f (the
+    reduction writes them there: no permuted copy behind it).  The mapped reduction is launched at once: it has no
+    place in the batched launch ``queue`` asks for, so the two together are refused."""
+    if queue and columns_cf is not None:
+        raise ValueError("tall_product: columns_cf cannot be combined with queue=True")
     n, g = a.shape
     k = c.shape[1]
     chunks = chunk_count(n, g, k)
+
+    def permuted(prod, dst):                                    # [G, (f, c)] -> [G, (c, f)]
+        cc, ff = columns_cf
+        dst.view(g, cc, ff).copy_(prod.view(g, ff, cc).transpose(1, 2))
+        return dst
     if chunks == 1:
         prod = a.t() @ c
+        if columns_cf is not None:
+            return permuted(prod, out if out is not None else torch.empty((g, k), dtype=out_dtype, device=a.device))
         if out is not None:
             return out.copy_(prod)
         return prod if prod.dtype == out_dtype else prod.to(out_dtype)
@@ -72,11 +84,16 @@ def tall_product(a, c, out_dtype=torch.float32, out=None, queue=False):
         out = torch.empty((g, k), dtype=out_dtype, device=a.device)
     if partial.is_cuda and out.is_contiguous() and partial.dtype in (torch.float32, torch.bfloat16) \
             and out.dtype in (torch.float32, torch.bfloat16):
+        if columns_cf is not None:
+            import seld_native
+            return seld_native.sum_chunks(partial, out, columns_cf=columns_cf)
         if queue and _batch is not None:
             _batch["sums"].append((partial, out))            # filled by flush_batch (``queue``: the caller allows it)
             return out
         import seld_native
         return seld_native.sum_chunks(partial, out)          # one launch (torch.sum(out=) is fill + reduce + copy)
+    if columns_cf is not None:
+        return permuted(torch.sum(partial, dim=0, dtype=out.dtype), out)
     return torch.sum(partial, dim=0, dtype=out.dtype, out=out)
 
 

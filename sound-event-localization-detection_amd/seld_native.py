@@ -94,6 +94,7 @@ def _declare(lib):
     lib.seld_gru_prepare.argtypes = [_ptr, _ptr, _ptr, _int, _i64, _ptr, _int, _ptr, _ptr, _ptr]
     lib.seld_gru_bias_grads.argtypes = [_ptr, _i64, _i64, _ptr, _ptr, _ptr]
     lib.seld_sum_chunks.argtypes = [_ptr, _int, _i64, _i64, _ptr, _int, _ptr]
+    lib.seld_sum_chunks_columns.argtypes = [_ptr, _int, _i64, _i64, _i64, _i64, _ptr, _int, _ptr]
     lib.seld_gru_dwhh_finish.argtypes = [_ptr, _ptr, _int, _i64, _i64, _ptr, _int, _ptr]
     lib.seld_column_sums.argtypes = [_ptr, _int, _i64, _i64, _ptr, _ptr, _int, _ptr]
     _pp, _pi64, _pi32 = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
@@ -1327,14 +1328,24 @@ def gru_bias_grads(partial: torch.Tensor, out=None):
     return out[0], out[1]
 
 
-def sum_chunks(partial: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-    """out[...] = partial.sum(dim=0) accumulated in fp32 (partial [chunks, ...] contiguous bf16 / fp32; out contiguous)."""
+def sum_chunks(partial: torch.Tensor, out: torch.Tensor, columns_cf=None) -> torch.Tensor:
+    """out[...] = partial.sum(dim=0) accumulated in fp32 (partial [chunks, ...] contiguous bf16 / fp32; out contiguous).
+    ``columns_cf = (C, F)``: partial is [chunks, rows, F * C] with columns ordered f * C + c and out [rows, C * F] gets
+    them ordered c * F + f -- the same bits as the plain sum followed by that column permutation, in one launch."""
     if not (partial.is_cuda and partial.is_contiguous() and out.is_contiguous()
             and tuple(partial.shape[1:]) == tuple(out.shape)):
         raise SeldNativeError("sum_chunks: partial [chunks, ...] and out [...] must be contiguous with matching shapes")
     with _device_guard(ensure_init(partial.device)):
-        check(load_library().seld_sum_chunks(_p(partial), _is_bf16(partial), partial.shape[0], out.numel(), _p(out),
-                                             _is_bf16(out), _stream_ptr(partial.device)), "seld_sum_chunks")
+        if columns_cf is None:
+            check(load_library().seld_sum_chunks(_p(partial), _is_bf16(partial), partial.shape[0], out.numel(), _p(out),
+                                                 _is_bf16(out), _stream_ptr(partial.device)), "seld_sum_chunks")
+        else:
+            c, f = columns_cf
+            if out.dim() != 2 or out.shape[1] != c * f:
+                raise SeldNativeError("sum_chunks: columns_cf = (C, F) needs out [rows, C * F]")
+            check(load_library().seld_sum_chunks_columns(_p(partial), _is_bf16(partial), partial.shape[0], out.shape[0],
+                                                         c, f, _p(out), _is_bf16(out), _stream_ptr(partial.device)),
+                  "seld_sum_chunks_columns")
     return out
 
 
