@@ -229,6 +229,23 @@ int seld_softmax_mse(const void* logits, int logits_is_bf16, const uint16_t* mas
                      int64_t n_cells, int num_classes, float grad_scale, float* loss_out, void* grad,
                      void* workspace, void* stream);
 
+/* ---- loss: loss.py:27-41 class_ce_loss (+ its backward), optional focal factor (csrc/loss_ce.hip) ---- */
+/* logits and labels as seld_softmax_mse (16-byte aligned).  The target t of a cell is the first maximal dense label
+ * (torch.argmax) or, for a mask m, the lowest set bit of m & 0x3fff, background (13) if there is none.  class_weights: 14 fp32
+ * on the DEVICE, or NULL for all ones.  With p = softmax(z), q = sum_{c != t} p_c, W = sum_cells w_t:
+ *   out[0] = (1/W) sum_cells w_t q^gamma (-log p_t)      out[1] = W
+ *   grad   = grad_scale (w_t / W) f (p_k - [k = t]),  f = q^gamma - gamma p_t q^(gamma-1) log p_t   (if grad != NULL)
+ * focal_gamma = 0 is nn.CrossEntropyLoss(weight = class_weights) and runs a kernel without the focal arithmetic; otherwise
+ * focal_gamma >= 1 (finite).  A cell with q == 0 contributes nothing.  The host never reads W: four launches, capturable,
+ * deterministic (integer class counts, fixed-order double sums, no global atomics).
+ * workspace: seld_softmax_ce_workspace_bytes() bytes of device scratch.
+ * -4: num_classes != 14, n_cells * 14 at or above the limit of seld_softmax_mse; -1: n_cells <= 0, a NULL logits / out /
+ * workspace, both or neither of mask / dense_labels, focal_gamma negative, non-finite or in (0, 1). */
+int64_t seld_softmax_ce_workspace_bytes(void);
+int seld_softmax_ce(const void* logits, int logits_is_bf16, const uint16_t* mask, const float* dense_labels,
+                    int64_t n_cells, int num_classes, const float* class_weights, float focal_gamma, float grad_scale,
+                    float* out, void* grad, void* workspace, void* stream);
+
 /* data[0..n) *= *scale with the scale read from DEVICE memory (the upstream gradient autograd hands the loss):
  * when it is exactly 1.0 -- what loss.backward() passes -- every block returns after one load and the data is not
  * touched.  n must be a multiple of 8; data bf16 when is_bf16, else fp32, 16-byte aligned. */

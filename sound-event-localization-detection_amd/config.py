@@ -89,7 +89,10 @@ class Config:
     # ==== MI355X additions (not in the reference) ==========================================
     AMP_DTYPE = "bf16"          # autocast dtype on ROCm devices: 'bf16' or 'fp32'
     CHANNELS_LAST = True        # NHWC conv blocks (MIOpen/hipBLASLt MFMA path)
-    FUSED_LOSS = True           # seld_softmax_mse instead of softmax + mse_loss + autograd
+    FUSED_LOSS = True           # seld_softmax_mse / seld_softmax_ce instead of softmax + mse_loss / cross_entropy + autograd
+    CE_FOCAL_GAMMA = 0.0        # LOSS_TYPE 'ce': 0 = the reference's weighted cross-entropy; >= 1 multiplies every cell's term
+                                # by (summed probability of the classes other than its target)^gamma, which takes weight off
+                                # the ~97 % of grid cells that are easy background (values in (0, 1) are refused)
     FUSED_CONV_TAIL = True      # BatchNorm -> ReLU -> MaxPool of the CNN blocks in two HBM passes (csrc/convtail.hip)
     CONV_DGRAD_AS_FORWARD = True  # encoder 3x3 convs: data gradient as a forward conv with transposed, flipped weights
     FUSED_CONV_WGRAD = True     # encoder 3x3 convs: weight gradient by the HIP split-K MFMA kernel (csrc/convwgrad.hip),

@@ -3,7 +3,8 @@ w_cl, grid_size, class_weights)``; ``forward(y_pred, y_true) -> (loss tensor, {n
 
 Active term (loss.py:149-172): ``w_class * class_loss`` where class_loss is
   'mse' : mean((softmax(logits) - y)^2)             loss.py:43-54   -> fused HIP kernel on ROCm devices
-  'ce'  : weighted CrossEntropy(argmax(y))          loss.py:27-41   -> stock ops
+  'ce'  : weighted CrossEntropy(argmax(y))          loss.py:27-41   -> fused HIP kernel on ROCm devices (csrc/loss_ce.hip);
+          ``focal_gamma`` > 0 multiplies every cell's term by (probability of the other classes)^gamma
 The AIUR and converging-localisation terms (loss.py:56-146) are, like upstream, not part of ``forward`` by default;
 ``three_term=True`` (Config.THREE_TERM_LOSS) sums all three on the probabilities as the reference's
 ``smrl_seld_gaussian.py:946-1072`` does -- on a ROCm device in one fused pass (csrc/loss3.hip).
@@ -39,6 +40,26 @@ class _FusedSoftmaxMSE(torch.autograd.Function):
         return seld_native.scale_by_device_scalar_(grad, grad_out), None
 
 
+class _FusedSoftmaxCE(torch.autograd.Function):
+    """loss and d(loss)/d(logits) from one call of seld_softmax_ce (csrc/loss_ce.hip); the gradient is computed in the forward
+    and scaled by the upstream gradient exactly as _FusedSoftmaxMSE does."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, class_weights, focal_gamma):
+        import seld_native
+        loss, grad = seld_native.softmax_ce(logits, labels, class_weights, focal_gamma,
+                                            grad_scale=1.0 if logits.requires_grad else None)
+        ctx.save_for_backward(grad if grad is not None else torch.empty(0))
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        import seld_native
+        (grad,) = ctx.saved_tensors
+        return seld_native.scale_by_device_scalar_(grad, grad_out), None, None, None
+
+
 class _FusedThreeTerm(torch.autograd.Function):
     """total = w_class * MSE + w_aiur * AIUR + w_cl * CL and d(total)/d(logits) from one pass (csrc/loss3.hip);
     returns the four scalars (total, mse, aiur, cl) as one tensor -- only element 0 carries a gradient."""
@@ -70,12 +91,18 @@ class SMRSELDLoss(nn.Module):
     fused_enabled = True     # flipped by the trainer from Config.FUSED_LOSS
 
     def __init__(self, loss_type="ce", w_class=1.0, w_aiur=0.5, w_cl=0.5, grid_size=None, class_weights=None,
-                 three_term=False):
-        """``three_term``: total = w_class * class + w_aiur * AIUR + w_cl * CL, the auxiliary terms on the probabilities,
+                 three_term=False, focal_gamma=0.0):
+        """``focal_gamma``: 0 (plain cross-entropy) or >= 1; the 'ce' term of a cell becomes q^gamma * (-log p_t) with q the
+        summed probability of the classes other than the target t (Config.CE_FOCAL_GAMMA), still divided by the sum of the
+        cells' class weights.
+        ``three_term``: total = w_class * class + w_aiur * AIUR + w_cl * CL, the auxiliary terms on the probabilities,
         as smrl_seld_gaussian.py:1058-1072 sums them (upstream's modular loss.py keeps them commented out of ``forward``,
         loss.py:158-166: the default here).  Config.THREE_TERM_LOSS selects it in the trainer."""
         super().__init__()
         self.three_term = bool(three_term)
+        self.focal_gamma = float(focal_gamma)
+        if not (self.focal_gamma == 0.0 or 1.0 <= self.focal_gamma < math.inf):
+            raise ValueError("focal_gamma must be 0 or a finite value >= 1 (q^(gamma-1) is unbounded for 0 < gamma < 1)")
         self.last_terms = None               # device tensor (total, class, aiur, cl) of the last three-term evaluation
         self.loss_type = loss_type
         self.w_class = w_class
@@ -89,10 +116,23 @@ class SMRSELDLoss(nn.Module):
     def _dense(self, y_true, num_classes):
         return mask_to_dense(y_true, num_classes) if y_true.dtype == torch.uint16 else y_true
 
-    def class_ce_loss(self, y_pred, y_true):
+    def class_ce_loss(self, y_pred, y_true, fused=True):
         m = y_pred.shape[-1]
-        target = torch.argmax(self._dense(y_true, m), dim=-1)
-        return self.ce_loss(y_pred.reshape(-1, m).float(), target.reshape(-1))
+        if fused and y_pred.is_cuda and self.fused_enabled and m == 14 and y_pred.dtype in (torch.float32, torch.bfloat16):
+            labels = y_true if y_true.dtype == torch.uint16 else y_true.to(torch.float32)
+            return _FusedSoftmaxCE.apply(y_pred, labels, self.ce_loss.weight, self.focal_gamma)
+        target = torch.argmax(self._dense(y_true, m), dim=-1).reshape(-1)
+        logits = y_pred.reshape(-1, m).float()
+        if self.focal_gamma == 0.0:
+            return self.ce_loss(logits, target)
+        # the focal form in plain torch: what the kernel computes, and its yardstick in the tests
+        log_p = F.log_softmax(logits, dim=-1)
+        is_target = F.one_hot(target, m).bool()
+        log_pt = log_p.gather(1, target.unsqueeze(1)).squeeze(1)
+        q = log_p.exp().masked_fill(is_target, 0.0).sum(dim=-1)      # the other classes' probabilities, not 1 - p_t
+        cell = torch.where(q > 0, q.pow(self.focal_gamma) * -log_pt, torch.zeros_like(q))
+        w = self.ce_loss.weight[target].to(cell.dtype) if self.ce_loss.weight is not None else torch.ones_like(cell)
+        return (w * cell).sum() / w.sum()
 
     def class_mse_loss(self, y_pred, y_true):
         if y_pred.is_cuda and self.fused_enabled and y_pred.shape[-1] == 14 \
@@ -147,7 +187,7 @@ class SMRSELDLoss(nn.Module):
             return terms[0], terms[1].detach()
         dense = self._dense(y_true, y_pred.shape[-1]).float()
         probs = F.softmax(y_pred.float(), dim=-1)
-        term = F.mse_loss(probs, dense) if self.loss_type == "mse" else self.class_ce_loss(y_pred, y_true)
+        term = F.mse_loss(probs, dense) if self.loss_type == "mse" else self.class_ce_loss(y_pred, y_true, fused=False)
         aiur = self.aiur_loss(probs, dense)
         cl = self.converging_localization_loss(probs, dense)
         total = self.w_class * term + self.w_aiur * aiur + self.w_cl * cl

@@ -83,6 +83,10 @@ def _declare(lib):
     lib.seld_softmax_mse_workspace_bytes.restype = _i64
     lib.seld_softmax_mse_workspace_bytes.argtypes = []
     lib.seld_softmax_mse.argtypes = [_ptr, _int, _ptr, _ptr, _i64, _int, ctypes.c_float, _ptr, _ptr, _ptr, _ptr]
+    lib.seld_softmax_ce_workspace_bytes.restype = _i64
+    lib.seld_softmax_ce_workspace_bytes.argtypes = []
+    lib.seld_softmax_ce.argtypes = [_ptr, _int, _ptr, _ptr, _i64, _int, _ptr, ctypes.c_float, ctypes.c_float, _ptr, _ptr,
+                                    _ptr, _ptr]
     lib.seld_scale_by_device_scalar.argtypes = [_ptr, _int, _i64, _ptr, _ptr]
     lib.seld_smr_loss_workspace_bytes.restype = _i64
     lib.seld_smr_loss_workspace_bytes.argtypes = [_i64, _i64]
@@ -657,6 +661,18 @@ def _workspace(device) -> torch.Tensor:
     return ws
 
 
+def _class_labels(name: str, logits: torch.Tensor, labels: torch.Tensor, n_cells: int):
+    """(labels contiguous, mask pointer, dense pointer) of a class-loss call: exactly one pointer is not None."""
+    labels = labels.contiguous()
+    if labels.dtype == torch.uint16:
+        if labels.numel() != n_cells:
+            raise ValueError(f"{name}: mask shape does not match logits")
+        return labels, _p(labels), None
+    if labels.dtype != torch.float32 or labels.numel() != logits.numel():
+        raise ValueError(f"{name}: dense labels must be float32 with the logits' shape")
+    return labels, None, _p(labels)
+
+
 def softmax_mse(logits: torch.Tensor, labels: torch.Tensor, grad_scale: float | None = None):
     """loss.py:43-54 fused.  ``labels``: uint16 mask [...cells] or dense float32 [...cells, 14].
     Returns (loss scalar tensor, grad or None); grad has the dtype/shape of ``logits``."""
@@ -668,15 +684,7 @@ def softmax_mse(logits: torch.Tensor, labels: torch.Tensor, grad_scale: float | 
     m = logits.shape[-1]
     n_cells = logits.numel() // m
     index = ensure_init(logits.device)
-    labels = labels.contiguous()
-    if labels.dtype == torch.uint16:
-        if labels.numel() != n_cells:
-            raise ValueError("softmax_mse: mask shape does not match logits")
-        mask_p, dense_p = _p(labels), None
-    else:
-        if labels.dtype != torch.float32 or labels.numel() != logits.numel():
-            raise ValueError("softmax_mse: dense labels must be float32 with the logits' shape")
-        mask_p, dense_p = None, _p(labels)
+    labels, mask_p, dense_p = _class_labels("softmax_mse", logits, labels, n_cells)
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     grad = torch.empty_like(logits) if grad_scale is not None else None
     with _device_guard(index):
@@ -685,6 +693,47 @@ def softmax_mse(logits: torch.Tensor, labels: torch.Tensor, grad_scale: float | 
                                               _p(_workspace(logits.device)), _stream_ptr(logits.device)),
               "seld_softmax_mse")
     return loss[0], grad
+
+
+_ce_workspaces = {}
+
+
+def softmax_ce(logits: torch.Tensor, labels: torch.Tensor, class_weights: torch.Tensor | None = None,
+               focal_gamma: float = 0.0, grad_scale: float | None = None, return_weight_sum: bool = False):
+    """loss.py:27-41 fused (csrc/loss_ce.hip): weighted cross-entropy against the labels' argmax, times q^focal_gamma with
+    q the probability of the other classes (focal_gamma = 0: nn.CrossEntropyLoss(weight=class_weights)).  ``labels``: uint16
+    mask [...cells] or dense float32 [...cells, 14]; ``class_weights``: 14 values on the logits' device, or None for ones.
+    Returns (loss scalar tensor, grad or None[, W = sum of the cells' weights]); grad = grad_scale * d(loss)/d(logits) has the
+    dtype/shape of ``logits``.  Nothing is read back: the call can be captured."""
+    if not logits.is_cuda:
+        raise SeldNativeError("softmax_ce: logits must be a GPU tensor")
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("softmax_ce: logits must be float32 or bfloat16")
+    logits = logits.contiguous()
+    m = logits.shape[-1]
+    n_cells = logits.numel() // m
+    index = ensure_init(logits.device)
+    if logits.data_ptr() % 16:                # a view into a larger buffer: the kernels move 16-byte pieces
+        logits = logits.clone()
+    if labels.dtype != torch.uint16 and labels.is_contiguous() and labels.data_ptr() % 16:
+        labels = labels.clone()
+    labels, mask_p, dense_p = _class_labels("softmax_ce", logits, labels, n_cells)
+    if class_weights is not None:
+        if class_weights.device != logits.device or class_weights.numel() != m:
+            raise ValueError(f"softmax_ce: class_weights must be {m} values on the logits' device")
+        class_weights = class_weights.detach().to(torch.float32).contiguous()
+    key = (logits.device.type, logits.device.index)
+    ws = _ce_workspaces.get(key)
+    if ws is None:
+        ws = _ce_workspaces[key] = torch.empty(load_library().seld_softmax_ce_workspace_bytes(), dtype=torch.uint8,
+                                               device=logits.device)
+    out = torch.empty(2, dtype=torch.float32, device=logits.device)
+    grad = torch.empty_like(logits) if grad_scale is not None else None
+    with _device_guard(index):
+        check(load_library().seld_softmax_ce(_p(logits), int(logits.dtype == torch.bfloat16), mask_p, dense_p, n_cells, m,
+                                             _p(class_weights), float(focal_gamma), float(grad_scale or 0.0), _p(out),
+                                             _p(grad), _p(ws), _stream_ptr(logits.device)), "seld_softmax_ce")
+    return (out[0], grad, out[1]) if return_weight_sum else (out[0], grad)
 
 
 def smr_loss(logits: torch.Tensor, labels: torch.Tensor, grid, w_class: float, w_aiur: float, w_cl: float,
