@@ -217,6 +217,42 @@ int seld_window_gather_rotate(const float* src, const float* rot, int64_t total_
 int seld_window_permute_mask_rotate(const uint16_t* src, int64_t total_rows, int I, int J, const int64_t* starts,
                                     const int32_t* params, int64_t B, int64_t window, uint16_t* dst, void* stream);
 
+/* ---- per-bin feature standardisation (csrc/standardise.hip and the three gathers) ------------- */
+/* Moments of a time-major feature timeline src float32 [total_rows][channels][64]:
+ *   moments double [2][channels][64] = (sum over the frames of x, sum over the frames of x * x)   per column (c, f).
+ * The summation order is FIXED, so the result is the same bits on every grid, CU count and device (every rank of a
+ * data-parallel run computes it from its own copy of the timeline and they agree without a collective):
+ *   - the timeline is cut into slabs of SELD_MOMENT_SLAB_FRAMES frames (the last one ragged);
+ *   - a slab's partial of a column is the fp64 sum over its frames in ascending order, starting from 0.0;
+ *   - the result is the fp64 sum of the slab partials in ascending slab order, starting from 0.0;
+ *   - x is widened to fp64 first; the squared term is the fp64 product x * x (exact for an fp32 x), added unfused.
+ * A grid-stride kernel writes the slab partials to `workspace` (seld_feature_moments_workspace bytes), a second one folds
+ * them; no atomics, no device-scope fence; the timeline is read once.  No allocation, no synchronisation.
+ * total_rows <= 0 (there are no statistics of an empty timeline), channels <= 0, a null pointer or a workspace smaller
+ * than reported: -1. */
+#define SELD_MOMENT_SLAB_FRAMES 1024
+int64_t seld_feature_moments_workspace(int64_t total_rows, int channels);   /* bytes; 0 for extents that are refused */
+int seld_feature_moments(const float* src, int64_t total_rows, int channels, double* moments, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+
+/* The three feature gathers above with one affine map per (OUTPUT channel c, bin f): scale and shift are float32
+ * [channels][64] on the device.  With v the fp32 value the gather of the same name without `_affine` writes for an element
+ * (after the signed channel copy, or the rotated log-mel / intensity computation), these write
+ *   fmaf(v, scale[c][f], shift[c][f])      (one fused multiply-add in fp32),
+ * the time and frequency masks are applied AFTERWARDS (a masked element is exactly mask_value) and rows outside
+ * [0, total_rows) stay +0.0 over the whole row.  Everything else -- refusals, their order, the parameter rows, graph-capture
+ * safety -- as the gather of the same name; scale and shift are refused with the other pointers. */
+int seld_window_gather_affine(const float* src, int64_t total_rows, int channels, const int64_t* starts, int64_t B,
+                              int64_t window, const float* scale, const float* shift, float* dst, void* stream);
+int seld_window_gather_augment_affine(const float* src, int64_t total_rows, int channels, int freq_channels,
+                                      const int64_t* starts, const int32_t* params, int64_t B, int64_t window,
+                                      const uint8_t* channel_table, float mask_value, const float* scale,
+                                      const float* shift, float* dst, void* stream);
+int seld_window_gather_rotate_affine(const float* src, const float* rot, int64_t total_rows, int channels, int freq_channels,
+                                     int ch_x, int ch_y, int ch_z, int J, const int64_t* starts, const int32_t* params,
+                                     int64_t B, int64_t window, const uint8_t* channel_table, float mask_value,
+                                     const float* scale, const float* shift, float* dst, void* stream);
+
 /* ---- loss: loss.py:43-54 class_mse_loss (+ its backward) ---------------------------------- */
 /* logits [n_cells][14] (fp32, or bf16 when logits_is_bf16), labels as EITHER the compact mask
  * (uint16 [n_cells]) OR dense float32 [n_cells][14] (exactly one non-NULL).  Writes

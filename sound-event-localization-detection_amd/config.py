@@ -170,6 +170,14 @@ class Config:
     AUGMENT_FREQ_MASK_MAX = 0   # widest frequency mask in mel bins
     AUGMENT_MASK_VALUE = 0.0    # what masked elements are set to (0.0 = what tail windows are padded with)
     FOA_CHANNEL_ORDER = "WYZX"  # which input channel is which: 'WYZX' (STARSS / DCASE FOA recordings) or 'WXYZ'
+    # Per-bin feature standardisation inside the device window gathers (seld_standardise.py, csrc/standardise.hip; DESIGN.md
+    # section 22).  Off by default: every entry point, checkpoint and benchmark figure is then what it was
+    STANDARDISE_FEATURES = False  # train_model reduces mean / std of every (channel, mel bin or lag) over the TRAINING timeline
+                                # on the device, both datasets' gathers then write (x - mean) / std -- after the augmentation
+                                # transform, before the SpecAugment masks -- and every checkpoint carries the statistics under
+                                # 'feature_statistics'; test_model / evaluate_seld / infer.py apply a checkpoint's statistics
+                                # whenever it holds them (with the switch on and none in the checkpoint: an error).  Needs
+                                # DEVICE_FEED like the augmentation switches (the host DataLoader path refuses to run)
     # Guarded optimiser update (csrc/guard.hip, csrc/adam.hip).  All off by default; device-side, inside
     # the one-launch update, so they need the master-weight path (bf16 autocast on a ROCm device): make_optimizer refuses
     # a switched-on guard anywhere else

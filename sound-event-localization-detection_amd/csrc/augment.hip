@@ -22,10 +22,14 @@
 namespace seld {
 
 // dst[b][w][c][f] = sign * src[starts[b] + w][srcch[c]][f], then the masks; rows past the timeline stay zero.
+// kAffine (seld_window_gather_augment_affine): the copied value goes through scale / shift [channels][64] of the OUTPUT
+// channel c before the masks (augment_core.h, standardised); the other instantiation never looks at the two pointers.
+template <bool kAffine>
 __global__ void __launch_bounds__(256)
 gather_augment_kernel(const uint4* __restrict__ src, long total_rows, int channels, int freq_channels,
                       const int64_t* __restrict__ starts, const int32_t* __restrict__ params, long B, int window,
-                      const ChannelTable table, unsigned mask_bits, uint4* __restrict__ dst) {
+                      const ChannelTable table, unsigned mask_bits, const uint4* __restrict__ scale,
+                      const uint4* __restrict__ shift, uint4* __restrict__ dst) {
   const int row_chunks = channels * kChunksPerChannel;
   const int per_window = window * row_chunks;                       // host: < 2^31
   for (long b = blockIdx.y; b < B; b += gridDim.y) {
@@ -44,7 +48,8 @@ gather_augment_kernel(const uint4* __restrict__ src, long total_rows, int channe
       uint4 v = make_uint4(0u, 0u, 0u, 0u);
       if (srow >= 0 && srow < total_rows) {
         const unsigned entry = channels <= 8 ? packed_entry(packed, c) : table.e[prm.pattern][c];
-        v = masked(signed_copy(src + srow * row_chunks, entry, fc), w, c, fc, prm, freq_channels, mask_bits);
+        v = standardised<kAffine>(signed_copy(src + srow * row_chunks, entry, fc), scale, shift, chunk);
+        v = masked(v, w, c, fc, prm, freq_channels, mask_bits);
       }
       to[q] = v;
     }
@@ -104,6 +109,32 @@ permute_mask_kernel(const uint16_t* __restrict__ src, long total_rows, int I, in
   }
 }
 
+// the two feature entry points
+template <bool kAffine>
+static int gather_augment(const char* who, const float* src, int64_t total_rows, int channels, int freq_channels,
+                          const int64_t* starts, const int32_t* params, int64_t B, int64_t window,
+                          const uint8_t* channel_table, float mask_value, const float* scale, const float* shift, float* dst,
+                          void* stream_) {
+  DeviceState* st;
+  const int64_t row_chunks = static_cast<int64_t>(channels) * kChunksPerChannel;
+  const bool extents_ok = channels > 0 && freq_channels >= 0 && freq_channels <= channels;
+  const Refusal many{channels > kMaxChannels, kErrUnsupported, "more than SELD_AUGMENT_MAX_CHANNELS feature channels"};
+  const int rc = kAffine ? check_window_args(who, total_rows, B, window, extents_ok, {many}, row_chunks,
+                                             {src, starts, params, scale, shift, dst}, &st)
+                         : check_window_args(who, total_rows, B, window, extents_ok, {many}, row_chunks,
+                                             {src, starts, params, dst}, &st);
+  if (rc != kOk || B == 0) return rc;
+  ChannelTable table;
+  if (const int bad = fill_channel_table(who, channel_table, channels, &table)) return bad;
+  hipLaunchKernelGGL(gather_augment_kernel<kAffine>, window_grid(window * row_chunks, B, st->num_cus), dim3(256), 0,
+                     static_cast<hipStream_t>(stream_), reinterpret_cast<const uint4*>(src), static_cast<long>(total_rows),
+                     channels, freq_channels, starts, params, static_cast<long>(B), static_cast<int>(window), table,
+                     mask_bits(mask_value), reinterpret_cast<const uint4*>(scale), reinterpret_cast<const uint4*>(shift),
+                     reinterpret_cast<uint4*>(dst));
+  SELD_HIP_TRY(hipGetLastError());
+  return kOk;
+}
+
 // the two label entry points
 template <bool kStep>
 static int permute_mask(const char* who, const uint16_t* src, int64_t total_rows, int I, int J, const int64_t* starts,
@@ -130,23 +161,16 @@ extern "C" {
 int seld_window_gather_augment(const float* src, int64_t total_rows, int channels, int freq_channels, const int64_t* starts,
                                const int32_t* params, int64_t B, int64_t window, const uint8_t* channel_table,
                                float mask_value, float* dst, void* stream_) {
-  using namespace seld;
-  const char* who = "seld_window_gather_augment";
-  DeviceState* st;
-  const int64_t row_chunks = static_cast<int64_t>(channels) * kChunksPerChannel;
-  const int rc = check_window_args(
-      who, total_rows, B, window, channels > 0 && freq_channels >= 0 && freq_channels <= channels,
-      {{channels > kMaxChannels, kErrUnsupported, "more than SELD_AUGMENT_MAX_CHANNELS feature channels"}}, row_chunks,
-      {src, starts, params, dst}, &st);
-  if (rc != kOk || B == 0) return rc;
-  ChannelTable table;
-  if (const int bad = fill_channel_table(who, channel_table, channels, &table)) return bad;
-  hipLaunchKernelGGL(gather_augment_kernel, window_grid(window * row_chunks, B, st->num_cus), dim3(256), 0,
-                     static_cast<hipStream_t>(stream_), reinterpret_cast<const uint4*>(src), static_cast<long>(total_rows),
-                     channels, freq_channels, starts, params, static_cast<long>(B), static_cast<int>(window), table,
-                     mask_bits(mask_value), reinterpret_cast<uint4*>(dst));
-  SELD_HIP_TRY(hipGetLastError());
-  return kOk;
+  return seld::gather_augment<false>("seld_window_gather_augment", src, total_rows, channels, freq_channels, starts, params, B,
+                                     window, channel_table, mask_value, nullptr, nullptr, dst, stream_);
+}
+
+int seld_window_gather_augment_affine(const float* src, int64_t total_rows, int channels, int freq_channels,
+                                      const int64_t* starts, const int32_t* params, int64_t B, int64_t window,
+                                      const uint8_t* channel_table, float mask_value, const float* scale,
+                                      const float* shift, float* dst, void* stream_) {
+  return seld::gather_augment<true>("seld_window_gather_augment_affine", src, total_rows, channels, freq_channels, starts,
+                                    params, B, window, channel_table, mask_value, scale, shift, dst, stream_);
 }
 
 int seld_window_permute_mask(const uint16_t* src, int64_t total_rows, int I, int J, const int64_t* starts,

@@ -1,6 +1,7 @@
 // What the window gathers share (labels.hip: the plain gather; augment.hip: the 16 sign-and-swap transforms and the label
 // permutation; rotate.hip: the same features with azimuth steps): the per-window parameter row, the mask test, the signed
-// channel copy, the by-value channel table, the launch grid and the host prologue of the five entry points.
+// channel copy, the standardising map of their kAffine instantiations, the by-value channel table, the launch grid and the
+// host prologue of the eight entry points.
 //
 // The two feature kernels stay two kernels: gather_rotate_kernel walks units, takes three by-value tables and needs 44
 // VGPRs against gather_augment_kernel's 16, so folding them would make the default training path pay for the rotating one.
@@ -68,6 +69,23 @@ __device__ __forceinline__ uint4 signed_copy(const uint4* __restrict__ row, unsi
   return v;
 }
 
+// The standardising instantiations of the three feature kernels (kAffine): fmaf(v, scale, shift) on the
+// four floats of a chunk, `entry` the chunk's place in the [channels][64] tables = output channel * kChunksPerChannel + fc.
+// Two 16-byte loads of tables that stay in cache (at most 18 KB); called in front of masked(), so a masked element is
+// exactly the mask value.  The other instantiation is the kernel as it was: nothing is loaded and v comes back untouched.
+template <bool kAffine>
+__device__ __forceinline__ uint4 standardised(uint4 v, const uint4* __restrict__ scale, const uint4* __restrict__ shift,
+                                              int entry) {
+  if constexpr (kAffine) {
+    const uint4 s = scale[entry], b = shift[entry];
+    v.x = __float_as_uint(fmaf(__uint_as_float(v.x), __uint_as_float(s.x), __uint_as_float(b.x)));
+    v.y = __float_as_uint(fmaf(__uint_as_float(v.y), __uint_as_float(s.y), __uint_as_float(b.y)));
+    v.z = __float_as_uint(fmaf(__uint_as_float(v.z), __uint_as_float(s.z), __uint_as_float(b.z)));
+    v.w = __float_as_uint(fmaf(__uint_as_float(v.w), __uint_as_float(s.w), __uint_as_float(b.w)));
+  }
+  return v;
+}
+
 // the time / frequency masks on one 16-byte chunk (bins 4 fc .. 4 fc + 3) of frame w of output channel c
 __device__ __forceinline__ uint4 masked(uint4 v, int w, int c, int fc, const WindowParams& prm, int freq_channels,
                                         unsigned mask_bits) {
@@ -116,7 +134,7 @@ static inline dim3 window_grid(long per_window, long B, int num_cus) {
   return dim3(static_cast<unsigned>(x), static_cast<unsigned>(y));
 }
 
-// ---- the host prologue of the five entry points ---------------------------------------------------------------------------
+// ---- the host prologue of the eight entry points ---------------------------------------------------------------------------
 struct Refusal {        // one of an entry point's own conditions: refused with `code` and "<entry point>: <why>" when `hit`
   bool hit;
   int code;

@@ -108,8 +108,12 @@ __global__ void expand_kernel(const uint16_t* __restrict__ mask, long n_cells, i
 
 // Row gather: dst[b][w][:] = src[starts[b] + w][:] for starts[b]+w < total_rows, else zeros.
 // One 16-byte chunk per thread; rows are multiples of 16 bytes (1024 B spec rows, 1296 B mask rows).
+// kAffine (seld_window_gather_affine): rows are float32 [channels][64] and a chunk inside the timeline goes through the
+// [channels][64] scale / shift tables on its way; the byte-copying instantiation never looks at the two pointers.
+template <bool kAffine>
 __global__ void gather_rows_kernel(const uint4* __restrict__ src, long total_rows, long row_chunks,
                                    const int64_t* __restrict__ starts, long B, long window,
+                                   const uint4* __restrict__ scale, const uint4* __restrict__ shift,
                                    uint4* __restrict__ dst) {
   const long total = B * window * row_chunks;
   for (long q = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x; q < total;
@@ -120,7 +124,8 @@ __global__ void gather_rows_kernel(const uint4* __restrict__ src, long total_row
     const long b = rw / window;
     const long srow = starts[b] + w;
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (srow >= 0 && srow < total_rows) v = src[srow * row_chunks + chunk];
+    if (srow >= 0 && srow < total_rows)
+      v = standardised<kAffine>(src[srow * row_chunks + chunk], scale, shift, static_cast<int>(chunk));
     dst[q] = v;
   }
 }
@@ -205,9 +210,27 @@ int seld_window_gather(const void* src, int64_t total_rows, int64_t row_bytes, c
   if (rc != kOk || B == 0) return rc;
   const long chunks = row_bytes / 16;
   const unsigned blocks = grid_for(B * window * chunks, 256, st->num_cus);
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_),
+  hipLaunchKernelGGL(gather_rows_kernel<false>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_),
                      static_cast<const uint4*>(src), static_cast<long>(total_rows), chunks, starts,
-                     static_cast<long>(B), static_cast<long>(window), static_cast<uint4*>(dst));
+                     static_cast<long>(B), static_cast<long>(window), static_cast<const uint4*>(nullptr),
+                     static_cast<const uint4*>(nullptr), static_cast<uint4*>(dst));
+  SELD_HIP_TRY(hipGetLastError());
+  return kOk;
+}
+
+int seld_window_gather_affine(const float* src, int64_t total_rows, int channels, const int64_t* starts, int64_t B,
+                              int64_t window, const float* scale, const float* shift, float* dst, void* stream_) {
+  using namespace seld;
+  DeviceState* st;
+  const int rc = check_window_args("seld_window_gather_affine", total_rows, B, window, channels > 0, {}, 0,
+                                   {src, starts, scale, shift, dst}, &st);
+  if (rc != kOk || B == 0) return rc;
+  const long chunks = static_cast<long>(channels) * kChunksPerChannel;
+  const unsigned blocks = grid_for(B * window * chunks, 256, st->num_cus);
+  hipLaunchKernelGGL(gather_rows_kernel<true>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_),
+                     reinterpret_cast<const uint4*>(src), static_cast<long>(total_rows), chunks, starts,
+                     static_cast<long>(B), static_cast<long>(window), reinterpret_cast<const uint4*>(scale),
+                     reinterpret_cast<const uint4*>(shift), reinterpret_cast<uint4*>(dst));
   SELD_HIP_TRY(hipGetLastError());
   return kOk;
 }

@@ -129,11 +129,15 @@ __device__ __forceinline__ unsigned rotated_db(float a, float px, float b, float
   return __float_as_uint(power_to_db(fmaf(a, px, fmaf(b, py, g))));
 }
 
+// kAffine (seld_window_gather_rotate_affine): every output chunk goes through scale / shift [channels][64] of ITS output
+// channel before the masks (augment_core.h, standardised); the other instantiation never looks at the two pointers.
+template <bool kAffine>
 __global__ void __launch_bounds__(256)
 gather_rotate_kernel(const uint4* __restrict__ src, const uint4* __restrict__ rot, long total_rows, int channels,
                      int freq_channels, int J, const int64_t* __restrict__ starts, const int32_t* __restrict__ params, long B,
                      int window, const ChannelTable8 table, const RotationTable angles, const UnitTable units,
-                     unsigned mask_bits, uint4* __restrict__ dst) {
+                     unsigned mask_bits, const uint4* __restrict__ scale, const uint4* __restrict__ shift,
+                     uint4* __restrict__ dst) {
   const int row_chunks = channels * kChunksPerChannel;
   const int row_units = units.slots * kChunksPerChannel;
   const int per_window = window * row_units;                        // host: < 2^31
@@ -187,8 +191,12 @@ gather_rotate_kernel(const uint4* __restrict__ src, const uint4* __restrict__ ro
           vb = make_uint4(__float_as_uint(fmaf(sn, x0, __fmul_rn(cg, y0))), __float_as_uint(fmaf(sn, x1, __fmul_rn(cg, y1))),
                           __float_as_uint(fmaf(sn, x2v, __fmul_rn(cg, y2))), __float_as_uint(fmaf(sn, x3, __fmul_rn(cg, y3))));
         }
+        va = standardised<kAffine>(va, scale, shift, static_cast<int>(ca) * kChunksPerChannel + fc);
         va = masked(va, w, static_cast<int>(ca), fc, prm, freq_channels, mask_bits);
-        if (pair) vb = masked(vb, w, static_cast<int>(cb), fc, prm, freq_channels, mask_bits);
+        if (pair) {
+          vb = standardised<kAffine>(vb, scale, shift, static_cast<int>(cb) * kChunksPerChannel + fc);
+          vb = masked(vb, w, static_cast<int>(cb), fc, prm, freq_channels, mask_bits);
+        }
       }
       uint4* __restrict__ out = to + w * row_chunks + fc;
       out[ca * kChunksPerChannel] = va;
@@ -219,6 +227,53 @@ static bool is_xyz_permutation(int x, int y, int z) {
   return x >= 1 && x <= 3 && y >= 1 && y <= 3 && z >= 1 && z <= 3 && x != y && x != z && y != z;
 }
 
+// the two rotating feature entry points
+template <bool kAffine>
+static int gather_rotate(const char* who, const float* src, const float* rot, int64_t total_rows, int channels,
+                         int freq_channels, int ch_x, int ch_y, int ch_z, int J, const int64_t* starts, const int32_t* params,
+                         int64_t B, int64_t window, const uint8_t* channel_table, float mask_value, const float* scale,
+                         const float* shift, float* dst, void* stream_) {
+  DeviceState* st;
+  const bool extents_ok = freq_channels >= 0 && freq_channels <= channels;
+  const Refusal own[3] = {
+      {channels != 4 && channels != 7, kErrUnsupported,
+       "a rotation is defined for 4 (log-mel) or 7 (log-mel + intensity) FOA feature channels"},
+      {!is_xyz_permutation(ch_x, ch_y, ch_z), kErrInvalidArgument, "ch_x, ch_y, ch_z must be a permutation of 1, 2, 3"},
+      {J < 4 || J > kMaxSteps || J % 4 != 0, kErrUnsupported, "J must be a multiple of 4 in 4..SELD_ROTATE_MAX_STEPS"}};
+  const int64_t frame_chunks = static_cast<int64_t>(channels) * kChunksPerChannel;
+  const int rc = kAffine ? check_window_args(who, total_rows, B, window, extents_ok, {own[0], own[1], own[2]}, frame_chunks,
+                                             {src, rot, starts, params, channel_table, scale, shift, dst}, &st)
+                         : check_window_args(who, total_rows, B, window, extents_ok, {own[0], own[1], own[2]}, frame_chunks,
+                                             {src, rot, starts, params, channel_table, dst}, &st);
+  if (rc != kOk || B == 0) return rc;
+  ChannelTable8 table;
+  if (const int bad = fill_channel_table(who, channel_table, channels, &table)) return bad;
+  // unit slots in output-channel order; the Y channel rides in the X channel's slot
+  UnitTable units{0ull, 0ull, 0};
+  auto add = [&units](int a, int b) {
+    units.first |= static_cast<unsigned long long>(a) << (8 * units.slots);
+    units.second |= static_cast<unsigned long long>(b) << (8 * units.slots);
+    ++units.slots;
+  };
+  for (int base = 0; base < channels - 1; base += 3)                // 0: W + log-mel X Y Z;  3: the intensity vectors
+    for (int c = base == 0 ? 0 : 1; c <= 3; ++c) {
+      if (c == ch_y) continue;
+      if (c == ch_x) add(base + ch_x, base + ch_y);
+      else add(base + c, static_cast<int>(kNoChannel));
+    }
+  RotationTable angles;
+  fill_rotation_table(J, angles);
+  const long per_window = window * units.slots * kChunksPerChannel;
+  hipLaunchKernelGGL(gather_rotate_kernel<kAffine>, window_grid(per_window, B, st->num_cus), dim3(256), 0,
+                     static_cast<hipStream_t>(stream_), reinterpret_cast<const uint4*>(src),
+                     reinterpret_cast<const uint4*>(rot), static_cast<long>(total_rows), channels, freq_channels, J, starts,
+                     params, static_cast<long>(B), static_cast<int>(window), table, angles, units, mask_bits(mask_value),
+                     reinterpret_cast<const uint4*>(scale), reinterpret_cast<const uint4*>(shift),
+                     reinterpret_cast<uint4*>(dst));
+  SELD_HIP_TRY(hipGetLastError());
+  return kOk;
+}
+
 }  // namespace seld
 
 extern "C" {
@@ -245,42 +300,18 @@ int seld_foa_rotation_terms(const float* spec_complex, int64_t N, int64_t F, int
 int seld_window_gather_rotate(const float* src, const float* rot, int64_t total_rows, int channels, int freq_channels,
                               int ch_x, int ch_y, int ch_z, int J, const int64_t* starts, const int32_t* params, int64_t B,
                               int64_t window, const uint8_t* channel_table, float mask_value, float* dst, void* stream_) {
-  using namespace seld;
-  const char* who = "seld_window_gather_rotate";
-  DeviceState* st;
-  const int rc = check_window_args(
-      who, total_rows, B, window, freq_channels >= 0 && freq_channels <= channels,
-      {{channels != 4 && channels != 7, kErrUnsupported,
-        "a rotation is defined for 4 (log-mel) or 7 (log-mel + intensity) FOA feature channels"},
-       {!is_xyz_permutation(ch_x, ch_y, ch_z), kErrInvalidArgument, "ch_x, ch_y, ch_z must be a permutation of 1, 2, 3"},
-       {J < 4 || J > kMaxSteps || J % 4 != 0, kErrUnsupported, "J must be a multiple of 4 in 4..SELD_ROTATE_MAX_STEPS"}},
-      static_cast<int64_t>(channels) * kChunksPerChannel, {src, rot, starts, params, channel_table, dst}, &st);
-  if (rc != kOk || B == 0) return rc;
-  ChannelTable8 table;
-  if (const int bad = fill_channel_table(who, channel_table, channels, &table)) return bad;
-  // unit slots in output-channel order; the Y channel rides in the X channel's slot
-  UnitTable units{0ull, 0ull, 0};
-  auto add = [&units](int a, int b) {
-    units.first |= static_cast<unsigned long long>(a) << (8 * units.slots);
-    units.second |= static_cast<unsigned long long>(b) << (8 * units.slots);
-    ++units.slots;
-  };
-  for (int base = 0; base < channels - 1; base += 3)                // 0: W + log-mel X Y Z;  3: the intensity vectors
-    for (int c = base == 0 ? 0 : 1; c <= 3; ++c) {
-      if (c == ch_y) continue;
-      if (c == ch_x) add(base + ch_x, base + ch_y);
-      else add(base + c, static_cast<int>(kNoChannel));
-    }
-  RotationTable angles;
-  fill_rotation_table(J, angles);
-  const long per_window = window * units.slots * kChunksPerChannel;
-  hipLaunchKernelGGL(gather_rotate_kernel, window_grid(per_window, B, st->num_cus), dim3(256), 0,
-                     static_cast<hipStream_t>(stream_), reinterpret_cast<const uint4*>(src),
-                     reinterpret_cast<const uint4*>(rot), static_cast<long>(total_rows), channels, freq_channels, J, starts,
-                     params, static_cast<long>(B), static_cast<int>(window), table, angles, units, mask_bits(mask_value),
-                     reinterpret_cast<uint4*>(dst));
-  SELD_HIP_TRY(hipGetLastError());
-  return kOk;
+  return seld::gather_rotate<false>("seld_window_gather_rotate", src, rot, total_rows, channels, freq_channels, ch_x, ch_y,
+                                    ch_z, J, starts, params, B, window, channel_table, mask_value, nullptr, nullptr, dst,
+                                    stream_);
+}
+
+int seld_window_gather_rotate_affine(const float* src, const float* rot, int64_t total_rows, int channels, int freq_channels,
+                                     int ch_x, int ch_y, int ch_z, int J, const int64_t* starts, const int32_t* params,
+                                     int64_t B, int64_t window, const uint8_t* channel_table, float mask_value,
+                                     const float* scale, const float* shift, float* dst, void* stream_) {
+  return seld::gather_rotate<true>("seld_window_gather_rotate_affine", src, rot, total_rows, channels, freq_channels, ch_x,
+                                   ch_y, ch_z, J, starts, params, B, window, channel_table, mask_value, scale, shift, dst,
+                                   stream_);
 }
 
 }  // extern "C"

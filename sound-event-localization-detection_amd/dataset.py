@@ -30,6 +30,7 @@ from torch.utils.data import Dataset
 
 import seld_augment
 import seld_native
+import seld_standardise
 from config import Config
 from utils import polar_to_grid  # noqa: F401  (re-exported like the reference module)
 
@@ -425,6 +426,41 @@ class SELDDataset(Dataset):
         self.use_gaussian_augmentation = bool(config.GAUSSIAN_AUGMENT)
         self.with_rotation = bool(getattr(config, "AUGMENT_ROTATE", False))   # as of construction: decides whether rot_tm exists
         self.rot_tm = None
+        self._feature_statistics = None          # statistics of THIS timeline (feature_statistics), computed once
+        self.feature_stats = None                # the statistics device_batch applies (set_feature_statistics), or None
+        self._feature_scale = self._feature_shift = None
+
+    # -- per-bin standardisation (Config.STANDARDISE_FEATURES; seld_standardise.py) ---------
+    def feature_statistics(self):
+        """Mean and standard deviation of every (channel, bin) column of this dataset's timeline (seld_standardise
+        statistics: CPU tensors), from the device moments kernel (csrc/standardise.hip); computed once and cached.  It sets
+        nothing: ``set_feature_statistics`` does."""
+        if self._feature_statistics is None:
+            if self.spec_tm is None:
+                raise RuntimeError("feature_statistics needs the device timeline (keep_on_device=True): the moments are "
+                                   "reduced on the GPU, there is no CPU fallback")
+            moments = seld_native.feature_moments(self.spec_tm)
+            self._feature_statistics = seld_standardise.finalise(moments.cpu(), self.total_frames)
+        return self._feature_statistics
+
+    def set_feature_statistics(self, stats):
+        """Make ``device_batch`` standardise: every gathered feature becomes fmaf(x, scale[c, f], shift[c, f]) with the
+        tables of ``stats`` (seld_standardise statistics, or a checkpoint's ``feature_statistics`` payload), uploaded here
+        once.  None switches it off.  ``__getitem__``, the host mirrors and the feature cache stay raw."""
+        if stats is None:
+            self.feature_stats = self._feature_scale = self._feature_shift = None
+            return
+        if self.spec_tm is None:
+            raise RuntimeError("set_feature_statistics needs the device timeline (keep_on_device=True): the statistics are "
+                               "applied by the device window gathers, there is no CPU fallback")
+        if "scale" not in stats or "shift" not in stats:
+            stats = seld_standardise.from_payload(stats)
+        channels = int(stats["mean"].shape[0])
+        if channels != self.n_channels:
+            raise ValueError(f"feature statistics are for {channels} feature channels, this dataset has {self.n_channels}")
+        self.feature_stats = stats
+        self._feature_scale = stats["scale"].to(self.spec_tm.device).contiguous()
+        self._feature_shift = stats["shift"].to(self.spec_tm.device).contiguous()
 
     # -- reference-shaped views ---------------------------------------------------------------
     @property
@@ -464,7 +500,8 @@ class SELDDataset(Dataset):
         ``augment``: None, or the windows' parameter table (int32 [B, 12], ``seld_augment.draw``): the batch is then
         produced by the augmenting gathers (csrc/augment.hip) -- channel swap + label cell permutation + masks; on a dataset
         constructed with Config.AUGMENT_ROTATE (``rot_tm`` exists) by the rotating pair (csrc/rotate.hip), which also honours
-        the azimuth step in slot [9] of a row."""
+        the azimuth step in slot [9] of a row.  After ``set_feature_statistics`` all three feature gathers go through their
+        standardising exports: affine map after the transform, before the masks."""
         if self.spec_tm is None:
             raise RuntimeError("device_batch needs keep_on_device=True")
         starts = torch.as_tensor(self.window_starts[np.asarray(indices, dtype=np.int64)])
@@ -473,6 +510,8 @@ class SELDDataset(Dataset):
         if out is not None:
             bufs = out((len(starts), w) + tuple(self.spec_tm.shape[1:]), self.spec_tm.dtype,
                        (len(starts), w) + tuple(self.mask_tm.shape[1:]), self.mask_tm.dtype)
+        # set_feature_statistics: the same three gathers through their standardising exports (None: the exports they were)
+        scale, shift = getattr(self, "_feature_scale", None), getattr(self, "_feature_shift", None)
         if augment is not None:
             table, freq_channels, mask_value = self._augment_tables()
             starts = starts.to(self.device, non_blocking=True)
@@ -480,17 +519,20 @@ class SELDDataset(Dataset):
                 params = seld_native.augment_params(augment, len(starts), w, self.device, steps=self.J)
                 spec = seld_native.gather_windows_rotate(self.spec_tm, self.rot_tm, starts, w, params, table,
                                                          getattr(config, "FOA_CHANNEL_ORDER", "WYZX"), self.J, freq_channels,
-                                                         mask_value, out=bufs[0] if bufs else None)
+                                                         mask_value, out=bufs[0] if bufs else None, scale=scale, shift=shift)
                 mask = seld_native.gather_windows_permute_rotate(self.mask_tm, starts, w, params, self.I, self.J,
                                                                  out=bufs[1] if bufs else None)
                 return spec, mask
             params = seld_native.augment_params(augment, len(starts), w, self.device)     # one more small async copy
             spec = seld_native.gather_windows_augment(self.spec_tm, starts, w, params, table, freq_channels, mask_value,
-                                                      out=bufs[0] if bufs else None)
+                                                      out=bufs[0] if bufs else None, scale=scale, shift=shift)
             mask = seld_native.gather_windows_permute(self.mask_tm, starts, w, params, self.I, self.J,
                                                       out=bufs[1] if bufs else None)
             return spec, mask
-        spec = seld_native.gather_windows(self.spec_tm, starts, w, out=bufs[0] if bufs else None)
+        if scale is not None:
+            spec = seld_native.gather_windows_affine(self.spec_tm, starts, w, scale, shift, out=bufs[0] if bufs else None)
+        else:
+            spec = seld_native.gather_windows(self.spec_tm, starts, w, out=bufs[0] if bufs else None)
         mask = seld_native.gather_windows(self.mask_tm, starts, w, out=bufs[1] if bufs else None)
         return spec, mask
 

@@ -102,6 +102,9 @@ def main(argv=None):
         finally:
             dataset.config.RESAMPLE_INPUT = saved
         seld_augment.check_tta(patterns, getattr(trainer.config, "FEATURE_SET", "logmel"), ds.n_channels)
+        # a checkpoint trained on standardised features carries their statistics: the recording's gathers apply them
+        # (Config.STANDARDISE_FEATURES on and none in the checkpoint: an error, as in evaluate_seld)
+        trainer.apply_checkpoint_statistics(checkpoint, ds)
         if model is None:
             model = trainer.prepare_model_for_device(trainer.build_model((ds.I, ds.J), True, n_channels=ds.n_channels),
                                                      device)

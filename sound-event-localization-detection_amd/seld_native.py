@@ -80,6 +80,14 @@ def _declare(lib):
     lib.seld_window_gather_rotate.argtypes = [_ptr, _ptr, _i64, _int, _int, _int, _int, _int, _int, _ptr, _ptr, _i64, _i64, _ptr,
                                               ctypes.c_float, _ptr, _ptr]
     lib.seld_window_permute_mask_rotate.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _i64, _i64, _ptr, _ptr]
+    lib.seld_feature_moments_workspace.restype = _i64
+    lib.seld_feature_moments_workspace.argtypes = [_i64, _int]
+    lib.seld_feature_moments.argtypes = [_ptr, _i64, _int, _ptr, _ptr, _i64, _ptr]
+    lib.seld_window_gather_affine.argtypes = [_ptr, _i64, _int, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr]
+    lib.seld_window_gather_augment_affine.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _i64, _i64, _ptr, ctypes.c_float,
+                                                      _ptr, _ptr, _ptr, _ptr]
+    lib.seld_window_gather_rotate_affine.argtypes = [_ptr, _ptr, _i64, _int, _int, _int, _int, _int, _int, _ptr, _ptr, _i64,
+                                                     _i64, _ptr, ctypes.c_float, _ptr, _ptr, _ptr, _ptr]
     lib.seld_softmax_mse_workspace_bytes.restype = _i64
     lib.seld_softmax_mse_workspace_bytes.argtypes = []
     lib.seld_softmax_mse.argtypes = [_ptr, _int, _ptr, _ptr, _i64, _int, ctypes.c_float, _ptr, _ptr, _ptr, _ptr]
@@ -524,6 +532,63 @@ def gather_windows(src: torch.Tensor, starts: torch.Tensor, window: int, out: to
     return out
 
 
+def _affine_tables(name: str, scale, shift, src: torch.Tensor):
+    """The [C, 64] float32 scale / shift tables of the standardising gathers on ``src``'s device, or
+    (None, None) when neither is given; one without the other is refused."""
+    if scale is None and shift is None:
+        return None, None
+    if scale is None or shift is None:
+        raise ValueError(f"{name}: scale and shift come together")
+    shape = (int(src.shape[1]), N_MELS)
+    for what, t in (("scale", scale), ("shift", shift)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == src.device and t.dtype == torch.float32
+                and tuple(t.shape) == shape):
+            raise SeldNativeError(f"{name}: {what} must be a float32 tensor {list(shape)} on {src.device}")
+    return scale.contiguous(), shift.contiguous()
+
+
+def gather_windows_affine(src: torch.Tensor, starts: torch.Tensor, window: int, scale: torch.Tensor, shift: torch.Tensor,
+                          out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gather_windows`` of the feature timeline src [T, C, 64] (float32) with every element inside the timeline mapped to
+    ``fmaf(x, scale[c, f], shift[c, f])`` on the way (csrc/labels.hip, the standardising instantiation of the plain gather);
+    rows past the timeline stay zero.  ``scale`` / ``shift``: float32 [C, 64] on the device."""
+    src, index, starts, out = _window_call("gather_windows_affine", src, torch.float32, (None, N_MELS),
+                                           "a float32 GPU tensor [T, C, 64]", starts, window, None, out)
+    if src.shape[1] == 0:
+        raise ValueError("gather_windows_affine: empty source")
+    if scale is None or shift is None:
+        raise ValueError("gather_windows_affine: scale and shift are required")
+    scale, shift = _affine_tables("gather_windows_affine", scale, shift, src)
+    with _device_guard(index):
+        check(load_library().seld_window_gather_affine(_p(src), src.shape[0], int(src.shape[1]), _p(starts), starts.numel(),
+                                                       window, _p(scale), _p(shift), _p(out), _stream_ptr(src.device)),
+              "seld_window_gather_affine")
+    return out
+
+
+def feature_moments(spec_tm: torch.Tensor) -> torch.Tensor:
+    """Moments of a time-major feature timeline spec_tm [T, C, 64] (float32, on the GPU): float64 [2, C, 64] on the device,
+    (sum x, sum x^2) over the frames per (channel, bin) in the fixed order of include/seld_hip.h -- the same bits on every
+    device and grid (csrc/standardise.hip).  The timeline is read once; the slab partials live in a workspace from the
+    caching allocator, freed on return (stream-ordered: the allocator reuses it only behind this stream's work)."""
+    if not (isinstance(spec_tm, torch.Tensor) and spec_tm.is_cuda and spec_tm.dtype == torch.float32 and spec_tm.dim() == 3
+            and spec_tm.shape[2] == N_MELS):
+        raise SeldNativeError("feature_moments: spec_tm must be a float32 GPU tensor [T, C, 64]")
+    if spec_tm.shape[0] == 0 or spec_tm.shape[1] == 0:
+        raise ValueError("feature_moments: empty timeline")
+    spec_tm = spec_tm.contiguous()
+    index = ensure_init(spec_tm.device)
+    lib = load_library()
+    frames, channels = int(spec_tm.shape[0]), int(spec_tm.shape[1])
+    nbytes = int(lib.seld_feature_moments_workspace(frames, channels))
+    with _device_guard(index):
+        workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=spec_tm.device)
+        moments = torch.empty((2, channels, N_MELS), dtype=torch.float64, device=spec_tm.device)
+        check(lib.seld_feature_moments(_p(spec_tm), frames, channels, _p(moments), _p(workspace), nbytes,
+                                       _stream_ptr(spec_tm.device)), "seld_feature_moments")
+    return moments
+
+
 def augment_params(params, batch: int, window: int, device, steps: int | None = None) -> torch.Tensor:
     """The per-window parameter table of the augmenting gathers as an int32 [batch, 12] device tensor.  A host table
     (numpy array / CPU tensor) is validated here -- pattern in 0..15, every mask inside its axis, and with ``steps`` (the J
@@ -551,16 +616,27 @@ def augment_params(params, batch: int, window: int, device, steps: int | None = 
 
 def gather_windows_augment(src: torch.Tensor, starts: torch.Tensor, window: int, params: torch.Tensor, channel_table=None,
                            freq_channels: int | None = None, mask_value: float = 0.0,
-                           out: torch.Tensor | None = None) -> torch.Tensor:
+                           out: torch.Tensor | None = None, scale: torch.Tensor | None = None,
+                           shift: torch.Tensor | None = None) -> torch.Tensor:
     """``gather_windows`` of the feature timeline src [T, C, 64] (float32) with one augmentation per window
     (csrc/augment.hip): a signed channel permutation chosen by the window's spatial pattern, then time / frequency masks.
     ``params``: int32 [B, 12] on the device (``augment_params``); ``channel_table``: uint8 [16, C] host array, entry =
-    source channel | 0x80 when negated (None: channels stay put); frequency masks touch channels < ``freq_channels``."""
+    source channel | 0x80 when negated (None: channels stay put); frequency masks touch channels < ``freq_channels``.
+    ``scale`` / ``shift`` (float32 [C, 64] on the device, both or neither): the standardising export -- the copied value of
+    OUTPUT channel c becomes ``fmaf(v, scale[c, f], shift[c, f])`` before the masks."""
     src, index, starts, out = _window_call("gather_windows_augment", src, torch.float32, (None, N_MELS),
                                            "a float32 GPU tensor [T, C, 64]", starts, window, params, out)
     channels = int(src.shape[1])
     freq_channels = channels if freq_channels is None else int(freq_channels)
     table = None if channel_table is None else _channel_table("gather_windows_augment", channel_table, channels)
+    scale, shift = _affine_tables("gather_windows_augment", scale, shift, src)
+    if scale is not None:
+        with _device_guard(index):
+            check(load_library().seld_window_gather_augment_affine(
+                _p(src), src.shape[0], channels, freq_channels, _p(starts), _p(params), starts.numel(), window,
+                ctypes.c_void_p(table.ctypes.data) if table is not None else None, float(mask_value), _p(scale), _p(shift),
+                _p(out), _stream_ptr(src.device)), "seld_window_gather_augment_affine")
+        return out
     with _device_guard(index):
         check(load_library().seld_window_gather_augment(
             _p(src), src.shape[0], channels, freq_channels, _p(starts), _p(params), starts.numel(), window,
@@ -612,11 +688,13 @@ def foa_rotation_terms(spec: torch.Tensor, order: str = "WYZX") -> torch.Tensor:
 
 def gather_windows_rotate(src: torch.Tensor, rot: torch.Tensor, starts: torch.Tensor, window: int, params: torch.Tensor,
                           channel_table, order: str = "WYZX", J: int = GRID_J, freq_channels: int | None = None,
-                          mask_value: float = 0.0, out: torch.Tensor | None = None) -> torch.Tensor:
+                          mask_value: float = 0.0, out: torch.Tensor | None = None, scale: torch.Tensor | None = None,
+                          shift: torch.Tensor | None = None) -> torch.Tensor:
     """``gather_windows_augment`` with the azimuth step of ``params[:, 9]`` (csrc/rotate.hip): src [T, C, 64] with C = 4
     ('logmel') or 7 ('logmel_iv'), rot [T, 3, 64] the timeline's rotation terms (``foa_rotation_terms``).  A window whose
     total rotation is a whole number of quarter turns is the signed channel copy of ``gather_windows_augment``, bit for bit;
-    any other window gets X' / Y' log-mel and IV_x' / IV_y' computed from the terms."""
+    any other window gets X' / Y' log-mel and IV_x' / IV_y' computed from the terms.  ``scale`` / ``shift``: as in
+    ``gather_windows_augment`` (the standardising export; applied to the rotated values, before the masks)."""
     src, index, starts, out = _window_call("gather_windows_rotate", src, torch.float32, (None, N_MELS),
                                            "a float32 GPU tensor [T, C, 64]", starts, window, params, out)
     channels = int(src.shape[1])
@@ -626,6 +704,14 @@ def gather_windows_rotate(src: torch.Tensor, rot: torch.Tensor, starts: torch.Te
     ch_x, ch_y, ch_z = foa_channels(order)
     freq_channels = channels if freq_channels is None else int(freq_channels)
     table = _channel_table("gather_windows_rotate", channel_table, channels)
+    scale, shift = _affine_tables("gather_windows_rotate", scale, shift, src)
+    if scale is not None:
+        with _device_guard(index):
+            check(load_library().seld_window_gather_rotate_affine(
+                _p(src), _p(rot), src.shape[0], channels, freq_channels, ch_x, ch_y, ch_z, int(J), _p(starts), _p(params),
+                starts.numel(), window, ctypes.c_void_p(table.ctypes.data), float(mask_value), _p(scale), _p(shift), _p(out),
+                _stream_ptr(src.device)), "seld_window_gather_rotate_affine")
+        return out
     with _device_guard(index):
         check(load_library().seld_window_gather_rotate(
             _p(src), _p(rot), src.shape[0], channels, freq_channels, ch_x, ch_y, ch_z, int(J), _p(starts), _p(params),

@@ -37,6 +37,7 @@ from torch.utils.data import DataLoader, RandomSampler, SequentialSampler  # noq
 from tqdm import tqdm
 
 import seld_augment
+import seld_standardise
 from config import Config
 from dataset import SELDDataset
 from loss import SMRSELDLoss
@@ -253,6 +254,11 @@ class LoaderFeed:
             raise RuntimeError(f"{', '.join(on)}: training augmentation is applied by the device window gather and needs the "
                                f"device feed (DEVICE_FEED = True, a ROCm GPU, a SELDDataset kept on the device); the host "
                                f"DataLoader path has no CPU implementation of it.  Switch the augmentation off to use it")
+        if getattr(config, "STANDARDISE_FEATURES", False):
+            # likewise: the statistics are reduced and applied by device kernels (csrc/standardise.hip, the affine gathers)
+            raise RuntimeError("STANDARDISE_FEATURES: the per-bin standardisation is applied by the device window gather and "
+                               "needs the device feed (DEVICE_FEED = True, a ROCm GPU, a SELDDataset kept on the device); the "
+                               "host DataLoader path has no CPU implementation of it.  Switch it off to use this path")
         self.loader, self.device = loader, device
         self.rank, self.world, self.seed = rank, world, seed
         sampler = getattr(loader, "sampler", None)
@@ -737,8 +743,46 @@ def make_stepper(model, criterion, optimizer, device, world=1):
     return lambda spectrograms, labels: train_step(model, criterion, optimizer, spectrograms, labels, device)
 
 
-def checkpoint_payload(epoch, model, optimizer, train_loss, test_loss):
-    """The dict format of trainer.py:278-285 (the Config INSTANCE is pickled, as upstream).  A capturable Adam keeps its
+def standardise_datasets(train_dataset, test_dataset):
+    """Config.STANDARDISE_FEATURES: the statistics of the TRAINING dataset's timeline, set on both
+    datasets (the test windows are standardised with the training statistics, never their own).  Returns the payload the
+    checkpoints carry under ``feature_statistics``; None -- and nothing is computed, launched or set -- with the switch off."""
+    if not getattr(config, "STANDARDISE_FEATURES", False):
+        for ds in (train_dataset, test_dataset):           # statistics an earlier run with the switch on left behind
+            if getattr(ds, "feature_stats", None) is not None:
+                ds.set_feature_statistics(None)
+        return None
+    for ds in (train_dataset, test_dataset):
+        if not isinstance(ds, SELDDataset) or getattr(ds, "spec_tm", None) is None:
+            raise RuntimeError("STANDARDISE_FEATURES needs SELDDatasets that keep their device timeline (DEVICE_FEED = True, "
+                               "keep_on_device=True): there is no CPU fallback")
+    stats = train_dataset.feature_statistics()
+    train_dataset.set_feature_statistics(stats)
+    test_dataset.set_feature_statistics(stats)
+    flat = int((stats["std"] < seld_standardise.FLAT_STD).sum())
+    logger.info(f"Feature standardisation: {stats['frames']} training frames, {train_dataset.n_channels} x 64 bins"
+                + (f", {flat} flat bin(s) only centred" if flat else ""))
+    return seld_standardise.to_payload(stats, getattr(config, "FEATURE_SET", "logmel"), train_dataset.n_channels)
+
+
+def apply_checkpoint_statistics(checkpoint, dataset):
+    """Evaluation: the checkpoint decides.  Its ``feature_statistics`` are set on ``dataset`` when it holds them; without
+    them the dataset gathers raw features -- unless Config.STANDARDISE_FEATURES is on, which is an error (the shape of the
+    EVAL_USE_EMA one: never a silent evaluation on other inputs than the weights were trained on).  Returns the statistics."""
+    stats = seld_standardise.checkpoint_statistics(checkpoint, config, channels=getattr(dataset, "n_channels", None))
+    if hasattr(dataset, "set_feature_statistics"):
+        if stats is not None or getattr(dataset, "feature_stats", None) is not None:
+            dataset.set_feature_statistics(stats)
+    elif stats is not None:
+        raise RuntimeError("the checkpoint holds feature_statistics: evaluation needs an SELDDataset, whose device gathers "
+                           "apply them")
+    return stats
+
+
+def checkpoint_payload(epoch, model, optimizer, train_loss, test_loss, feature_statistics=None):
+    """The dict format of trainer.py:278-285 (the Config INSTANCE is pickled, as upstream).  ``feature_statistics``: the
+    payload of ``standardise_datasets`` (Config.STANDARDISE_FEATURES), stored under that key; None adds no key.
+    A capturable Adam keeps its
     learning rate (and step counts) in device tensors; the file holds what the reference's plain Adam would have written --
     a float learning rate, host-side step counts, no ``capturable`` flag -- so that upstream code can format, compare or
     resume from it on any box."""
@@ -761,6 +805,8 @@ def checkpoint_payload(epoch, model, optimizer, train_loss, test_loss):
         ema = ema_state_dict(model, optimizer)
         if ema is not None:
             payload["ema_state_dict"] = ema
+    if feature_statistics is not None:
+        payload["feature_statistics"] = feature_statistics
     return payload
 
 
@@ -818,6 +864,9 @@ def train_model(train_loader, test_loader, num_epochs=None, batch_size=None, lea
     train_feed = make_feed(train_loader, device, rank, world)
     test_feed = make_feed(test_loader, device, rank, world)
     logger.info(f"Batch source: {type(train_feed).__name__}; autocast: {getattr(config, 'AMP_DTYPE', 'fp32')}")
+    # Config.STANDARDISE_FEATURES: the training timeline's statistics on both datasets (every rank reduces its own copy of
+    # the timeline in the same fixed order: the same bits without a collective); None with the switch off
+    feature_statistics = standardise_datasets(train_dataset, test_dataset)
 
     train_losses, test_losses = [], []
     best_train_loss = best_test_loss = float("inf")
@@ -903,13 +952,13 @@ def train_model(train_loader, test_loader, num_epochs=None, batch_size=None, lea
             gained = best_test_loss - avg_test_loss
             best_test_loss = avg_test_loss
             if is_main:
-                torch.save(checkpoint_payload(epoch, model, optimizer, avg_train_loss, avg_test_loss),
+                torch.save(checkpoint_payload(epoch, model, optimizer, avg_train_loss, avg_test_loss, feature_statistics),
                            config.CHECKPOINT_PATH / "best_model.pth")
             logger.info(f"  New best model saved! (test loss improvement: {gained:.6f})")
 
         if epoch % config.SAVE_EVERY_N_EPOCHS == 0 and is_main:
             path = config.CHECKPOINT_PATH / f"checkpoint_epoch_{epoch}.pth"
-            torch.save(checkpoint_payload(epoch, model, optimizer, avg_train_loss, avg_test_loss), path)
+            torch.save(checkpoint_payload(epoch, model, optimizer, avg_train_loss, avg_test_loss, feature_statistics), path)
             kept_checkpoints.append(path)
             logger.info(f"  Checkpoint saved: {path.name}")
             if len(kept_checkpoints) > config.KEEP_LAST_N_CHECKPOINTS:
@@ -989,6 +1038,7 @@ def test_model(test_loader, model_path=None, batch_size=None, device=None, num_v
     model = prepare_model_for_device(build_model(grid, True, n_channels=getattr(test_dataset, "n_channels", None)),
                                      device)
     model.load_state_dict(select_state_dict(checkpoint, use_ema))
+    apply_checkpoint_statistics(checkpoint, test_dataset)      # the checkpoint decides (Config.STANDARDISE_FEATURES)
     model.eval()
     logger.info(f"Model loaded (epoch {checkpoint['epoch']}, test loss {checkpoint['test_loss']:.6f})")
     criterion = SMRSELDLoss(loss_type=config.LOSS_TYPE, w_class=config.W_CLASS, w_aiur=config.W_AIUR,
@@ -1048,8 +1098,11 @@ def test_model(test_loader, model_path=None, batch_size=None, device=None, num_v
         (config.OUTPUT_PATH / "test_visualizations").mkdir(exist_ok=True)
     for viz, (window_idx, time_idx, num_active) in enumerate(chosen, start=1):
         spec, labels = test_dataset[window_idx]
+        spec = spec.unsqueeze(0).to(device)
+        if getattr(test_dataset, "feature_stats", None) is not None:     # __getitem__ stays raw: the model's input is the
+            spec = test_dataset.device_batch([window_idx])[0]            # standardised window of the device gather
         with torch.no_grad(), autocast_context(device):
-            logits = model(spec.unsqueeze(0).to(device))[0, time_idx].float().cpu()
+            logits = model(spec)[0, time_idx].float().cpu()
         save_path = None
         if save_visualizations:
             save_path = config.OUTPUT_PATH / "test_visualizations" / f"test_viz_{viz}_window{window_idx}_frame{time_idx}.png"
@@ -1154,6 +1207,7 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
     model = prepare_model_for_device(build_model((test_dataset.I, test_dataset.J), True,
                                                  n_channels=getattr(test_dataset, "n_channels", None)), device)
     model.load_state_dict(select_state_dict(checkpoint, use_ema))
+    apply_checkpoint_statistics(checkpoint, test_dataset)      # the checkpoint decides (Config.STANDARDISE_FEATURES)
     model.eval()
     logger.info(f"SELD evaluation: {len(test_dataset)} windows, checkpoint epoch {checkpoint['epoch']}")
     if patterns:
