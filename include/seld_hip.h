@@ -460,6 +460,17 @@ int seld_conv3x3_dgrad_supported(int64_t F, int64_t Cin, int64_t Cout);
 int seld_conv3x3_dgrad(const void* dy, const void* w, int64_t B, int64_t T, int64_t F, int64_t Cin, int64_t Cout,
                        void* dx, void* stream);
 
+/* Forward of the same convolution on the data-gradient kernel's loop (csrc/convfwd.hip): x [B][T][F][Cin] and
+ * w [Cout][3][3][Cin] -> y [B][T][F][Cout], all bf16, fp32 accumulation, one rounding; the weights are read as they
+ * lie.  F in {8, 16, 32}, Cin % 64 == 0, Cout % 64 == 0 (see _supported); all pointers 16-byte aligned.
+ * partials (may be NULL): [2][chunks][Cout] fp32 with chunks = seld_conv3x3_forward_chunks(B, T, F); row c receives the
+ * sum and the sum of squares per output channel of the bf16 values stored for chunk c (256 positions of one clip, fewer
+ * in a clip's last chunk), summed in a fixed order: the input of seld_conv_tail_forward_from_partials. */
+int seld_conv3x3_forward_supported(int64_t F, int64_t Cin, int64_t Cout);
+int64_t seld_conv3x3_forward_chunks(int64_t B, int64_t T, int64_t F);
+int seld_conv3x3_forward(const void* x, const void* w, int64_t B, int64_t T, int64_t F, int64_t Cin, int64_t Cout,
+                         void* y, float* partials, void* stream);
+
 /* ---- First encoder block with the convolution recomputed in place (csrc/convfirst.hip) --------------------- */
 /* Conv3x3(4 -> 64, stride 1, pad 1, no bias) -> BatchNorm2d (training mode, affine, running statistics) -> ReLU ->
  * MaxPool2d((1,2)) of model_crnn.py:5-17 without ever writing the convolution output or its gradient.
@@ -506,6 +517,14 @@ int seld_conv_tail_forward(const void* x, const void* residual, int is_bf16, int
                            const float* weight, const float* bias, float* running_mean, float* running_var,
                            float momentum, float eps, int training, void* y, float* mean_invstd, float* scale_shift,
                            float* workspace, void* stream);
+/* The training-mode forward without its statistics pass: partials [2][nrows][C] holds plain (unshifted) sums of x and
+ * x^2 over disjoint parts of the rows (seld_conv3x3_forward), 1 <= nrows <= seld_conv_tail_partial_rows(); they are
+ * combined in double in a fixed order.  No residual. */
+int64_t seld_conv_tail_partial_rows(void);
+int seld_conv_tail_forward_from_partials(const void* x, int is_bf16, int64_t rows, int C, int pool,
+                                         const float* partials, int64_t nrows, const float* weight, const float* bias,
+                                         float* running_mean, float* running_var, float momentum, float eps, void* y,
+                                         float* mean_invstd, float* scale_shift, void* stream);
 int seld_conv_tail_backward(const void* x, const void* residual, const void* dy, int is_bf16, int64_t rows, int C,
                             int pool, const float* mean_invstd, const float* scale_shift, void* dx, void* dresidual,
                             float* dweight, float* dbias, float* workspace, void* stream);

@@ -101,6 +101,10 @@ class Config:
     FUSED_CONV_DGRAD = True     # encoder 3x3 convs: data gradient by the HIP MFMA kernel (csrc/convdgrad.hip) from the weights
                                 # where they lie (no flip / transpose launch, no library call); shapes it does not cover:
                                 # the library.  Part of the _Conv3x3 path: no effect when CONV_DGRAD_AS_FORWARD is off
+    FUSED_CONV_FWD = True       # encoder 3x3 convs in training: forward by the HIP MFMA kernel on the data-gradient loop
+                                # (csrc/convfwd.hip), which also forms the BatchNorm sums, so the tail runs without its
+                                # statistics pass; blocks on model_crnn.ConvBlock.fused_fwd_adopted only.  Part of the _Conv3x3
+                                # path and needs FUSED_CONV_TAIL; eval, fp32 and other shapes: the library
     FUSED_FIRST_BLOCK = True    # encoder block 1 (4 -> 64 channels, bf16 training): the 36-MAC convolution is recomputed inside
                                 # the BatchNorm / ReLU / pool kernels and inside its own weight gradient instead of stored
                                 # (csrc/convfirst.hip): its 65.5 MB output and gradient never reach HBM.  Needs FUSED_CONV_TAIL

@@ -1,5 +1,5 @@
 // Shared pieces of the encoder's 3x3 / stride 1 / pad 1 convolution kernels on channels-last bf16 activations
-// (convwgrad.hip, convdgrad.hip): a chunk of P positions = TC consecutive time rows of one clip is staged in LDS as an
+// (convwgrad.hip, convdgrad.hip, convfwd.hip): a chunk of P positions = TC consecutive time rows of one clip is staged in LDS as an
 // image [TC + 2][F + 2][64 channels] with zero rows outside [0, T) and a zero column on each frequency edge, so the
 // nine taps are nine constant row offsets into it and nothing crosses a clip boundary.  Rows have a 160-byte pitch:
 // eight consecutive rows then cover all 64 banks, which keeps the 32-lane halves of ds_read_b64_tr_b16 conflict-free

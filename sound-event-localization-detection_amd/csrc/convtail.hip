@@ -152,7 +152,9 @@ __global__ __launch_bounds__(kTailThreads) void tail_stats_kernel(const void* __
 // One block per 16 channels: reduce the partial rows in double, produce mean / invstd / affine coefficients and
 // update the running statistics exactly like nn.BatchNorm2d in training mode (biased variance for the
 // normalisation, unbiased for running_var, momentum blend).  training == 0: coefficients from the running stats.
-template <typename T>
+// kShifted = false: the partial rows hold plain sums of x and x^2 (the forward convolution's statistics epilogue,
+// convfwd.hip: one row per chunk of 256 positions), x is not read.
+template <typename T, bool kShifted = true>
 __global__ __launch_bounds__(kFinalThreads) void tail_stats_final_kernel(const void* __restrict__ x, long rows, int C,
                                                                         const float* __restrict__ partials, int nblocks,
                                                                         const float* __restrict__ weight,
@@ -184,9 +186,12 @@ __global__ __launch_bounds__(kFinalThreads) void tail_stats_final_kernel(const v
     double mean, var;
     if (training) {
       const double n = static_cast<double>(rows);
-      float first[8];
-      Row8<T>::load(x, ch & ~7, first);
-      const double shift = static_cast<double>(first[ch & 7]);
+      double shift = 0.0;
+      if constexpr (kShifted) {
+        float first[8];
+        Row8<T>::load(x, ch & ~7, first);
+        shift = static_cast<double>(first[ch & 7]);
+      }
       const double m1 = red[tid] / n, m2 = red[tid + 16] / n;
       mean = shift + m1;
       var = m2 - m1 * m1;
@@ -484,6 +489,29 @@ static unsigned tail_grid(const DeviceState* st, long work_rows, int C) {
   return static_cast<unsigned>(blocks < 1 ? 1 : blocks);
 }
 
+// the apply pass of the forward tail (mode 3 with a residual)
+static void launch_tail_apply(const DeviceState* st, const void* x, const void* residual, int is_bf16, int64_t rows,
+                              int C, int pool, const float* scale_shift, void* y, hipStream_t stream) {
+  const long out_rows = pool == 2 ? rows / 2 : rows;
+  const dim3 grid(tail_grid(st, out_rows, C));
+  const int mode = residual ? 3 : pool;
+#define SELD_TAIL_APPLY(T, P)                                                                                     \
+  hipLaunchKernelGGL((tail_apply_kernel<T, P>), grid, dim3(kTailThreads), 0, stream, x, residual, out_rows, C, \
+                     scale_shift, y)
+  if (is_bf16) {
+    if (mode == 2) SELD_TAIL_APPLY(__hip_bfloat16, 2);
+    else if (mode == 3) SELD_TAIL_APPLY(__hip_bfloat16, 3);
+    else if (mode == 4) SELD_TAIL_APPLY(__hip_bfloat16, 4);
+    else SELD_TAIL_APPLY(__hip_bfloat16, 1);
+  } else {
+    if (mode == 2) SELD_TAIL_APPLY(float, 2);
+    else if (mode == 3) SELD_TAIL_APPLY(float, 3);
+    else if (mode == 4) SELD_TAIL_APPLY(float, 4);
+    else SELD_TAIL_APPLY(float, 1);
+  }
+#undef SELD_TAIL_APPLY
+}
+
 }  // namespace seld
 
 extern "C" {
@@ -519,24 +547,36 @@ int seld_conv_tail_forward(const void* x, const void* residual, int is_bf16, int
   else hipLaunchKernelGGL(tail_stats_final_kernel<float>, fgrid, dim3(kFinalThreads), 0, stream, x,
                           static_cast<long>(rows), C, workspace, nblocks, weight, bias, running_mean, running_var,
                           momentum, eps, training, mean_invstd, scale_shift);
-  const long out_rows = pool == 2 ? rows / 2 : rows;
-  const dim3 grid(tail_grid(st, out_rows, C));
-  const int mode = residual ? 3 : pool;
-#define SELD_TAIL_APPLY(T, P)                                                                                     \
-  hipLaunchKernelGGL((tail_apply_kernel<T, P>), grid, dim3(kTailThreads), 0, stream, x, residual, out_rows, C, \
-                     scale_shift, y)
-  if (is_bf16) {
-    if (mode == 2) SELD_TAIL_APPLY(__hip_bfloat16, 2);
-    else if (mode == 3) SELD_TAIL_APPLY(__hip_bfloat16, 3);
-    else if (mode == 4) SELD_TAIL_APPLY(__hip_bfloat16, 4);
-    else SELD_TAIL_APPLY(__hip_bfloat16, 1);
-  } else {
-    if (mode == 2) SELD_TAIL_APPLY(float, 2);
-    else if (mode == 3) SELD_TAIL_APPLY(float, 3);
-    else if (mode == 4) SELD_TAIL_APPLY(float, 4);
-    else SELD_TAIL_APPLY(float, 1);
-  }
-#undef SELD_TAIL_APPLY
+  launch_tail_apply(st, x, residual, is_bf16, rows, C, pool, scale_shift, y, stream);
+  SELD_HIP_TRY(hipGetLastError());
+  return kOk;
+}
+
+int64_t seld_conv_tail_partial_rows(void) { return seld::kTailStatBlocks; }
+
+// Training-mode forward tail whose statistics pass already happened: `partials` [2][nrows][C] holds plain per-chunk
+// sums of x and x^2 (seld_conv3x3_forward with statistics); finalise + apply only.
+int seld_conv_tail_forward_from_partials(const void* x, int is_bf16, int64_t rows, int C, int pool,
+                                         const float* partials, int64_t nrows, const float* weight, const float* bias,
+                                         float* running_mean, float* running_var, float momentum, float eps, void* y,
+                                         float* mean_invstd, float* scale_shift, void* stream_) {
+  using namespace seld;
+  DeviceState* st = current_state();
+  if (!st) return kErrNotInitialised;
+  if (int rc = tail_check("seld_conv_tail_forward_from_partials", rows, C, pool)) return rc;
+  if (!x || !y || !mean_invstd || !scale_shift || !partials)
+    return fail(kErrInvalidArgument, "seld_conv_tail_forward_from_partials: null pointer");
+  if (nrows <= 0 || nrows > kTailStatBlocks)
+    return fail(kErrUnsupported, "seld_conv_tail_forward_from_partials: 1 .. 1024 partial rows");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const dim3 fgrid((C + kFinalChannels - 1) / kFinalChannels);
+  if (is_bf16) hipLaunchKernelGGL((tail_stats_final_kernel<__hip_bfloat16, false>), fgrid, dim3(kFinalThreads), 0, stream,
+                                  x, static_cast<long>(rows), C, partials, static_cast<int>(nrows), weight, bias,
+                                  running_mean, running_var, momentum, eps, 1, mean_invstd, scale_shift);
+  else hipLaunchKernelGGL((tail_stats_final_kernel<float, false>), fgrid, dim3(kFinalThreads), 0, stream, x,
+                          static_cast<long>(rows), C, partials, static_cast<int>(nrows), weight, bias, running_mean,
+                          running_var, momentum, eps, 1, mean_invstd, scale_shift);
+  launch_tail_apply(st, x, nullptr, is_bf16, rows, C, pool, scale_shift, y, stream);
   SELD_HIP_TRY(hipGetLastError());
   return kOk;
 }

@@ -87,13 +87,40 @@ class _Conv3x3(torch.autograd.Function):
         return dx, dw if dw.dtype == w_dtype else dw.to(w_dtype)
 
 
+class _Conv3x3Stats(torch.autograd.Function):
+    """``_Conv3x3`` with the forward convolution by csrc/convfwd.hip, which also forms the per-chunk sums of y and y^2
+    per channel for the BatchNorm tail that follows (no statistics pass over y).  The sums are appended to the list
+    ``sums`` rather than returned: as a second output they would be handed a zero gradient, one fill launch per block
+    in the backward pass.  Keeps what ``_Conv3x3`` keeps; the backward pass is ``_Conv3x3``'s."""
+
+    @staticmethod
+    def forward(ctx, x, weight, sums):
+        import seld_native
+        with torch.autocast(device_type="cuda", enabled=False):
+            xc, wc = x.to(torch.bfloat16), weight.to(torch.bfloat16)
+            y, partials = seld_native.conv3x3_forward(xc, wc, stats=True)
+        sums.append(partials)
+        ctx.save_for_backward(xc, wc)
+        ctx.dtypes = (x.dtype, weight.dtype)
+        ctx.after_cut = bool(x.is_leaf and x.requires_grad)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _Conv3x3.backward(ctx, dy) + (None,)
+
+
+def _conv3x3_eligible(c, x):
+    return (x.is_cuda and _Conv3x3.enabled and c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1)
+            and c.dilation == (1, 1) and c.groups == 1 and c.bias is None and c.padding_mode == "zeros"
+            and x.is_contiguous(memory_format=torch.channels_last) and torch.is_grad_enabled()
+            and (x.requires_grad or c.weight.requires_grad))
+
+
 def conv3x3(c, x):
     """``c(x)`` for an nn.Conv2d; 3x3 / stride 1 / pad 1 / bias-free convolutions on channels-last GPU activations go
     through ``_Conv3x3`` when gradients are being recorded."""
-    if (x.is_cuda and _Conv3x3.enabled and c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1)
-            and c.dilation == (1, 1) and c.groups == 1 and c.bias is None and c.padding_mode == "zeros"
-            and x.is_contiguous(memory_format=torch.channels_last) and torch.is_grad_enabled()
-            and (x.requires_grad or c.weight.requires_grad)):
+    if _conv3x3_eligible(c, x):
         return _Conv3x3.apply(x, c.weight)
     return c(x)
 
@@ -109,11 +136,43 @@ class ConvBlock(nn.Module):
         self.act = nn.ReLU(inplace=True)
         self.pool = nn.MaxPool2d(pool_size) if pool_size else None
 
+    fused_fwd = True            # forward convolution with BatchNorm sums by csrc/convfwd.hip (config.FUSED_CONV_FWD)
+    # (F, Cin, Cout) of the blocks that use it: those tools/bench_conv_fwd.py measured ahead of the library
+    # convolution + statistics pass at batch 32
+    fused_fwd_adopted = frozenset({(32, 64, 128), (16, 128, 256), (8, 256, 512)})
+
+    def _fused_forward(self, x):
+        """conv + BN sums in one kernel, then finalise + apply: training, bf16 autocast, channels-last, adopted shapes."""
+        c = self.conv
+        if not (ConvBlock.fused_fwd and self.training and x.dim() == 4
+                and (x.shape[3], c.in_channels, c.out_channels) in ConvBlock.fused_fwd_adopted
+                and _conv3x3_eligible(c, x)):
+            return None
+        cdt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else x.dtype
+        if cdt != torch.bfloat16 or x.dtype != torch.bfloat16 or \
+                not c.weight.is_contiguous(memory_format=torch.channels_last):
+            return None
+        import seld_convtail
+        import seld_native
+        # more chunks than the finalise step's partial rows: the general path
+        if not (seld_convtail.applicable_after_conv(self, x)
+                and seld_native.conv3x3_forward_supported(x.shape[3], c.in_channels, c.out_channels)
+                and seld_native.conv3x3_forward_chunks(x.shape[0], x.shape[2], x.shape[3])
+                <= seld_native.conv_tail_partial_rows()):
+            return None
+        sums = []
+        y = _Conv3x3Stats.apply(x, c.weight, sums)
+        return seld_convtail.conv_tail_from_partials(self, y, sums[0])
+
     def forward(self, x):
         if x.is_cuda and self.conv.in_channels <= 8:
             import seld_convfirst
             if seld_convfirst.applicable(self, x):          # first block: convolution recomputed (csrc/convfirst.hip)
                 return seld_convfirst.first_block(self, x)
+        if x.is_cuda:
+            y = self._fused_forward(x)
+            if y is not None:
+                return y
         x = conv3x3(self.conv, x)
         if x.is_cuda:
             import seld_convtail

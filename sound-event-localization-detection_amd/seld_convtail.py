@@ -22,16 +22,27 @@ def bn_applicable(bn, x):
     return bn.training or not (torch.is_grad_enabled() and x.requires_grad)
 
 
+def _pool_ok(pool, x):
+    if pool is None:
+        return True
+    k = pool.kernel_size if isinstance(pool.kernel_size, tuple) else (pool.kernel_size,) * 2
+    s = pool.stride if isinstance(pool.stride, tuple) else (pool.stride,) * 2
+    return not (tuple(k) != (1, 2) or tuple(s) != (1, 2) or pool.padding not in (0, (0, 0)) or pool.ceil_mode
+                or x.dim() != 4 or x.shape[3] % 2)
+
+
 def applicable(block, x):
     """``block``: a ConvBlock; ``x``: the convolution output."""
-    pool = block.pool
-    if pool is not None:
-        k = pool.kernel_size if isinstance(pool.kernel_size, tuple) else (pool.kernel_size,) * 2
-        s = pool.stride if isinstance(pool.stride, tuple) else (pool.stride,) * 2
-        if tuple(k) != (1, 2) or tuple(s) != (1, 2) or pool.padding not in (0, (0, 0)) or pool.ceil_mode \
-                or x.dim() != 4 or x.shape[3] % 2:
-            return False
-    return bn_applicable(block.bn, x)
+    return _pool_ok(block.pool, x) and bn_applicable(block.bn, x)
+
+
+def applicable_after_conv(block, x):
+    """``applicable`` in training mode for the bf16 channels-last output of ``block``'s 3x3 / stride 1 / pad 1
+    convolution of the channels-last GPU activation ``x``, before that output exists (same map size as x)."""
+    bn = block.bn
+    return bool(enabled and bn.training and x.is_cuda and x.dim() == 4 and type(bn) is nn.BatchNorm2d and bn.affine
+                and bn.track_running_stats and bn.momentum is not None and _pool_ok(block.pool, x)
+                and seld_native.conv_tail_supported(bn.num_features))
 
 
 class _ConvTail(torch.autograd.Function):
@@ -53,6 +64,25 @@ class _ConvTail(torch.autograd.Function):
             dx, dweight, dbias = seld_native.conv_tail_backward(x, dy, mean_invstd, scale_shift, ctx.pool)
             dres = None
         return dx, dres, dweight, dbias, None, None, None, None, None, None
+
+
+class _ConvTailFromPartials(torch.autograd.Function):
+    """``_ConvTail`` in training mode without its statistics pass: the per-chunk sums come from the forward convolution's
+    epilogue (csrc/convfwd.hip).  The same tensors are kept and the backward pass is ``_ConvTail``'s."""
+
+    @staticmethod
+    def forward(ctx, x, partials, weight, bias, running_mean, running_var, momentum, eps, pool):
+        y, mean_invstd, scale_shift = seld_native.conv_tail_forward_from_partials(x, partials, weight, bias, running_mean,
+                                                                                  running_var, momentum, eps, pool)
+        ctx.save_for_backward(x, mean_invstd, scale_shift, x.new_empty(0))
+        ctx.pool = pool
+        ctx.has_residual = False
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, _, dweight, dbias = _ConvTail.backward(ctx, dy)[:4]
+        return dx, None, dweight, dbias, None, None, None, None, None
 
 
 _collected = None          # the num_batches_tracked buffers of the fused tails run inside a ``batched_counters`` block
@@ -91,6 +121,17 @@ def bn_relu(bn, x, pool=1, residual=None):
 
 def conv_tail(block, x):
     return bn_relu(block.bn, x, 2 if block.pool is not None else 1)
+
+
+def conv_tail_from_partials(block, x, partials):
+    """``conv_tail`` in training mode on a convolution output whose per-chunk sums ``partials`` [2, chunks, C] are known."""
+    bn = block.bn
+    if _collected is not None:
+        _collected.append(bn.num_batches_tracked)
+    else:
+        bn.num_batches_tracked.add_(1)
+    return _ConvTailFromPartials.apply(x, partials, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum,
+                                       bn.eps, 2 if block.pool is not None else 1)
 
 
 def bn1d_silu_applicable(bn, x):

@@ -128,6 +128,14 @@ def _declare(lib):
     lib.seld_conv3x3_wgrad.argtypes = [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _int, _ptr, _ptr]
     lib.seld_conv3x3_dgrad_supported.argtypes = [_i64, _i64, _i64]
     lib.seld_conv3x3_dgrad.argtypes = [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr]
+    lib.seld_conv3x3_forward_supported.argtypes = [_i64, _i64, _i64]
+    lib.seld_conv3x3_forward_chunks.restype = _i64
+    lib.seld_conv3x3_forward_chunks.argtypes = [_i64, _i64, _i64]
+    lib.seld_conv3x3_forward.argtypes = [_ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr]
+    lib.seld_conv_tail_partial_rows.restype = _i64
+    lib.seld_conv_tail_partial_rows.argtypes = []
+    lib.seld_conv_tail_forward_from_partials.argtypes = [_ptr, _int, _i64, _int, _int, _ptr, _i64, _ptr, _ptr, _ptr, _ptr,
+                                                         ctypes.c_float, ctypes.c_float, _ptr, _ptr, _ptr, _ptr]
     lib.seld_convfirst_supported.argtypes = [_i64, _i64, _i64]
     lib.seld_convfirst_workspace_floats.restype = _i64
     lib.seld_convfirst_workspace_floats.argtypes = [_int]
@@ -1185,6 +1193,31 @@ def conv_tail_forward(x, weight, bias, running_mean, running_var, momentum, eps,
     return y, stats[0], stats[1]
 
 
+def conv_tail_forward_from_partials(x, partials, weight, bias, running_mean, running_var, momentum, eps, pool):
+    """The training-mode ``conv_tail_forward`` without its statistics pass: ``partials`` [2, rows, C] fp32 holds plain
+    sums of x and x^2 over disjoint parts of x (``conv3x3_forward(..., stats=True)``).  Same returns."""
+    rows, c = _tail_view(x)
+    lib = load_library()
+    if not (partials.is_cuda and partials.dtype == torch.float32 and partials.dim() == 3 and partials.is_contiguous()
+            and partials.shape[0] == 2 and partials.shape[2] == c
+            and 1 <= partials.shape[1] <= lib.seld_conv_tail_partial_rows()):
+        raise SeldNativeError("conv_tail: partials must be contiguous fp32 [2, rows <= 1024, C]")
+    b, _, t, f = x.shape
+    width = 2 if pool == 2 else 1
+    if f % width:
+        raise ValueError("conv_tail: the frequency extent must be a multiple of the pool width")
+    index = ensure_init(x.device)
+    y = torch.empty((b, c, t, f // width), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    stats = torch.empty((2, 2, c), dtype=torch.float32, device=x.device)
+    with _device_guard(index):
+        check(lib.seld_conv_tail_forward_from_partials(_p(x), int(x.dtype == torch.bfloat16), rows, c, pool, _p(partials),
+                                                       partials.shape[1], _p(weight), _p(bias), _p(running_mean),
+                                                       _p(running_var), float(momentum), float(eps), _p(y),
+                                                       _p(stats[0]), _p(stats[1]), _stream_ptr(x.device)),
+              "seld_conv_tail_forward_from_partials")
+    return y, stats[0], stats[1]
+
+
 def conv_tail_backward(x, dy, mean_invstd, scale_shift, pool, residual=None):
     """-> (dx like x, dweight [C] fp32, dbias [C] fp32[, dresidual like x when ``residual`` is given])."""
     rows, c = _tail_view(x)
@@ -1654,6 +1687,62 @@ def conv3x3_dgrad(dy: torch.Tensor, w: torch.Tensor, out: "torch.Tensor | None" 
         check(load_library().seld_conv3x3_dgrad(_p(dy), _p(w), b, t, f, cin, cout, _p(out), _stream_ptr(dy.device)),
               "seld_conv3x3_dgrad")
     return out
+
+
+def conv3x3_forward_applicable(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """True when ``conv3x3_forward`` covers this 3x3 / stride 1 / pad 1 convolution: bf16 x [B, Cin, T, F] and bf16
+    weights [Cout, Cin, 3, 3], both in channels-last memory, F in {8, 16, 32}, channel counts multiples of 64."""
+    if not (x.is_cuda and x.dim() == 4 and w.dim() == 4 and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+            and tuple(w.shape[2:]) == (3, 3) and x.shape[1] == w.shape[1]):
+        return False
+    if not (x.is_contiguous(memory_format=torch.channels_last) and w.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    return bool(load_library().seld_conv3x3_forward_supported(x.shape[3], w.shape[1], w.shape[0]))
+
+
+def conv3x3_forward_supported(f: int, cin: int, cout: int) -> bool:
+    return bool(load_library().seld_conv3x3_forward_supported(f, cin, cout))
+
+
+def conv_tail_partial_rows() -> int:
+    """Partial rows per statistic the tail's finalise step takes."""
+    return int(load_library().seld_conv_tail_partial_rows())
+
+
+def conv3x3_forward_chunks(b: int, t: int, f: int) -> int:
+    """Partial rows ``conv3x3_forward(..., stats=True)`` writes: chunks of 256 positions, whole time rows of one clip."""
+    return int(load_library().seld_conv3x3_forward_chunks(b, t, f))
+
+
+def conv3x3_forward(x: torch.Tensor, w: torch.Tensor, stats: bool = False, out: "torch.Tensor | None" = None,
+                    partials: "torch.Tensor | None" = None):
+    """y [B, Cout, T, F] (bf16, channels-last memory; ``out`` when given) = the 3x3 / stride 1 / pad 1 bias-free
+    convolution of x with w (``conv3x3_forward_applicable``), the weights read as they lie.  fp32 accumulation, one
+    rounding; deterministic.  ``stats``: also returns partials [2, chunks, Cout] fp32 (``partials`` when given), the
+    per-chunk sums of the stored y and y^2 per channel."""
+    if not conv3x3_forward_applicable(x, w):
+        raise SeldNativeError("conv3x3_forward: unsupported shapes, dtypes or layouts")
+    b, cin, t, f = x.shape
+    cout = w.shape[0]
+    if out is None:
+        out = torch.empty((b, cout, t, f), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+    elif not (out.dtype == torch.bfloat16 and out.device == x.device and tuple(out.shape) == (b, cout, t, f)
+              and out.is_contiguous(memory_format=torch.channels_last)):
+        raise SeldNativeError("conv3x3_forward: out must be bf16 [B, Cout, T, F] in channels-last memory")
+    with _device_guard(ensure_init(x.device)):
+        lib = load_library()
+        if stats:
+            shape = (2, int(lib.seld_conv3x3_forward_chunks(b, t, f)), cout)
+            if partials is None:
+                partials = torch.empty(shape, dtype=torch.float32, device=x.device)
+            elif not (partials.dtype == torch.float32 and partials.device == x.device and tuple(partials.shape) == shape
+                      and partials.is_contiguous()):
+                raise SeldNativeError("conv3x3_forward: partials must be contiguous fp32 [2, chunks, Cout]")
+        else:
+            partials = None
+        check(lib.seld_conv3x3_forward(_p(x), _p(w), b, t, f, cin, cout, _p(out), _p(partials), _stream_ptr(x.device)),
+              "seld_conv3x3_forward")
+    return (out, partials) if stats else out
 
 
 # --------------------------------------------------------------------------- first encoder block (conv recomputed)

@@ -99,6 +99,8 @@ def prepare_model_for_device(model, device):
             os.environ.get("SELD_CONV_WGRAD", "1") != "0"           # developer switch for A/B runs
         model_crnn._Conv3x3.fused_dgrad = bool(getattr(config, "FUSED_CONV_DGRAD", True)) and \
             os.environ.get("SELD_CONV_DGRAD", "1") != "0"           # developer switch for A/B runs
+        model_crnn.ConvBlock.fused_fwd = bool(getattr(config, "FUSED_CONV_FWD", True)) and \
+            os.environ.get("SELD_CONV_FWD", "1") != "0"             # developer switch for A/B runs
         import seld_convfirst
         seld_convfirst.enabled = bool(getattr(config, "FUSED_FIRST_BLOCK", True)) and \
             os.environ.get("SELD_FIRST_BLOCK", "1") != "0"          # developer switch for A/B runs
