@@ -127,6 +127,39 @@ int seld_gcc_phat_q15(const uint32_t* phasors_q15, int64_t N, int64_t C, int64_t
  * w_0 = w_480 = 1, else 2; zero for k > 480 or n > 32. */
 int seld_gcc_table_host(uint16_t* table);
 
+/* ---- mel-band NIPD, the microphone-array cue of FEATURE_SET 'logmel_nipd' (no upstream
+ * counterpart).  With P_c[k] the phasor word of channel c, bin k (f_k = 25 k Hz), channel 0 the reference, and the bins IN
+ * RANGE those with k >= 1 and min_hz <= f_k <= max_hz:
+ *   phi_m[k]  = atan2(Im, Re) of conj(P_0[k]) P_m[k] on the integers of the two words (Re = re0 rem + im0 imm,
+ *               Im = re0 imm - im0 rem, exact in int32); 0 when either word is 0 (a silent bin);   m = 1..C-1
+ *   nipd_m[j] = sum over in-range k, ascending, in fp32 with fused multiply-adds, of W[k][j] phi_m[k],   j = 0..63
+ *   W[k][j]   = fb[k][j] (-sound_speed / (2 pi f_k)) / sum_{k' in range} fb[k'][j],  fb = seld_default_tables' filterbank;
+ *               0 for a band without an in-range bin.
+ * A channel that is channel 0 delayed by tau seconds has nipd = +sound_speed * tau (metres) in every band.
+ *
+ * seld_nipd_table_host: W as a sparse table -- host only, no GPU, HOST pointers, any of them may be NULL: band j owns
+ * bins first_bin[j] .. first_bin[j] + taps[j] - 1 (taps <= 48: the filterbank's widest band, j = 63, has 44 non-zero bins;
+ * 0, and first_bin 0, for an empty band) with the weights w[j * 48 + i] (fp32) / w_f64[j * 48 + i], zero past the band's taps; evaluated in double, summing in ascending k,
+ * w = (float) w_f64.  -1 for a range that is negative, reversed, above 12 kHz or holds no bin, or a speed that is not
+ * positive.
+ *
+ * seld_nipd_table_bytes: size of the DEVICE table seld_nipd_q15 reads: int32 first_bin[64], int32 taps[64], float
+ * w[64][48], in this order (12 800 bytes).
+ *
+ * seld_nipd_q15: phasors_q15 [N][C][F][seld_phasor_pitch()] as written by seld_logmel_phasors_*, 2 <= C <= 8;
+ *   out[n*sN + (m-1)*sC + j*sM + t*sT] = nipd_m[j] of frame t of clip n;  sM must be 1 and rows 16-byte aligned (out, and
+ *   sN, sC, sT multiples of 4), as for seld_gcc_phat_q15.  Only the in-range words of a row are read.  No allocation,
+ *   nothing but the kernel on `stream`, with one exception: the FIRST call that sees a table address on a device reads
+ *   its 512-byte header back (it synchronises the stream; inside a stream capture that call is refused, so use a table
+ *   once before capturing) and refuses a table with a tap count outside 0..48, a band outside bins 1..480 or no taps at
+ *   all (-1).  A table's contents must not change while its address is in use; the kernel treats a band it could not
+ *   read inside the checked span as empty. */
+int seld_nipd_table_host(double min_hz, double max_hz, double sound_speed, int32_t* first_bin, int32_t* taps, float* w,
+                         double* w_f64);
+int64_t seld_nipd_table_bytes(void);
+int seld_nipd_q15(const uint32_t* phasors_q15, int64_t N, int64_t C, int64_t F, const void* table_dev, float* out,
+                  int64_t sN, int64_t sC, int64_t sM, int64_t sT, void* stream);
+
 /* ---- labels: dataset.py:60-119 metadata_to_labels + utils.py:77-90 polar_to_grid ---------- */
 /* events: int32 [R][5] = (meta_frame, class, source, azimuth_deg, elevation_deg), the CSV rows after
  * the reference's int() casts (dataset.py:93-97).  T = int((L/sr*1000)/20) label frames, computed by

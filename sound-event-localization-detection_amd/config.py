@@ -148,8 +148,14 @@ class Config:
     SYNC_BATCHNORM = False      # per-rank BN statistics by default
     SEED = None                 # the reference never seeds; set an int for reproducible runs
     FEATURE_SET = "logmel"      # 'logmel' (the reference) | 'logmel_iv' (FOA: + 3 intensity-vector channels) |
-                                # 'logmel_gcc' (MIC array: + C(C-1)/2 GCC-PHAT channels); the model's n_channels
-                                # follows the dataset (4 -> 7, 8 -> 36)
+                                # 'logmel_gcc' (MIC array: + C(C-1)/2 GCC-PHAT channels) | 'logmel_nipd' (MIC array: + C-1
+                                # mel-band NIPD channels against channel 0, csrc/nipd.hip); the
+                                # model's n_channels follows the dataset (4 -> 7, 8 -> 36, 8 -> 15)
+    NIPD_MIN_HZ = 50.0          # 'logmel_nipd': STFT bins below this carry no usable phase (the 1 / f of the weights blows
+                                # their noise up); mel bands without a bin in [NIPD_MIN_HZ, NIPD_MAX_HZ] are exactly 0
+    NIPD_MAX_HZ = 2000.0        # should be c / (2 * largest microphone spacing), the spatial-aliasing limit above which a
+                                # phase difference wraps; 2 kHz is SALSA-Lite's value for a 4.2 cm array
+    SOUND_SPEED = 343.0         # m/s: scales the NIPD channels to metres of extra path length (c * delay)
     FEATURE_CACHE_DIR = None    # directory for the per-recording COMPACT features (fp32 log-mel [T,C,64] + uint16 label mask
                                 # [T,648], 2.3 KB per frame): a later SELDDataset construction uploads them instead of
                                 # decoding and transforming the recording again
@@ -170,7 +176,7 @@ class Config:
                                 # rows per frame of the timeline); 'logmel' with 4 channels and 'logmel_iv' only
     AUGMENT_TIME_MASKS = 0      # SpecAugment: time masks per window, 0..2, every channel
     AUGMENT_TIME_MASK_MAX = 0   # longest time mask in frames (a length is uniform in [0, max])
-    AUGMENT_FREQ_MASKS = 0      # frequency masks per window, 0..2, log-mel and intensity-vector channels (not GCC-PHAT lags)
+    AUGMENT_FREQ_MASKS = 0      # frequency masks per window, 0..2, log-mel, intensity-vector and NIPD channels (not GCC-PHAT lags)
     AUGMENT_FREQ_MASK_MAX = 0   # widest frequency mask in mel bins
     AUGMENT_MASK_VALUE = 0.0    # what masked elements are set to (0.0 = what tail windows are padded with)
     FOA_CHANNEL_ORDER = "WYZX"  # which input channel is which: 'WYZX' (STARSS / DCASE FOA recordings) or 'WXYZ'

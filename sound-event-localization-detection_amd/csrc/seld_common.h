@@ -47,6 +47,11 @@ struct DeviceState {
   // kernels that need more dynamic LDS than the default limit: hipFuncSetAttribute is per DEVICE (and is not a stream
   // operation: done once so that launches stay graph-capturable); one bit per kernel family, see need_lds()
   unsigned lds_attr_done = 0;
+  // NIPD tables (device addresses) whose header seld_nipd_q15 has read back and checked, with the span of 16-byte row
+  // units their bins cover (nipd.hip): the check is a synchronous read, done once per address
+  struct NipdChecked { const void* table; int u_lo, u_cnt; };
+  NipdChecked nipd_checked[16] = {};
+  int nipd_checked_n = 0, nipd_checked_next = 0;
   LogmelTables tables() const { return LogmelTables{window, twiddle, mel_b0, mel_wd, mel_wu, mel_pos}; }
 };
 

@@ -73,6 +73,11 @@ def load_audio(audio_path):
     return waveform, rate
 
 
+def _nipd_settings():
+    """(NIPD_MIN_HZ, NIPD_MAX_HZ, SOUND_SPEED) of FEATURE_SET 'logmel_nipd' as this module's config holds them."""
+    return config.NIPD_MIN_HZ, config.NIPD_MAX_HZ, config.SOUND_SPEED
+
+
 def _compute_device():
     if not torch.cuda.is_available():
         raise seld_native.SeldNativeError(
@@ -283,6 +288,8 @@ class SELDDataset(Dataset):
                   self.num_classes, getattr(config, "GRID_CELL_DEGREES", 10), "v2")
         if getattr(config, "RESAMPLE_INPUT", False):       # the converter's design is part of what the arrays depend on;
             fields += ("resample-kaiser10.06-zc64-v1",)    # with the switch off the names are the ones they always were
+        if getattr(config, "FEATURE_SET", "logmel") == "logmel_nipd":      # what the NIPD channels depend on
+            fields += tuple(float(v) for v in _nipd_settings())
         key = "|".join(str(v) for v in fields)
         return Path(root) / f"{a.stem}.{hashlib.sha1(key.encode()).hexdigest()[:16]}.npz"
 
@@ -305,7 +312,7 @@ class SELDDataset(Dataset):
 
     def _file_features_uncached(self, audio_path, metadata_path):
         data, rate, bits = _read_wav(audio_path)
-        if data.shape[0] != 4 and getattr(config, "FEATURE_SET", "logmel") != "logmel_gcc":
+        if data.shape[0] != 4 and getattr(config, "FEATURE_SET", "logmel") not in ("logmel_gcc", "logmel_nipd"):
             logger.warning(f"Expected 4 channels but got {data.shape[0]} channels in {audio_path}")
         if bits == 16:
             pcm = torch.from_numpy(data).to(self.device)                       # int16: half the PCIe / HBM bytes
@@ -322,8 +329,13 @@ class SELDDataset(Dataset):
             # kernels; the labels below keep the FILE's duration, so they do not move
             signal = seld_native.resample(pcm.contiguous(), int(rate), self.sample_rate)
         # [F, C_total, 64]: the reference's per-channel log-mel, optionally followed by the north-star additions
-        # (FOA intensity vectors / GCC-PHAT, csrc/spatial.hip) as extra input channels
-        spec = seld_native.spatial_features(signal, getattr(config, "FEATURE_SET", "logmel"))
+        # (FOA intensity vectors / GCC-PHAT, csrc/spatial.hip; mel-band NIPD, csrc/nipd.hip) as extra input channels
+        feature_set = getattr(config, "FEATURE_SET", "logmel")
+        if feature_set == "logmel_nipd":
+            lo, hi, speed = _nipd_settings()
+            spec = seld_native.spatial_features(signal, feature_set, nipd_min_hz=lo, nipd_max_hz=hi, sound_speed=speed)
+        else:
+            spec = seld_native.spatial_features(signal, feature_set)
         audio_duration = pcm.shape[1] / rate                                   # dataset.py:232 (float64)
         if self.use_gaussian_augmentation:                                      # smrl_seld_gaussian.py:608-618
             mask, _, _ = augment_with_gaussian_mask(rows, audio_duration, self.I, self.J,

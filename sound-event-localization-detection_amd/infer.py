@@ -12,6 +12,8 @@ nearest integer degrees of the detections' sub-cell directions (DESIGN.md sectio
 With ``--resample`` a recording whose rate is not 24 kHz is converted on the GPU first.
 With ``--thresholds`` the per-class detection thresholds of a sweep's thresholds file take the place of ``--threshold``
 (DESIGN.md section 17).
+A checkpoint trained with FEATURE_SET 'logmel_nipd' carries NIPD_MIN_HZ, NIPD_MAX_HZ and SOUND_SPEED in its ``config``: the
+recordings' features are computed with those values, which are logged.
 """
 import argparse
 import logging
@@ -83,6 +85,11 @@ def main(argv=None):
     model_type = args.model_type or getattr(checkpoint.get("config"), "MODEL_TYPE", None)
     if model_type:
         trainer.config.MODEL_TYPE = model_type
+    # FEATURE_SET 'logmel_nipd': the range and the speed of sound the checkpoint's features were computed with
+    own = getattr(checkpoint.get("config"), "__dict__", {})
+    nipd = {k: float(own[k]) for k in trainer.NIPD_SETTINGS if k in own}
+    if nipd:
+        logging.getLogger(__name__).info("NIPD settings of the checkpoint: " + ", ".join(f"{k} = {v:g}" for k, v in nipd.items()))
     patterns = seld_augment.tta_patterns(getattr(trainer.config, "SELD_TTA_PATTERNS", ()) if args.tta is None else args.tta)
     track = {"gate_deg": args.track_gate_deg, "max_gap": args.track_max_gap, "min_len": args.track_min_len} \
         if args.track else False
@@ -96,11 +103,16 @@ def main(argv=None):
         pcm, rate = _pcm(wav)
         saved = dataset.config.RESAMPLE_INPUT
         dataset.config.RESAMPLE_INPUT = bool(args.resample)      # the switch the dataset path reads, for this run only
+        saved_nipd = {k: getattr(dataset.config, k) for k in nipd}
+        for k, v in nipd.items():
+            setattr(dataset.config, k, v)
         try:
             ds = dataset.SELDDataset.from_pcm([pcm], [np.zeros((0, 5), dtype=np.int64)], sample_rate=rate, device=device,
                                               use_gaussian_augmentation=False)
         finally:
             dataset.config.RESAMPLE_INPUT = saved
+            for k, v in saved_nipd.items():
+                setattr(dataset.config, k, v)
         seld_augment.check_tta(patterns, getattr(trainer.config, "FEATURE_SET", "logmel"), ds.n_channels)
         # a checkpoint trained on standardised features carries their statistics: the recording's gathers apply them
         # (Config.STANDARDISE_FEATURES on and none in the checkpoint: an error, as in evaluate_seld)

@@ -86,7 +86,8 @@ def channel_table(feature_set: str, n_channels: int, order: str = "WYZX") -> np.
 
 def freq_mask_channels(feature_set: str, n_channels: int) -> int:
     """Frequency masks apply to channels [0, this): log-mel and intensity vectors have a 64-bin FREQUENCY axis, the 64-wide
-    axis of a GCC-PHAT channel is lags."""
+    axis of a GCC-PHAT channel is lags.  Every other set gets all its channels: that is what 'logmel_nipd' wants, whose
+    2C - 1 channels (C log-mel, C - 1 mel-band NIPD) all lie on the mel axis."""
     if feature_set == "logmel_gcc":                     # C + C(C-1)/2 channels: the first C are log-mel
         c = int(round((np.sqrt(8 * n_channels + 1) - 1) / 2))
         return c if c * (c + 1) // 2 == n_channels else 0

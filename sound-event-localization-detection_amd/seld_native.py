@@ -69,6 +69,10 @@ def _declare(lib):
     lib.seld_gcc_phat_q15.argtypes = [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _ptr]
     lib.seld_gcc_table_host.argtypes = [_ptr]
     lib.seld_gcc_phat.argtypes = [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _ptr]
+    lib.seld_nipd_table_host.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_double, _ptr, _ptr, _ptr, _ptr]
+    lib.seld_nipd_table_bytes.restype = _i64
+    lib.seld_nipd_table_bytes.argtypes = []
+    lib.seld_nipd_q15.argtypes = [_ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr]
     lib.seld_labels_rasterise.argtypes = [_ptr, _i64, _i64, _int, _int, _ptr, _ptr]
     lib.seld_labels_expand.argtypes = [_ptr, _i64, _int, _ptr, _ptr]
     lib.seld_labels_rasterise_box.argtypes = [_ptr, _ptr, _i64, _i64, _int, _int, ctypes.c_double, ctypes.c_double, _ptr,
@@ -1823,33 +1827,127 @@ def stft(pcm: torch.Tensor) -> torch.Tensor:
     return spec[0] if squeeze else spec
 
 
-def spatial_features(pcm: torch.Tensor, kind: str) -> torch.Tensor:
+NIPD_MAX_TAPS = 48          # capacity of a band in the table (csrc/nipd.hip kNipdMaxTaps; the widest band has 44 bins)
+_nipd_tables = {}
+
+
+def _nipd_defaults(min_hz, max_hz, sound_speed):
+    """The range and the speed of sound: what the caller gave, else the Config values."""
+    if min_hz is None or max_hz is None or sound_speed is None:
+        from config import Config
+        min_hz = Config.NIPD_MIN_HZ if min_hz is None else min_hz
+        max_hz = Config.NIPD_MAX_HZ if max_hz is None else max_hz
+        sound_speed = Config.SOUND_SPEED if sound_speed is None else sound_speed
+    return float(min_hz), float(max_hz), float(sound_speed)
+
+
+def nipd_table_host(min_hz: float | None = None, max_hz: float | None = None, sound_speed: float | None = None):
+    """The sparse mel-band NIPD weights on the host, no GPU needed: (first_bin int32 [64], taps int32
+    [64], w float32 [64, 48], w_f64 float64 [64, 48]) as numpy arrays.  Raises for a range the library refuses."""
+    import numpy as np
+    min_hz, max_hz, sound_speed = _nipd_defaults(min_hz, max_hz, sound_speed)
+    first, taps = np.zeros(N_MELS, dtype=np.int32), np.zeros(N_MELS, dtype=np.int32)
+    w, w64 = np.zeros((N_MELS, NIPD_MAX_TAPS), dtype=np.float32), np.zeros((N_MELS, NIPD_MAX_TAPS), dtype=np.float64)
+    check(load_library().seld_nipd_table_host(min_hz, max_hz, sound_speed, ctypes.c_void_p(first.ctypes.data),
+                                              ctypes.c_void_p(taps.ctypes.data), ctypes.c_void_p(w.ctypes.data),
+                                              ctypes.c_void_p(w64.ctypes.data)), "seld_nipd_table_host")
+    return first, taps, w, w64
+
+
+def nipd_pack_table(first_bin, taps, w) -> torch.Tensor:
+    """The device table's layout as one int32 host tensor: first_bin[64] | taps[64] | the bits of w[64][48]."""
+    import numpy as np
+    packed = np.concatenate([np.asarray(first_bin, dtype=np.int32).reshape(N_MELS), np.asarray(taps, dtype=np.int32).reshape(N_MELS),
+                             np.ascontiguousarray(w, dtype=np.float32).reshape(N_MELS * NIPD_MAX_TAPS).view(np.int32)])
+    assert packed.nbytes == int(load_library().seld_nipd_table_bytes())
+    return torch.from_numpy(packed)
+
+
+def nipd_table(device, min_hz: float | None = None, max_hz: float | None = None, sound_speed: float | None = None):
+    """(host tables as ``nipd_table_host``, device table int32 [3200]) of a range and speed, built once per device."""
+    min_hz, max_hz, sound_speed = _nipd_defaults(min_hz, max_hz, sound_speed)
+    device = torch.device(device)
+    index = ensure_init(device)
+    key = (index, min_hz, max_hz, sound_speed)
+    hit = _nipd_tables.get(key)
+    if hit is None:
+        host = nipd_table_host(min_hz, max_hz, sound_speed)
+        hit = (host, nipd_pack_table(*host[:3]).to(torch.device("cuda", index)))
+        _nipd_tables[key] = hit
+    return hit
+
+
+def nipd_q15(phasors: torch.Tensor, out: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """csrc/nipd.hip on the words of ``seld_logmel_phasors_*``: phasors int32 [N, C, F, pitch] (2 <= C <= 8), ``table`` a
+    device table (``nipd_table``), ``out`` float32 [N, F, C - 1, 64] -- any view with unit band stride and 16-byte aligned
+    rows, e.g. channels C.. of a [N, F, 2C - 1, 64] feature tensor -- which receives nipd_1 .. nipd_{C-1}."""
+    n, c, frames, pitch = phasors.shape
+    if phasors.dtype != torch.int32 or not phasors.is_contiguous() or pitch != int(load_library().seld_phasor_pitch()):
+        raise ValueError("nipd_q15: phasors must be contiguous int32 [N, C, F, seld_phasor_pitch()]")
+    if out.dtype != torch.float32 or tuple(out.shape) != (n, frames, c - 1, N_MELS) or out.device != phasors.device:
+        raise ValueError(f"nipd_q15: out must be float32 {(n, frames, c - 1, N_MELS)} on {phasors.device}")
+    if table.dtype != torch.int32 or table.device != phasors.device or not table.is_contiguous() \
+            or table.numel() * 4 != int(load_library().seld_nipd_table_bytes()):
+        raise ValueError("nipd_q15: table must be the int32 device table of nipd_table()")
+    index = ensure_init(phasors.device)
+    s_n, s_t, s_c, s_m = out.stride()
+    with _device_guard(index):
+        check(load_library().seld_nipd_q15(_p(phasors), n, c, frames, _p(table), _p(out), s_n, s_c, s_m, s_t,
+                                           _stream_ptr(phasors.device)), "seld_nipd_q15")
+    return out
+
+
+def feature_channels(kind: str, c: int) -> int:
+    """Feature channels of ``spatial_features(pcm, kind)`` for ``c`` input channels; ValueError for a kind it does not
+    know or a channel count the kind does not take."""
+    if kind == "logmel":
+        return c
+    if kind == "logmel_iv":
+        if c != 4:
+            raise ValueError("FOA intensity vectors need 4 channels (W first)")
+        return c + 3
+    if kind == "logmel_gcc":
+        if not 2 <= c <= 8:
+            raise ValueError("GCC-PHAT supports 2..8 channels")
+        return c + c * (c - 1) // 2
+    if kind == "logmel_nipd":
+        if not 2 <= c <= 8:
+            raise ValueError("NIPD supports 2..8 channels")
+        return c + c - 1
+    raise ValueError(f"unknown feature kind {kind!r}")
+
+
+def spatial_features(pcm: torch.Tensor, kind: str, nipd_min_hz: float | None = None, nipd_max_hz: float | None = None,
+                     sound_speed: float | None = None) -> torch.Tensor:
     """Time-major feature tensor [N, F, C_total, 64] (float32) for one of
       'logmel'      C_total = C                       (the reference's features)
       'logmel_iv'   C_total = 4 + 3   (FOA: log-mel + mel-projected intensity vectors; needs C = 4)
-      'logmel_gcc'  C_total = C + C(C-1)/2            (MIC: log-mel + GCC-PHAT, 2 <= C <= 8)."""
+      'logmel_gcc'  C_total = C + C(C-1)/2            (MIC: log-mel + GCC-PHAT, 2 <= C <= 8)
+      'logmel_nipd' C_total = C + C - 1               (MIC: log-mel + mel-band NIPD against channel 0, 2 <= C <= 8; the
+                    range and the speed of sound from the keyword arguments, else Config.NIPD_MIN_HZ / NIPD_MAX_HZ /
+                    SOUND_SPEED)."""
     pcm, squeeze = _prep_pcm(pcm)
     n, c, length = pcm.shape
     frames = num_frames(length)
     if kind == "logmel":
         out = logmel(pcm, layout="tcf")
         return out[0] if squeeze else out
-    if kind == "logmel_iv":
-        if c != 4:
-            raise ValueError("FOA intensity vectors need 4 channels (W first)")
-        extra = 3
-    elif kind == "logmel_gcc":
-        if not 2 <= c <= 8:
-            raise ValueError("GCC-PHAT supports 2..8 channels")
-        extra = c * (c - 1) // 2
-    else:
-        raise ValueError(f"unknown feature kind {kind!r}")
     index = ensure_init(pcm.device)
-    total = c + extra
+    total = feature_channels(kind, c)
     out = torch.empty((n, frames, total, N_MELS), dtype=torch.float32, device=pcm.device)
     s_n, s_t, s_c, s_m = frames * total * N_MELS, total * N_MELS, N_MELS, 1
     lib = load_library()
     stream = _stream_ptr(pcm.device)
+    if kind == "logmel_nipd":
+        # the phasor pass of 'logmel_gcc' (the same log-mel channels, bit for bit), then the NIPD kernel on its words
+        _, table = nipd_table(pcm.device, nipd_min_hz, nipd_max_hz, sound_speed)
+        pitch = int(lib.seld_phasor_pitch())
+        with _device_guard(index):
+            phasors = torch.empty((n, c, frames, pitch), dtype=torch.int32, device=pcm.device)
+            fn = lib.seld_logmel_phasors_f32 if pcm.dtype == torch.float32 else lib.seld_logmel_phasors_i16
+            check(fn(_p(pcm), n, c, length, _p(out), s_n, s_c, s_m, s_t, _p(phasors), stream), "seld_logmel_phasors")
+        nipd_q15(phasors, out[:, :, c:], table)
+        return out[0] if squeeze else out
     import os
     mode = os.environ.get("SELD_GCC", "mfma")                # developer A/B: "fft" = the FFT kernel, "spectra" = the
     if kind == "logmel_gcc" and mode not in ("fft", "spectra"):     # matrix-core kernel fed with complex64 spectra

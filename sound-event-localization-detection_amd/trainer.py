@@ -781,6 +781,9 @@ def apply_checkpoint_statistics(checkpoint, dataset):
     return stats
 
 
+NIPD_SETTINGS = ("NIPD_MIN_HZ", "NIPD_MAX_HZ", "SOUND_SPEED")
+
+
 def checkpoint_payload(epoch, model, optimizer, train_loss, test_loss, feature_statistics=None):
     """The dict format of trainer.py:278-285 (the Config INSTANCE is pickled, as upstream).  ``feature_statistics``: the
     payload of ``standardise_datasets`` (Config.STANDARDISE_FEATURES), stored under that key; None adds no key.
@@ -800,6 +803,11 @@ def checkpoint_payload(epoch, model, optimizer, train_loss, test_loss, feature_s
     for entry in opt_state["state"].values():
         if isinstance(entry.get("step"), torch.Tensor):
             entry["step"] = entry["step"].detach().float().cpu()
+    if getattr(config, "FEATURE_SET", "logmel") == "logmel_nipd":
+        # a pickled instance carries its OWN attributes only: pin what the NIPD channels were computed with, so that
+        # infer.py reads them from the file and not from whatever the class says on the day it runs
+        for name in NIPD_SETTINGS:
+            setattr(config, name, getattr(config, name))
     payload = {"epoch": epoch, "model_state_dict": model_state_dict(model),
                "optimizer_state_dict": opt_state, "train_loss": train_loss, "test_loss": test_loss,
                "config": config}
