@@ -286,6 +286,36 @@ int seld_window_gather_rotate_affine(const float* src, const float* rot, int64_t
                                      int64_t B, int64_t window, const uint8_t* channel_table, float mask_value,
                                      const float* scale, const float* shift, float* dst, void* stream);
 
+/* ---- windows mixed in pairs, labels united (csrc/mix.hip) ------------------------------------ */
+/* seld_window_gather_augment(_affine) / seld_window_permute_mask where window b may get a PARTNER: another window of the
+ * same timeline.  partners: int64 [B][2] on the device,
+ *   partners[b][0] = sb, the partner's start frame;
+ *   partners[b][1] = fp32 bits of the linear power gain g in bits 0..31 | the partner's spatial pattern pb in bits 32..35.
+ * A g that is not a finite value > 0 (0, negative, NaN, infinity) means NO partner, whatever the other fields hold.  Per
+ * output frame w of window b (a = the window itself: start starts[b], pattern and masks of params[b]):
+ *   row starts[b] + w outside [0, total_rows):   a zero row;
+ *   no partner, or row sb + w outside the timeline:  bit for bit what the entry point without `mix` in its name writes;
+ *   otherwise, with x_a / x_b the stored values of the source channels the channel table names for pa / pb:
+ *     log-mel channel:     power_to_db(P_a + g P_b),  P = 10^(x/10), P = 0 where x <= -100  (floor exactly -100 dB);
+ *     intensity channel:   (E_a IV_a + g E_b IV_b) / (E_a + g E_b), 0 where the denominator is 0,
+ *                          E = P_W + (P_X + P_Y + P_Z) / 3 of the operand at that (frame, bin), IV the signed copies;
+ *     label cell:          perm_pa(mask[starts[b] + w]) | perm_pb(mask[sb + w]).
+ *   Then scale / shift (the _standardised export: the map of the _affine gathers above), then the masks of params[b] on the mixture; labels are never masked.
+ * iv_channels: 0 -- every channel is a log-mel channel (any channels <= SELD_AUGMENT_MAX_CHANNELS); 3 with channels == 7 --
+ * channels 0..3 log-mel, 4..6 intensity vectors.  Anything else: -4.  The kernels reduce both patterns modulo 16, use sb only
+ * through the same row-in-timeline test as starts[b] and only multiply by g: no row of params or partners can make them
+ * read or write out of bounds.  No allocation, no synchronisation (graph-capture safe); a window's output depends on
+ * (source, starts[b], params[b], partners[b]) only.  Refusals and their order as the entry points they extend. */
+int seld_window_gather_mix(const float* src, int64_t total_rows, int channels, int freq_channels, const int64_t* starts,
+                           const int32_t* params, const int64_t* partners, int64_t B, int64_t window,
+                           const uint8_t* channel_table, float mask_value, int iv_channels, float* dst, void* stream);
+int seld_window_gather_mix_standardised(const float* src, int64_t total_rows, int channels, int freq_channels, const int64_t* starts,
+                                  const int32_t* params, const int64_t* partners, int64_t B, int64_t window,
+                                  const uint8_t* channel_table, float mask_value, int iv_channels, const float* scale,
+                                  const float* shift, float* dst, void* stream);
+int seld_window_mix_mask(const uint16_t* src, int64_t total_rows, int I, int J, const int64_t* starts, const int32_t* params,
+                         const int64_t* partners, int64_t B, int64_t window, uint16_t* dst, void* stream);
+
 /* ---- loss: loss.py:43-54 class_mse_loss (+ its backward) ---------------------------------- */
 /* logits [n_cells][14] (fp32, or bf16 when logits_is_bf16), labels as EITHER the compact mask
  * (uint16 [n_cells]) OR dense float32 [n_cells][14] (exactly one non-NULL).  Writes

@@ -179,6 +179,10 @@ class Config:
     AUGMENT_FREQ_MASKS = 0      # frequency masks per window, 0..2, log-mel, intensity-vector and NIPD channels (not GCC-PHAT lags)
     AUGMENT_FREQ_MASK_MAX = 0   # widest frequency mask in mel bins
     AUGMENT_MASK_VALUE = 0.0    # what masked elements are set to (0.0 = what tail windows are padded with)
+    AUGMENT_MIX_PROB = 0.0      # probability that a training window is mixed with a partner window of the timeline, labels
+                                # united (csrc/mix.hip): powers add on the stored features.  'logmel' and
+                                # 'logmel_iv' only; not together with AUGMENT_ROTATE
+    AUGMENT_MIX_GAIN_DB = 6.0   # the partner's level relative to the window: uniform in +- this many dB
     FOA_CHANNEL_ORDER = "WYZX"  # which input channel is which: 'WYZX' (STARSS / DCASE FOA recordings) or 'WXYZ'
     # Per-bin feature standardisation inside the device window gathers (seld_standardise.py, csrc/standardise.hip; DESIGN.md
     # section 22).  Off by default: every entry point, checkpoint and benchmark figure is then what it was

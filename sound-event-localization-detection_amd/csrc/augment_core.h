@@ -100,6 +100,28 @@ __device__ __forceinline__ uint4 masked(uint4 v, int w, int c, int fc, const Win
   return v;
 }
 
+// The partner of window b in the mixing gathers (mix.hip): row b of int64 [B][2] =
+// (start frame sb, fp32 bits of the linear power gain g in bits 0..31 | spatial pattern pb in bits 32..35).  A gain that is
+// not a finite value > 0 (0, negative, NaN, infinity) means NO partner, whatever the other fields hold.  As with a parameter
+// row nothing is trusted: the pattern is reduced modulo 16, the start only goes through the row-in-timeline test, the gain
+// is only multiplied.
+struct Partner {
+  long start;
+  float gain;
+  int pattern;
+  bool on;
+};
+
+__device__ __forceinline__ Partner load_partner(const int64_t* __restrict__ partners, long b) {
+  Partner p;
+  p.start = partners[2 * b];
+  const unsigned long long packed = static_cast<unsigned long long>(partners[2 * b + 1]);
+  p.gain = __uint_as_float(static_cast<unsigned>(packed));
+  p.pattern = static_cast<int>(packed >> 32) & (kPatterns - 1);
+  p.on = p.gain > 0.0f && p.gain < __builtin_huge_valf();            // a NaN fails both comparisons
+  return p;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 static inline unsigned mask_bits(float mask_value) {
   unsigned bits;

@@ -504,7 +504,7 @@ class SELDDataset(Dataset):
         return spec, torch.from_numpy(_expand_mask_host(mask, self.num_classes))
 
     # -- device feed (used by trainer when DEVICE_FEED is on) -----------------------------------
-    def device_batch(self, indices, out=None, augment=None):
+    def device_batch(self, indices, out=None, augment=None, mix=None):
         """Window indices -> (spec [B, 250, C, 64] f32, mask [B, 250, 648] u16) on the device, gathered
         by seld_window_gather straight from the device timeline (no host round trip, no dense labels).
         ``out``: callable (spec_shape, spec_dtype, mask_shape, mask_dtype) -> (spec_buffer, mask_buffer) or None --
@@ -513,9 +513,19 @@ class SELDDataset(Dataset):
         produced by the augmenting gathers (csrc/augment.hip) -- channel swap + label cell permutation + masks; on a dataset
         constructed with Config.AUGMENT_ROTATE (``rot_tm`` exists) by the rotating pair (csrc/rotate.hip), which also honours
         the azimuth step in slot [9] of a row.  After ``set_feature_statistics`` all three feature gathers go through their
-        standardising exports: affine map after the transform, before the masks."""
+        standardising exports: affine map after the transform, before the masks.
+        ``mix``: None, or the windows' partners (``seld_augment.draw_mix``: partner window index or -1, the partner's spatial
+        pattern, its linear power gain): the batch is produced by the mixing pair (csrc/mix.hip) --
+        powers added on the stored features, labels united; a window without a partner is the augmenting pair's, bit for
+        bit.  Needs ``augment`` rows (identity rows will do); not available on a dataset that holds rotation terms."""
         if self.spec_tm is None:
             raise RuntimeError("device_batch needs keep_on_device=True")
+        if mix is not None:
+            if augment is None:
+                raise ValueError("device_batch: mix needs the windows' augment rows (seld_augment.identity_rows will do)")
+            if getattr(self, "rot_tm", None) is not None:
+                raise ValueError("device_batch: mixing is not defined together with the rotating gathers (this dataset was "
+                                 "constructed with AUGMENT_ROTATE and holds rotation terms)")
         starts = torch.as_tensor(self.window_starts[np.asarray(indices, dtype=np.int64)])
         w = self.window_length_frames
         bufs = None
@@ -536,6 +546,24 @@ class SELDDataset(Dataset):
                                                                  out=bufs[1] if bufs else None)
                 return spec, mask
             params = seld_native.augment_params(augment, len(starts), w, self.device)     # one more small async copy
+            if mix is not None:
+                feature_set = getattr(config, "FEATURE_SET", "logmel")
+                if not seld_augment.mix_supported(feature_set):
+                    raise ValueError(f"device_batch: no mix is defined for FEATURE_SET={feature_set!r}")
+                partner, pattern_b, gain = (np.asarray(v).reshape(-1) for v in mix)
+                if not len(partner) == len(pattern_b) == len(gain) == len(starts):
+                    raise ValueError(f"device_batch: mix must hold one (partner, pattern, gain) per window, {len(starts)} here")
+                if len(partner) and (int(partner.min()) < -1 or int(partner.max()) >= len(self.window_starts)):
+                    raise ValueError(f"device_batch: mix partner outside -1..{len(self.window_starts) - 1}")
+                none = partner < 0
+                starts_b = np.where(none, 0, self.window_starts[np.where(none, 0, partner)])
+                partners = seld_native.mix_partners(starts_b, pattern_b, np.where(none, np.float32(0), gain), self.device)
+                spec = seld_native.gather_windows_mix(self.spec_tm, starts, w, params, partners, table, freq_channels,
+                                                      mask_value, seld_augment.mix_iv_channels(feature_set, self.n_channels),
+                                                      out=bufs[0] if bufs else None, scale=scale, shift=shift)
+                mask = seld_native.gather_windows_mix_mask(self.mask_tm, starts, w, params, partners, self.I, self.J,
+                                                           out=bufs[1] if bufs else None)
+                return spec, mask
             spec = seld_native.gather_windows_augment(self.spec_tm, starts, w, params, table, freq_channels, mask_value,
                                                       out=bufs[0] if bufs else None, scale=scale, shift=shift)
             mask = seld_native.gather_windows_permute(self.mask_tm, starts, w, params, self.I, self.J,

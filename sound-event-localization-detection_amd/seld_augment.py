@@ -33,7 +33,7 @@ NEGATE = 0x80                     # channel-table flag: the output channel is MI
 STEP = 9                          # parameter-row slot of the azimuth step r
 MAX_STEPS = 72                    # SELD_ROTATE_MAX_STEPS
 
-SWITCHES = ("AUGMENT_SPATIAL", "AUGMENT_TIME_MASKS", "AUGMENT_FREQ_MASKS", "AUGMENT_ROTATE")
+SWITCHES = ("AUGMENT_SPATIAL", "AUGMENT_TIME_MASKS", "AUGMENT_FREQ_MASKS", "AUGMENT_ROTATE", "AUGMENT_MIX_PROB")
 
 
 def decode(p: int):
@@ -82,6 +82,17 @@ def channel_table(feature_set: str, n_channels: int, order: str = "WYZX") -> np.
             if n_channels == 7:
                 table[p, 3 + c] = (3 + sc) | (NEGATE if sign < 0 else 0)
     return table
+
+
+def mix_supported(feature_set: str) -> bool:
+    """Two windows can be mixed on the stored features where these are powers (log-mel) or power-normalised intensities:
+    'logmel' with any channel count and 'logmel_iv' (DESIGN.md section 24)."""
+    return feature_set in ("logmel", "logmel_iv")
+
+
+def mix_iv_channels(feature_set: str, n_channels: int) -> int:
+    """The ``iv_channels`` argument of the mixing gather: 3 for 'logmel_iv' (channels 4..6), else 0."""
+    return 3 if feature_set == "logmel_iv" and int(n_channels) == 7 else 0
 
 
 def freq_mask_channels(feature_set: str, n_channels: int) -> int:
@@ -162,12 +173,14 @@ def settings(cfg):
         "freq_max": int(getattr(cfg, "AUGMENT_FREQ_MASK_MAX", 0)),
         "mask_value": float(getattr(cfg, "AUGMENT_MASK_VALUE", 0.0)),
         "order": str(getattr(cfg, "FOA_CHANNEL_ORDER", "WYZX")),
+        "mix_prob": float(getattr(cfg, "AUGMENT_MIX_PROB", 0.0)),
+        "mix_gain_db": float(getattr(cfg, "AUGMENT_MIX_GAIN_DB", 6.0)),
     }
 
 
 def enabled(cfg) -> bool:
     s = settings(cfg)
-    return s["spatial"] or s["rotate"] or s["time_masks"] > 0 or s["freq_masks"] > 0
+    return s["spatial"] or s["rotate"] or s["time_masks"] > 0 or s["freq_masks"] > 0 or s["mix_prob"] > 0
 
 
 def check_settings(cfg, feature_set: str | None = None, n_channels: int | None = None):
@@ -191,6 +204,19 @@ def check_settings(cfg, feature_set: str | None = None, n_channels: int | None =
             f"AUGMENT_ROTATE is defined for 4-channel FOA features ('logmel' with 4 channels, 'logmel_iv'), not for "
             f"FEATURE_SET={feature_set!r} with {n_channels} feature channels: a microphone array's geometry is unknown here, "
             f"so no rotation is defined (time / frequency masks work for every feature set)")
+    if not 0.0 <= s["mix_prob"] <= 1.0:                 # a NaN fails both comparisons
+        raise ValueError(f"AUGMENT_MIX_PROB must be a probability in [0, 1], got {s['mix_prob']}")
+    if not (np.isfinite(s["mix_gain_db"]) and s["mix_gain_db"] >= 0):
+        raise ValueError(f"AUGMENT_MIX_GAIN_DB must be finite and not negative, got {s['mix_gain_db']}")
+    if s["mix_prob"] > 0 and s["rotate"]:
+        raise ValueError(
+            "AUGMENT_MIX_PROB cannot be combined with AUGMENT_ROTATE: the mixing gather transforms each operand with one of "
+            "the 16 sign-and-swap patterns (AUGMENT_SPATIAL) and does not read the rotation terms; switch one of them off")
+    if s["mix_prob"] > 0 and feature_set is not None and not mix_supported(feature_set):
+        raise ValueError(
+            f"AUGMENT_MIX_PROB is defined for power features ('logmel' with any channel count, 'logmel_iv'), not for "
+            f"FEATURE_SET={feature_set!r} with {n_channels} feature channels: the powers of two recordings add, the phase cues "
+            f"of two sound fields (GCC-PHAT lags, NIPD) do not add in any stored form, so no mix is defined")
     return s
 
 
@@ -283,3 +309,35 @@ def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, 
                 rows[r, first + 2 * n] = rng.integers(0, axis - length + 1)
                 rows[r, first + 2 * n + 1] = length
     return rows
+
+
+def draw_mix(seed: int, epoch: int, window_indices, cfg, n_windows: int):
+    """The partners of the windows ``window_indices`` of ``epoch`` for the mixing gathers (csrc/mix.hip):
+    (partner int64 [B]: a dataset window index, -1 = none; pattern_b int32 [B]: the partner's spatial pattern;
+    gain float32 [B]: its linear power gain, 0 = none).
+
+    A window's triple comes from ``np.random.default_rng([seed, epoch, index, 1])`` -- a stream of its own, so ``draw`` asks
+    its generator exactly what it asks without the mix -- always in this order: u = random() (a partner iff
+    u < AUGMENT_MIX_PROB), the partner uniform over the ``n_windows`` windows of the dataset, its pattern uniform over the 16
+    (used only with AUGMENT_SPATIAL, else 0), its level uniform in +-AUGMENT_MIX_GAIN_DB dB; the gain is 10^(dB / 10)
+    evaluated in double precision and rounded once.  Like a parameter row the triple is a function of (seed, epoch, window
+    index) only: N ranks see the mixtures of one rank, a wrap-padded repeat gets the same partner."""
+    s = check_settings(cfg)
+    idx = np.asarray(window_indices, dtype=np.int64).reshape(-1)
+    partner = np.full(len(idx), -1, dtype=np.int64)
+    pattern = np.zeros(len(idx), dtype=np.int32)
+    gain = np.zeros(len(idx), dtype=np.float32)
+    if not s["mix_prob"] > 0:
+        return partner, pattern, gain
+    if int(n_windows) <= 0:
+        raise ValueError("draw_mix: the dataset has no windows to draw a partner from")
+    for r, i in enumerate(idx):
+        rng = np.random.default_rng([int(seed), int(epoch), int(i), 1])
+        u = rng.random()
+        other = int(rng.integers(0, int(n_windows)))
+        p = int(rng.integers(0, PATTERNS))
+        level = float(rng.uniform(-s["mix_gain_db"], s["mix_gain_db"]))
+        if u < s["mix_prob"]:
+            partner[r], gain[r] = other, np.float32(10.0 ** (level / 10.0))
+            pattern[r] = p if s["spatial"] else 0
+    return partner, pattern, gain

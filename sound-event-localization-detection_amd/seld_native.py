@@ -92,6 +92,11 @@ def _declare(lib):
                                                       _ptr, _ptr, _ptr, _ptr]
     lib.seld_window_gather_rotate_affine.argtypes = [_ptr, _ptr, _i64, _int, _int, _int, _int, _int, _int, _ptr, _ptr, _i64,
                                                      _i64, _ptr, ctypes.c_float, _ptr, _ptr, _ptr, _ptr]
+    lib.seld_window_gather_mix.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _ptr, _i64, _i64, _ptr, ctypes.c_float, _int,
+                                           _ptr, _ptr]
+    lib.seld_window_gather_mix_standardised.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _ptr, _i64, _i64, _ptr, ctypes.c_float,
+                                                  _int, _ptr, _ptr, _ptr, _ptr]
+    lib.seld_window_mix_mask.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr]
     lib.seld_softmax_mse_workspace_bytes.restype = _i64
     lib.seld_softmax_mse_workspace_bytes.argtypes = []
     lib.seld_softmax_mse.argtypes = [_ptr, _int, _ptr, _ptr, _i64, _int, ctypes.c_float, _ptr, _ptr, _ptr, _ptr]
@@ -742,6 +747,81 @@ def gather_windows_permute_rotate(src: torch.Tensor, starts: torch.Tensor, windo
         check(load_library().seld_window_permute_mask_rotate(_p(src), src.shape[0], I, J, _p(starts), _p(params),
                                                              starts.numel(), window, _p(out), _stream_ptr(src.device)),
               "seld_window_permute_mask_rotate")
+    return out
+
+
+def mix_partners(starts_b, patterns_b, gains, device) -> torch.Tensor:
+    """The partner table of the mixing gathers (csrc/mix.hip) as an int64 [B, 2] device tensor, packed on the host and
+    uploaded with one small asynchronous copy: row b = (start frame of the partner, fp32 bits of the linear power gain in
+    bits 0..31 | the partner's spatial pattern in bits 32..35).  A gain of 0 means no partner.  The host table is checked --
+    pattern in 0..15, gain finite and >= 0; the kernels clamp whatever a device table holds."""
+    import numpy as np
+    starts_b = np.asarray(starts_b, dtype=np.int64).reshape(-1)
+    patterns_b = np.asarray(patterns_b, dtype=np.int64).reshape(-1)
+    gains = np.asarray(gains, dtype=np.float32).reshape(-1)
+    if not len(starts_b) == len(patterns_b) == len(gains):
+        raise ValueError(f"mix partners: starts, patterns and gains must have one entry per window, got {len(starts_b)}, "
+                         f"{len(patterns_b)} and {len(gains)}")
+    if len(starts_b):
+        if int(patterns_b.min()) < 0 or int(patterns_b.max()) >= AUGMENT_PATTERNS:
+            raise ValueError("mix partners: spatial pattern outside 0..15")
+        if not np.isfinite(gains).all() or float(gains.min()) < 0.0:
+            raise ValueError("mix partners: a gain must be finite and >= 0 (0 = no partner)")
+    table = np.empty((len(starts_b), 2), dtype=np.int64)
+    table[:, 0] = starts_b
+    table[:, 1] = gains.view(np.uint32).astype(np.int64) | (patterns_b << 32)
+    return torch.from_numpy(table).to(device, non_blocking=True)
+
+
+def _partner_table(name: str, partners: torch.Tensor, batch: int, device) -> torch.Tensor:
+    if not (isinstance(partners, torch.Tensor) and partners.is_cuda and partners.device == device
+            and partners.dtype == torch.int64 and partners.is_contiguous() and tuple(partners.shape) == (batch, 2)):
+        raise ValueError(f"{name}: partners must be a contiguous int64 [B, 2] GPU tensor (mix_partners)")
+    return partners
+
+
+def gather_windows_mix(src: torch.Tensor, starts: torch.Tensor, window: int, params: torch.Tensor, partners: torch.Tensor,
+                       channel_table=None, freq_channels: int | None = None, mask_value: float = 0.0, iv_channels: int = 0,
+                       out: torch.Tensor | None = None, scale: torch.Tensor | None = None,
+                       shift: torch.Tensor | None = None) -> torch.Tensor:
+    """``gather_windows_augment`` where window b may be mixed with a partner window of the same timeline (csrc/mix.hip,
+    DESIGN.md section 24): ``partners`` int64 [B, 2] on the device (``mix_partners``).  A frame without a partner row is
+    the augmenting gather's, bit for bit; a mixed log-mel value is power_to_db(P_a + g P_b) on the stored dB values, each
+    operand under its own spatial pattern; with ``iv_channels`` = 3 (C = 7, 'logmel_iv') channels 4..6 are intensity vectors,
+    mixed with the band energies as weights.  ``scale`` / ``shift`` and the masks of ``params`` apply to the mixture."""
+    src, index, starts, out = _window_call("gather_windows_mix", src, torch.float32, (None, N_MELS),
+                                           "a float32 GPU tensor [T, C, 64]", starts, window, params, out)
+    partners = _partner_table("gather_windows_mix", partners, starts.numel(), src.device)
+    channels = int(src.shape[1])
+    freq_channels = channels if freq_channels is None else int(freq_channels)
+    table = None if channel_table is None else _channel_table("gather_windows_mix", channel_table, channels)
+    table_p = ctypes.c_void_p(table.ctypes.data) if table is not None else None
+    scale, shift = _affine_tables("gather_windows_mix", scale, shift, src)
+    with _device_guard(index):
+        if scale is not None:
+            check(load_library().seld_window_gather_mix_standardised(
+                _p(src), src.shape[0], channels, freq_channels, _p(starts), _p(params), _p(partners), starts.numel(), window,
+                table_p, float(mask_value), int(iv_channels), _p(scale), _p(shift), _p(out), _stream_ptr(src.device)),
+                "seld_window_gather_mix_standardised")
+        else:
+            check(load_library().seld_window_gather_mix(
+                _p(src), src.shape[0], channels, freq_channels, _p(starts), _p(params), _p(partners), starts.numel(), window,
+                table_p, float(mask_value), int(iv_channels), _p(out), _stream_ptr(src.device)), "seld_window_gather_mix")
+    return out
+
+
+def gather_windows_mix_mask(src: torch.Tensor, starts: torch.Tensor, window: int, params: torch.Tensor,
+                            partners: torch.Tensor, I: int = GRID_I, J: int = GRID_J,
+                            out: torch.Tensor | None = None) -> torch.Tensor:
+    """``gather_windows_permute`` with the labels of each window's partner, moved by the partner's own pattern, ORed in
+    (csrc/mix.hip): the class masks are bit masks, so the union is exact."""
+    src, index, starts, out = _window_call("gather_windows_mix_mask", src, torch.uint16, (I * J,),
+                                           "a uint16 GPU tensor [T, I*J]", starts, window, params, out)
+    partners = _partner_table("gather_windows_mix_mask", partners, starts.numel(), src.device)
+    with _device_guard(index):
+        check(load_library().seld_window_mix_mask(_p(src), src.shape[0], I, J, _p(starts), _p(params), _p(partners),
+                                                  starts.numel(), window, _p(out), _stream_ptr(src.device)),
+              "seld_window_mix_mask")
     return out
 
 

@@ -318,6 +318,9 @@ class DeviceFeed:
             if seld_augment.settings(config)["rotate"] and getattr(self.dataset, "rot_tm", None) is None:
                 raise ValueError("AUGMENT_ROTATE needs a dataset constructed with the switch on and kept on the device: the "
                                  "rotating gather reads three extra mel rows per frame of the timeline (SELDDataset.rot_tm)")
+            if seld_augment.settings(config)["mix_prob"] > 0 and getattr(self.dataset, "rot_tm", None) is not None:
+                raise ValueError("AUGMENT_MIX_PROB cannot be used with a dataset constructed with AUGMENT_ROTATE: its batches "
+                                 "come from the rotating gathers, which do not mix (construct the dataset with the switch off)")
 
     def _order(self, epoch):
         return shard_indices(epoch_order(len(self.dataset), self.shuffle, self.seed, epoch), self.rank, self.world)
@@ -332,10 +335,16 @@ class DeviceFeed:
         epoch and the window's dataset index only).  Only the training loop passes True; with every switch off it is the
         plain gather."""
         augment = bool(augment) and seld_augment.enabled(config)
+        # AUGMENT_MIX_PROB: a partner per window from a stream of its own (seld_augment.draw_mix; csrc/mix.hip)
+        mixing = augment and seld_augment.settings(config)["mix_prob"] > 0
         for idx in batched(self._order(epoch), self.batch_size, self.drop_last):
             params = seld_augment.draw(self.seed, epoch, idx, config, window=self.dataset.window_length_frames) \
                 if augment else None
-            yield self.dataset.device_batch(idx, out=out, augment=params)
+            if not mixing:
+                yield self.dataset.device_batch(idx, out=out, augment=params)
+                continue
+            mix = seld_augment.draw_mix(self.seed, epoch, idx, config, len(self.dataset))
+            yield self.dataset.device_batch(idx, out=out, augment=params, mix=mix)
 
 
 def make_feed(loader, device, rank, world):
