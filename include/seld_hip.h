@@ -322,14 +322,17 @@ int seld_window_mix_mask(const uint16_t* src, int64_t total_rows, int I, int J, 
  * loss_out[0] = mean((softmax(logits) - y)^2) and, if grad != NULL, grad (same dtype/shape as logits)
  * = grad_scale * p_k * ((p_k - y_k) - sum_c p_c (p_c - y_c)); pass grad_scale = 2*w/(n_cells*14) for
  * d(w*loss)/dlogits.  workspace: seld_softmax_mse_workspace_bytes() bytes of device scratch.
- * Deterministic (fixed-order reduction, no float atomics). */
+ * Deterministic (fixed-order reduction, no float atomics).
+ * Alignment: logits and grad may be any pointer aligned for their element type.  Full 256-cell tiles move in 16-byte
+ * pieces when the pointer (logits for the load, grad for the store) is 16-byte aligned, element by element otherwise;
+ * the result is the same bits either way.  Dense label rows are read as float2 (8-byte aligned). */
 int64_t seld_softmax_mse_workspace_bytes(void);
 int seld_softmax_mse(const void* logits, int logits_is_bf16, const uint16_t* mask, const float* dense_labels,
                      int64_t n_cells, int num_classes, float grad_scale, float* loss_out, void* grad,
                      void* workspace, void* stream);
 
 /* ---- loss: loss.py:27-41 class_ce_loss (+ its backward), optional focal factor (csrc/loss_ce.hip) ---- */
-/* logits and labels as seld_softmax_mse (16-byte aligned).  The target t of a cell is the first maximal dense label
+/* logits and labels as seld_softmax_mse, alignment included.  The target t of a cell is the first maximal dense label
  * (torch.argmax) or, for a mask m, the lowest set bit of m & 0x3fff, background (13) if there is none.  class_weights: 14 fp32
  * on the DEVICE, or NULL for all ones.  With p = softmax(z), q = sum_{c != t} p_c, W = sum_cells w_t:
  *   out[0] = (1/W) sum_cells w_t q^gamma (-log p_t)      out[1] = W

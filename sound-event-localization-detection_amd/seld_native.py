@@ -839,6 +839,15 @@ def _workspace(device) -> torch.Tensor:
     return ws
 
 
+def _class_logits(name: str, logits: torch.Tensor) -> torch.Tensor:
+    """The logits of a class-loss call, contiguous: a GPU tensor of float32 or bfloat16."""
+    if not logits.is_cuda:
+        raise SeldNativeError(f"{name}: logits must be a GPU tensor")
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{name}: logits must be float32 or bfloat16")
+    return logits.contiguous()
+
+
 def _class_labels(name: str, logits: torch.Tensor, labels: torch.Tensor, n_cells: int):
     """(labels contiguous, mask pointer, dense pointer) of a class-loss call: exactly one pointer is not None."""
     labels = labels.contiguous()
@@ -854,11 +863,7 @@ def _class_labels(name: str, logits: torch.Tensor, labels: torch.Tensor, n_cells
 def softmax_mse(logits: torch.Tensor, labels: torch.Tensor, grad_scale: float | None = None):
     """loss.py:43-54 fused.  ``labels``: uint16 mask [...cells] or dense float32 [...cells, 14].
     Returns (loss scalar tensor, grad or None); grad has the dtype/shape of ``logits``."""
-    if not logits.is_cuda:
-        raise SeldNativeError("softmax_mse: logits must be a GPU tensor")
-    if logits.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("softmax_mse: logits must be float32 or bfloat16")
-    logits = logits.contiguous()
+    logits = _class_logits("softmax_mse", logits)
     m = logits.shape[-1]
     n_cells = logits.numel() // m
     index = ensure_init(logits.device)
@@ -883,11 +888,7 @@ def softmax_ce(logits: torch.Tensor, labels: torch.Tensor, class_weights: torch.
     mask [...cells] or dense float32 [...cells, 14]; ``class_weights``: 14 values on the logits' device, or None for ones.
     Returns (loss scalar tensor, grad or None[, W = sum of the cells' weights]); grad = grad_scale * d(loss)/d(logits) has the
     dtype/shape of ``logits``.  Nothing is read back: the call can be captured."""
-    if not logits.is_cuda:
-        raise SeldNativeError("softmax_ce: logits must be a GPU tensor")
-    if logits.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("softmax_ce: logits must be float32 or bfloat16")
-    logits = logits.contiguous()
+    logits = _class_logits("softmax_ce", logits)
     m = logits.shape[-1]
     n_cells = logits.numel() // m
     index = ensure_init(logits.device)
@@ -919,26 +920,14 @@ def smr_loss(logits: torch.Tensor, labels: torch.Tensor, grid, w_class: float, w
     """smrl_seld_gaussian.py:946-1072 fused (csrc/loss3.hip).  logits [..., G, 14] with G = grid[0] * grid[1]; labels:
     uint16 mask [..., G] or dense float32 [..., G, 14].  Returns (terms [4] fp32 = total, mse, aiur, cl; grad like logits
     or None)."""
-    if not logits.is_cuda:
-        raise SeldNativeError("smr_loss: logits must be a GPU tensor")
-    if logits.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("smr_loss: logits must be float32 or bfloat16")
+    logits = _class_logits("smr_loss", logits)
     rows, cols = int(grid[0]), int(grid[1])
     m = logits.shape[-1]
     cells = rows * cols
     if logits.dim() < 2 or logits.shape[-2] != cells:
         raise ValueError(f"smr_loss: logits must be [..., {cells}, {m}] for a {rows} x {cols} grid")
-    logits = logits.contiguous()
     frames = logits.numel() // (cells * m)
-    labels = labels.contiguous()
-    if labels.dtype == torch.uint16:
-        if labels.numel() != frames * cells:
-            raise ValueError("smr_loss: mask shape does not match logits")
-        mask_p, dense_p = _p(labels), None
-    else:
-        if labels.dtype != torch.float32 or labels.numel() != logits.numel():
-            raise ValueError("smr_loss: dense labels must be float32 with the logits' shape")
-        mask_p, dense_p = None, _p(labels)
+    labels, mask_p, dense_p = _class_labels("smr_loss", logits, labels, frames * cells)
     index = ensure_init(logits.device)
     lib = load_library()
     out = torch.empty(4, dtype=torch.float32, device=logits.device)

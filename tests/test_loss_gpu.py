@@ -183,6 +183,36 @@ def test_three_term_every_variant(gpu_device, dtype, frames, grid):
         assert (grad.float() - ref_grad).abs().max().item() <= tol * ref_grad.abs().max().item()
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("name", ["softmax_mse", "smr_loss"])
+def test_misaligned_logits_equal_aligned_logits(gpu_device, name, dtype):
+    """The tile mover of csrc/loss_core.h takes its 16-byte route only behind a 16-byte aligned base.  522 cells (58
+    frames of a 3 x 3 grid: two full tiles and a ragged one) as the view [1:] of 523, so that the logits start 28 B
+    (bf16) / 56 B (fp32) and the mask 2 B past an aligned allocation: value and gradient must be the bits of the same
+    call on aligned copies."""
+    import seld_native
+    g = torch.Generator().manual_seed(523)
+    logits = (torch.randn(523, 14, generator=g) * 2).to(gpu_device).to(dtype)[1:].view(58, 9, 14)
+    cls = torch.randint(0, 13, (523,), generator=g).to(torch.int32)
+    mask = torch.where(torch.rand(523, generator=g) < 0.1, torch.ones(1, dtype=torch.int32) << cls,
+                       torch.zeros(1, dtype=torch.int32))
+    mask = mask.to(torch.uint16).to(gpu_device)[1:].view(58, 9)
+    assert logits.is_contiguous() and logits.data_ptr() % 16 != 0 and mask.data_ptr() % 16 != 0
+
+    def run(lg, mk):
+        assert lg.is_contiguous() and mk.is_contiguous()
+        if name == "softmax_mse":
+            return seld_native.softmax_mse(lg, mk, grad_scale=1.0)
+        return seld_native.smr_loss(lg, mk, (3, 3), 1.0, 0.7, 1.3, want_grad=True)
+
+    value, grad = run(logits, mask)
+    aligned_logits, aligned_mask = logits.clone(), mask.clone()
+    assert aligned_logits.data_ptr() % 16 == 0 and aligned_mask.data_ptr() % 16 == 0
+    ref_value, ref_grad = run(aligned_logits, aligned_mask)
+    assert grad.dtype == dtype and bool(torch.isfinite(ref_grad.float()).all()) and float(ref_grad.float().abs().max()) > 0
+    assert torch.equal(value, ref_value) and torch.equal(grad, ref_grad)
+
+
 def test_three_term_module_and_config5_training_step(gpu_device):
     """BASELINE configs[4] on one GPU: ResNet50-Conformer + Gaussian label augmentation + the three-term loss under bf16,
     through the captured training step; the breakdown carries the reference's three keys."""
