@@ -8,9 +8,16 @@
 //     the nine taps are nine row offsets into it.  The weights are not shared between taps: each stage stages its own
 //     slice, so the output tile is GEMM-sized to keep the L2 -> LDS traffic per FLOP low.
 //   * the products are formed transposed, D[n][pos] = W-slice x src^T, so that a lane ends with four consecutive result
-//     channels of one position: 8-byte stores, no shuffle.
-//   * the next stage's weight slice is fetched into registers while the current one multiplies; two workgroups per CU,
-//     one stages while the other multiplies.
+//     channels of one position; the epilogue swaps halves between neighbouring 16-lane rows (v_permlane16_swap_b32) so
+//     that a lane stores eight consecutive channels: 16-byte stores, half as many of them.
+//   * the next stage's weight slice is requested (scalar base + one 32-bit offset per thread) behind the second barrier,
+//     ahead of the stage's first MFMA, and waited for behind its last; the position fragments are read two (four with
+//     the 64-wide tile) steps of kNTiles MFMAs ahead and the weight fragments of the second K half during the first, so
+//     the LDS waits inside a stage are counted ones.  The compiler keeps neither by itself (it used to issue the loads
+//     at the loop header and wait for them right behind the barrier, and to read each fragment just ahead of its
+//     MFMAs): scheduling fences hold the order and tests/test_conv_loop_schedule_cpu.py reads it off the assembly.
+//     Two workgroups per CU, one stages while the other multiplies.  The image is still loaded and stored in two
+//     batches at the top of tap 0 (requesting the first batch under the previous tap's MFMAs was measured: no gain).
 //   * v_mfma_f32_16x16x32_bf16, fp32 accumulation over all of K in a fixed order, one rounding, every output written
 //     once: no atomics, no split-K, the same inputs give the same bits.
 //
@@ -40,6 +47,7 @@ namespace conv3x3 {
 
 constexpr int kLoopP = 256;          // positions per workgroup
 constexpr int kLoopKc = kChannels;   // K channels per stage
+constexpr int kLoopMaxChannels = 1 << 20;   // a weight piece's byte offset inside its slice (< 64 rows of 9 * C) is 32-bit
 
 template <int F, int NT, bool kFwd>
 struct LoopGeom {
@@ -51,6 +59,7 @@ struct LoopGeom {
   static constexpr int kWLoads = kLoopKc * NT / 8 / kThreads;   // 16-byte pieces per thread and stage
   static constexpr int kNTiles = NT / 32;                       // 16-channel tiles per wave
   static constexpr int kImgBatch = (Img::kLoads + 1) / 2;       // 16-byte image pieces per thread and batch
+  static constexpr int kAhead = NT == 128 ? 2 : 4;              // steps a position fragment is read ahead (>= 8 MFMAs)
   static constexpr int kImgShorts = Img::kRows * kPitch;
   static constexpr int kLdsShorts = kImgShorts + kWRows * kWPitch;
   static_assert(2 * kLdsShorts * 2 <= 160 * 1024, "two workgroups per CU");
@@ -98,32 +107,38 @@ __device__ __forceinline__ void conv3x3_loop(const unsigned short* __restrict__ 
   const int d_off = image_row<F>(wm * 128 + l15) * kPitch + 8 * g;
   auto d_rows = [](int m) { return image_row<F>(16 * m) - image_row<F>(0); };
 
-  // the prefetched weight slice lives across the loop's back edge: named registers (as an array it stays in scratch)
+  // the prefetched weight slice lives across the loop's back edge: named registers (as an array it stays in scratch).
+  // A piece's address is a wave-uniform base (the stage's tap and K slice, and the piece's row group: scalar registers)
+  // plus one 32-bit byte offset per thread that is the same for every piece and stage: no address registers live
+  // across the loop and no vector multiplies between the MFMAs.
   static_assert(G::kWLoads == 2 || G::kWLoads == 4, "weight pieces per thread");
-  uint4 rw0, rw1, rw2 = make_uint4(0u, 0u, 0u, 0u), rw3 = rw2;
-  auto w_piece = [&](int stage, int i) {
-    const int kc = stage / 9, tap = stage - kc * 9;
-    const int piece = tid + i * kThreads;
-    if constexpr (kFwd) {
-      const int row = piece >> 3, ch = piece & 7;
-      return *reinterpret_cast<const uint4*>(w + (static_cast<long>(n0 + row) * 9 + tap) * Ck + kc * kLoopKc + ch * 8);
-    } else {
-      const int row = piece / (NT / 8), ch = piece % (NT / 8);
-      return *reinterpret_cast<const uint4*>(w + (static_cast<long>(kc * kLoopKc + row) * 9 + tap) * Cn + n0 + ch * 8);
-    }
+  constexpr int kWPieceRows = kFwd ? kThreads / 8 : kThreads / (NT / 8);        // slice rows between a thread's pieces
+  const long w_row = 9L * (kFwd ? Ck : Cn);                                     // elements per slice row
+  const unsigned w_voff = kFwd ? ((tid >> 3) * 9 * Ck + (tid & 7) * 8) * 2u
+                               : ((tid / (NT / 8)) * 9 * Cn + (tid % (NT / 8)) * 8) * 2u;
+  u32x4 rw0, rw1, rw2 = u32x4{0u, 0u, 0u, 0u}, rw3 = rw2;
+  auto w_piece = [&](const unsigned short* base, int i, unsigned voff) {
+    return *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(base + i * kWPieceRows * w_row) + voff);
   };
   auto load_w = [&](int stage) {
-    rw0 = w_piece(stage, 0);
-    rw1 = w_piece(stage, 1);
+    // the offset's widening must stay beside the loads for the scalar-base form of the load to be chosen: hoisted
+    // out of the loop it comes back as four 64-bit vector addresses per stage
+    unsigned voff = w_voff;
+    asm volatile("" : "+v"(voff));
+    const int kc = stage / 9, tap = stage - kc * 9;
+    const unsigned short* const base = kFwd ? w + (n0 * 9L + tap) * Ck + kc * kLoopKc
+                                            : w + (kc * kLoopKc * 9L + tap) * Cn + n0;
+    rw0 = w_piece(base, 0, voff);
+    rw1 = w_piece(base, 1, voff);
     if constexpr (G::kWLoads == 4) {
-      rw2 = w_piece(stage, 2);
-      rw3 = w_piece(stage, 3);
+      rw2 = w_piece(base, 2, voff);
+      rw3 = w_piece(base, 3, voff);
     }
   };
   auto w_slot = [&](int i) {
     const int piece = tid + i * kThreads;
-    if constexpr (kFwd) return reinterpret_cast<uint4*>(lw + (piece >> 3) * G::kWPitch + (piece & 7) * 8);
-    else return reinterpret_cast<uint4*>(lw + piece / (NT / 8) * G::kWPitch + piece % (NT / 8) * 8);
+    if constexpr (kFwd) return reinterpret_cast<u32x4*>(lw + (piece >> 3) * G::kWPitch + (piece & 7) * 8);
+    else return reinterpret_cast<u32x4*>(lw + piece / (NT / 8) * G::kWPitch + piece % (NT / 8) * 8);
   };
 
   const int stages = Ck / kLoopKc * 9;
@@ -134,9 +149,13 @@ __device__ __forceinline__ void conv3x3_loop(const unsigned short* __restrict__ 
     // is in flight while the other waves finish the previous stage
     uint4 rimg[G::kImgBatch];
     auto load_img = [&](int first) {
+      // the pieces' addresses and bounds are derived again for every image (once per nine stages) behind an empty
+      // asm: kept over the loop they would cost twelve registers beside the accumulators
+      int t = tid;
+      asm volatile("" : "+v"(t));
 #pragma unroll
       for (int i = 0; i < G::kImgBatch; ++i)
-        rimg[i] = image_piece<F, kLoopP>(src, clip_row, t0, T, Ck, kc * kLoopKc, tid + (first + i) * kThreads);
+        rimg[i] = image_piece<F, kLoopP>(src, clip_row, t0, T, Ck, kc * kLoopKc, t + (first + i) * kThreads);
     };
     auto store_img = [&](int first) {
 #pragma unroll
@@ -168,47 +187,74 @@ __device__ __forceinline__ void conv3x3_loop(const unsigned short* __restrict__ 
       store_img(G::kImgBatch);
     }
     __syncthreads();
-    load_w(min(stage + 1, stages - 1));                         // in flight under this stage's products (the last
-                                                                // stage fetches its own slice again: no branch)
+    // the next slice is requested here, ahead of this stage's first MFMA, and waited for behind its last (the last
+    // stage fetches its own slice again: no branch).  Nothing may move across the fence; without it and the use of
+    // the registers below, the compiler merges these loads with the ones ahead of the loop and issues them at the
+    // loop header, where every stage waits a full load latency for them behind the barrier.
+    load_w(min(stage + 1, stages - 1));
+    __builtin_amdgcn_sched_barrier(0);
 
     // forward reads src at (t + r - 1, f + s - 1); the data gradient at (t + 1 - r, f + 1 - s): the mirrored offset
     const int shift = (kFwd ? tap_shift<F>(tap) : -tap_shift<F>(tap)) * kPitch;
+    // a stage is 16 steps (ks, m) of kNTiles MFMAs.  The position fragment of a step is read kAhead steps before
+    // its MFMAs and the weight fragments of ks = 1 during the first steps of ks = 0, so the waits are counted
+    // (lgkmcnt(N > 0)) instead of one full LDS latency per step.  A fence after every step keeps that order.
+    constexpr int kSteps = 8 * (kLoopKc / 32);
+    constexpr int kAhead = G::kAhead;
+    auto read_w = [&](int ks, int n) {
+      if constexpr (kFwd)
+        return *reinterpret_cast<const bf16x8*>(lw + w_off + n * 16 * G::kWPitch + ks * 32);
+      else
+        return join(tr_read(lw, w_off + ks * 32 * G::kWPitch + n * 16),
+                    tr_read(lw, w_off + (ks * 32 + 16) * G::kWPitch + n * 16));
+    };
+    auto read_d = [&](int step) {
+      return *reinterpret_cast<const bf16x8*>(limg + d_off + d_rows(step & 7) * kPitch + shift + (step >> 3) * 32);
+    };
+    bf16x8 wf[kLoopKc / 32][G::kNTiles], df[kAhead + 1];
 #pragma unroll
-    for (int ks = 0; ks < kLoopKc / 32; ++ks) {
-      bf16x8 wf[G::kNTiles];
+    for (int n = 0; n < G::kNTiles; ++n) wf[0][n] = read_w(0, n);
 #pragma unroll
-      for (int n = 0; n < G::kNTiles; ++n) {
-        if constexpr (kFwd)
-          wf[n] = *reinterpret_cast<const bf16x8*>(lw + w_off + n * 16 * G::kWPitch + ks * 32);
-        else
-          wf[n] = join(tr_read(lw, w_off + ks * 32 * G::kWPitch + n * 16),
-                       tr_read(lw, w_off + (ks * 32 + 16) * G::kWPitch + n * 16));
-      }
+    for (int a = 0; a < kAhead; ++a) df[a] = read_d(a);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        const bf16x8 df = *reinterpret_cast<const bf16x8*>(limg + d_off + d_rows(m) * kPitch + shift + ks * 32);
+    for (int step = 0; step < kSteps; ++step) {
+      const int ks = step >> 3, m = step & 7;
+      if (step + kAhead < kSteps) df[(step + kAhead) % (kAhead + 1)] = read_d(step + kAhead);
+      if (ks + 1 < kLoopKc / 32 && m < G::kNTiles) wf[ks + 1][m] = read_w(ks + 1, m);
 #pragma unroll
-        for (int n = 0; n < G::kNTiles; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[n], df, acc[m][n], 0, 0, 0);
-      }
+      for (int n = 0; n < G::kNTiles; ++n)
+        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][n], df[step % (kAhead + 1)], acc[m][n], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
     }
+    // the prefetched slice is due here, not earlier
+    asm volatile("" : "+v"(rw0), "+v"(rw1));
+    if constexpr (G::kWLoads == 4) asm volatile("" : "+v"(rw2), "+v"(rw3));
   }
 
-  // C/D of the 16x16 tile: column (position) = lane & 15, rows (result channel) = 4 * (lane >> 4) + j
+  // C/D of the 16x16 tile: column (position) = lane & 15, rows (result channel) = 4 * (lane >> 4) + j.  Two position
+  // tiles are stored together: the 16-lane rows g and g + 1 (g even) hold channels 4g .. 4g+3 and 4g+4 .. 4g+7 of the
+  // same positions, and v_permlane16_swap_b32 hands row g the other row's half of tile 2k and row g + 1 the other
+  // row's half of tile 2k + 1, so every lane stores 8 consecutive channels of one position: half as many store
+  // instructions of 16 bytes (the tail of 8-byte stores was issue-bound), the same bytes at the same addresses.
   const int rows_left = (T - t0) * F;                           // positions of the chunk inside the clip
-  unsigned short* const out = dst + ((clip_row + t0) * F) * Cn + n0 + wn * (NT / 2) + 4 * g;
+  unsigned short* const out = dst + ((clip_row + t0) * F) * Cn + n0 + wn * (NT / 2) + 4 * (g & ~1);
+  auto pack = [](float a, float c) {
+    return static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(a))) |
+           (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(c))) << 16);
+  };
 #pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    const int pos = wm * 128 + m * 16 + l15;
-    if (pos >= rows_left) continue;
+  for (int k = 0; k < 4; ++k) {
+    const int pos = wm * 128 + (2 * k + (g & 1)) * 16 + l15;
 #pragma unroll
     for (int n = 0; n < G::kNTiles; ++n) {
-      const f32x4 v = acc[m][n];
-      const unsigned lo = static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(v[0]))) |
-                          (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(v[1]))) << 16);
-      const unsigned hi = static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(v[2]))) |
-                          (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(v[3]))) << 16);
-      *reinterpret_cast<uint2*>(out + static_cast<long>(pos) * Cn + n * 16) = make_uint2(lo, hi);
+      const f32x4 v0 = acc[2 * k][n], v1 = acc[2 * k + 1][n];
+      // [0]: rows 0, 2 keep their value of tile 2k, rows 1, 3 receive rows 0, 2's value of tile 2k + 1;
+      // [1]: rows 0, 2 receive rows 1, 3's value of tile 2k, rows 1, 3 keep their value of tile 2k + 1
+      const u32x2 lo = __builtin_amdgcn_permlane16_swap(pack(v0[0], v0[1]), pack(v1[0], v1[1]), false, false);
+      const u32x2 hi = __builtin_amdgcn_permlane16_swap(pack(v0[2], v0[3]), pack(v1[2], v1[3]), false, false);
+      if (pos < rows_left)
+        *reinterpret_cast<u32x4*>(out + static_cast<long>(pos) * Cn + n * 16) = u32x4{lo[0], hi[0], lo[1], hi[1]};
     }
   }
 

@@ -17,9 +17,10 @@
 //     the same relabelling the staging pass writes each 32-channel group of an image row in the order
 //     0-3, 16-19, 4-7, 20-23, 8-11, 24-27, 12-15, 28-31 (two 8-byte stores per 16-byte piece).
 //   * the products are formed transposed, D[ci][pos] = W^T dy^T, so that a lane ends with four consecutive input
-//     channels of one position: 8-byte stores, no shuffle.
-//   * the next stage's weight slice is fetched into registers while the current one multiplies; two workgroups per CU
-//     (at most 72 832 B of LDS each), one stages while the other multiplies.
+//     channels of one position; neighbouring lane rows swap halves and a lane stores eight of them, 16 bytes.
+//   * the next stage's weight slice is requested ahead of the current stage's MFMAs and waited for behind them
+//     (conv3x3_loop.h says how that is held against the compiler); two workgroups per CU (at most 72 832 B of LDS
+//     each), one stages while the other multiplies.
 //   * v_mfma_f32_16x16x32_bf16, fp32 accumulation over all of K in a fixed order, one rounding, every output written
 //     once: no atomics, no split-K, the same inputs give the same bits.
 #include <hip/hip_bf16.h>
@@ -45,7 +46,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_dgrad_kernel(
 }
 
 bool dgrad_supported(int64_t F, int64_t Cin, int64_t Cout) {
-  return (F == 8 || F == 16 || F == 32) && Cin > 0 && Cout > 0 && Cin % 64 == 0 && Cout % kDgKc == 0;
+  return (F == 8 || F == 16 || F == 32) && Cin > 0 && Cout > 0 && Cin % 64 == 0 && Cout % kDgKc == 0 &&
+         Cin <= kLoopMaxChannels && Cout <= kLoopMaxChannels;
 }
 
 template <int F>

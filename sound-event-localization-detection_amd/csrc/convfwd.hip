@@ -33,7 +33,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_fwd_kernel(
 }
 
 bool fwd_supported(int64_t F, int64_t Cin, int64_t Cout) {
-  return (F == 8 || F == 16 || F == 32) && Cin > 0 && Cout > 0 && Cin % kLoopKc == 0 && Cout % 64 == 0;
+  return (F == 8 || F == 16 || F == 32) && Cin > 0 && Cout > 0 && Cin % kLoopKc == 0 && Cout % 64 == 0 &&
+         Cin <= kLoopMaxChannels && Cout <= kLoopMaxChannels;
 }
 
 int64_t fwd_chunks(int64_t B, int64_t T, int64_t F) {
