@@ -7,7 +7,7 @@
 // its gradient dx1 another 65.5 MB; the block's real operands are the 4 MB input, the 33 MB pooled output and the
 // 33 MB pooled gradient.  Block 1 has no data gradient (its input is data), so dx1 only ever feeds the weight gradient.
 //
-//   forward  1  stats    : in -> conv -> sum / sum of squares partials per channel                   (x1 not written)
+//   forward  1  stats    : in -> conv -> sum / sum of squares (in double) partials per channel       (x1 not written)
 //               finalise : partials -> mean / invstd / a, b, running statistics                      (8 small workgroups)
 //            2  apply    : in -> conv -> max_pair(relu(round(a x + b))) -> y
 //   backward 3  reduce   : in, dy -> conv -> routing (ReLU gate, first-wins argmax) -> sum dz, sum dz x partials
@@ -270,17 +270,44 @@ __device__ __forceinline__ void cf_block_partials(const f32x4 (&colsum)[4], cons
   }
 }
 
+// The statistics kernel's partial row: the column sums as above; the sums of squares arrive as doubles (lane group c / 4
+// holds channel 4 c + nt), are added in wave order in double and stored as a float pair hi + lo in planes 1 and 2.
+__device__ __forceinline__ void cf_stats_partials(const f32x4 (&colsum)[4], const double (&sq)[4], float* part /* [4 * 64] */,
+                                                  double* partd /* [4 * 64] */, float* __restrict__ partials, int nrows) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+    if (g == 0) part[wave * kCfCout + 4 * c + nt] = colsum[nt][0];
+    if (g == (c >> 2)) partd[wave * kCfCout + 4 * c + nt] = sq[nt];
+  }
+  __syncthreads();
+  if (tid < kCfCout) {
+    const float sum = ((part[tid] + part[kCfCout + tid]) + part[2 * kCfCout + tid]) + part[3 * kCfCout + tid];
+    const double sumsq = ((partd[tid] + partd[kCfCout + tid]) + partd[2 * kCfCout + tid]) + partd[3 * kCfCout + tid];
+    const float hi = static_cast<float>(sumsq), lo = static_cast<float>(sumsq - static_cast<double>(hi));
+    const long row = static_cast<long>(blockIdx.x) * kCfCout + tid, plane = static_cast<long>(nrows) * kCfCout;
+    partials[row] = sum;
+    partials[plane + row] = hi;
+    partials[2 * plane + row] = lo;
+  }
+}
+
 // The finalise launches: block cg reduces the partial rows of channels 8 cg .. 8 cg + 7 (both statistics) in double in a
 // fixed order -- 16 row subsets, then the subsets in order -- and thread ch < 8 finishes its channel.  (Reducing the rows
 // in the prologue of every workgroup of the next kernel instead was measured: 256 - 512 workgroups each pulling the
 // 128 - 256 KB of partials through L2 cost that kernel 6 - 8 us, a launch of this costs 2 - 3.)
 constexpr int kCfFinalThreads = 256;
 
+// (kLowPlane: the second statistic is a float pair, its low halves in plane 2 -- cf_stats_partials)
+template <bool kLowPlane>
 __device__ __forceinline__ void cf_final_sums(const float* __restrict__ partials, int nrows, double* red /* [16 * 16] */) {
   const int tid = threadIdx.x, item = tid & 15, s = item >> 3, ch = blockIdx.x * 8 + (item & 7), rg = tid >> 4;
   double sum = 0.0;
 #pragma unroll 8
-  for (int r = rg; r < nrows; r += 16) sum += static_cast<double>(partials[(static_cast<long>(s) * nrows + r) * kCfCout + ch]);
+  for (int r = rg; r < nrows; r += 16) {
+    sum += static_cast<double>(partials[(static_cast<long>(s) * nrows + r) * kCfCout + ch]);
+    if (kLowPlane && s == 1) sum += static_cast<double>(partials[(2L * nrows + r) * kCfCout + ch]);
+  }
   red[rg * 16 + item] = sum;
   __syncthreads();
   if (tid < 16) {
@@ -296,7 +323,7 @@ __global__ __launch_bounds__(kCfFinalThreads) void convfirst_stats_final_kernel(
     const float* __restrict__ bias, float* __restrict__ running_mean, float* __restrict__ running_var, float momentum,
     float eps, float* __restrict__ mean_invstd, float* __restrict__ scale_shift) {
   __shared__ double red[16 * 16];
-  cf_final_sums(partials, nrows, red);
+  cf_final_sums<true>(partials, nrows, red);
   if (threadIdx.x < 8) {
     const int ch = blockIdx.x * 8 + threadIdx.x;
     const double n = static_cast<double>(rows);
@@ -309,7 +336,8 @@ __global__ __launch_bounds__(kCfFinalThreads) void convfirst_stats_final_kernel(
     const float meanf = static_cast<float>(mean);
     const float invstd = static_cast<float>(1.0 / sqrt(var + static_cast<double>(eps)));
     // two roundings (the fp32 invstd, then the product): up to 1.5 ulp from weight / sigma, so up to 1 ulp from the `a` of
-    // csrc/convtail.hip, which rounds weight * the double invstd once; no test pins this path's `a` to the ulp
+    // csrc/convtail.hip, which rounds weight * the double invstd once; tests/test_convfirst_parity_gpu.py pins this
+    // path's `a` to fl32(weight * the returned invstd) bit for bit and the invstd to the float64 value
     const float a = weight[ch] * invstd;
     mean_invstd[ch] = meanf;
     mean_invstd[kCfCout + ch] = invstd;
@@ -324,7 +352,7 @@ __global__ __launch_bounds__(kCfFinalThreads) void convfirst_bwd_final_kernel(
     const float* __restrict__ scale_shift, float* __restrict__ dgamma, float* __restrict__ dbeta,
     float* __restrict__ coef /* [2][64] p, q */) {
   __shared__ double red[16 * 16];
-  cf_final_sums(partials, nrows, red);
+  cf_final_sums<false>(partials, nrows, red);
   if (threadIdx.x < 8) {
     const int ch = blockIdx.x * 8 + threadIdx.x;
     const double invstd = mean_invstd[kCfCout + ch], mean = mean_invstd[ch], a = scale_shift[ch];
@@ -345,18 +373,26 @@ __global__ __launch_bounds__(kCfFinalThreads) void convfirst_bwd_final_kernel(
   const CfLane ln = cf_lane(gm.logF, lane, wave)
 
 // ------------------------------------------------------------------------------------------------ 1: statistics
-// sum x and sum x^2 per channel.  The products x * x of bf16 values are exact in fp32 and an accumulator takes only the
-// few hundred positions of one wave before the partials are combined in double, so no shift is needed to keep
-// E[x^2] - E[x]^2 from cancelling (convtail.hip's per-thread chains are a thousand times longer and are shifted).
+// sum x and sum x^2 per channel.  The products x * x of bf16 values are exact in fp32; each matrix instruction adds the
+// squares of 32 positions into a ZERO accumulator and its diagonal is then added up in double, in the wave, across the
+// waves and across the workgroups, so the only fp32 roundings a square passes through are those inside one instruction:
+// invstd stays within an ulp of the float64 value even when a single chunk leaves nothing to average over (a chained fp32
+// accumulator was 1.09 ulp off there), and no shift is needed to keep E[x^2] - E[x]^2 from cancelling.
 __global__ __launch_bounds__(kCfThreads, 2) void convfirst_stats_kernel(const void* __restrict__ in, CfWeights w, CfGeom gm,
                                                                         float* __restrict__ partials) {
   __shared__ uint2 img[kCfImage];
-  __shared__ float part[4 * 128];
+  __shared__ float part[4 * kCfCout];
+  __shared__ double partd[4 * kCfCout];
   SELD_CF_PROLOGUE();
-  f32x4 colsum[4], diag[4];
+  f32x4 colsum[4];
+  double sq[4];                                                  // channel 4 c + nt, valid in lane group c / 4
 #pragma unroll
-  for (int nt = 0; nt < 4; ++nt) colsum[nt] = diag[nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  for (int nt = 0; nt < 4; ++nt) {
+    colsum[nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    sq[nt] = 0.0;
+  }
   const bf16x8 ones = cf_ones();
+  const int dj = lane & 3;                                       // the diagonal element (c, c) is j = c % 4 of group c / 4
   uint2 rin[kCfStage];
   int chunk = blockIdx.x;
   if (chunk < gm.chunks) cf_load_image(in2, gm, cf_chunk(gm, chunk), rin);
@@ -378,11 +414,12 @@ __global__ __launch_bounds__(kCfThreads, 2) void convfirst_stats_kernel(const vo
       for (int nt = 0; nt < 4; ++nt) {
         const bf16x8 x = cf_operand(xp[0][nt], xp[1][nt]);
         colsum[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, x, colsum[nt], 0, 0, 0);
-        diag[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, x, diag[nt], 0, 0, 0);
+        const f32x4 diag = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, x, f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+        sq[nt] += static_cast<double>(cf_pick(diag, dj));
       }
     }
   }
-  cf_block_partials(colsum, diag, part, partials, gridDim.x);
+  cf_stats_partials(colsum, sq, part, partd, partials, gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------ 2: apply
@@ -720,7 +757,7 @@ int seld_convfirst_supported(int64_t F, int64_t Cin, int64_t Cout) { return seld
 
 int64_t seld_convfirst_workspace_floats(int backward) {
   using namespace seld;
-  const int64_t partials = 2LL * kCfMaxGroups * kCfCout;
+  const int64_t partials = 3LL * kCfMaxGroups * kCfCout;      // forward: sum, sum of squares as a float pair
   return backward ? partials + static_cast<int64_t>(kCfMaxGroups) * kCfCout * kCfK + 2 * kCfCout : partials;
 }
 

@@ -5,7 +5,10 @@ Reference: the stock Conv2d -> BatchNorm2d -> ReLU -> MaxPool2d((1, 2)) in fp32 
 weights.  Against it stand today's general path (the library's bf16 convolution, seld_native.conv_tail_forward /
 conv_tail_backward, aten.convolution_backward) and the new kernels.  The two differ only in the order in which the 36
 products of an output are added ahead of the same single rounding to bf16, so their errors against the reference must be
-equal statistically: no absolute tolerance, the new error is held to a multiple of the old one."""
+equal statistically: no absolute tolerance, the new error is held to a multiple of the old one.
+
+Element-wise parity (every y bit for bit, every dW element under a derived bound, edges, the chunk walk, guard regions)
+is in tests/test_convfirst_parity_gpu.py."""
 import pytest
 import torch
 import torch.nn as nn
