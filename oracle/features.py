@@ -177,8 +177,10 @@ def foa_intensity_f64(pcm: np.ndarray, eps: float = 1e-8) -> np.ndarray:
 def gcc_phat_f64(pcm: np.ndarray, n_lags: int = N_MELS) -> np.ndarray:
     """[C, L] -> [C(C-1)/2, 64, F]: cc = irfft(exp(1j*angle(conj(X_m) X_n))), lags -32..31.
     A bin of a SILENT channel has the phase factor 1.  Silent means |X|^2 <= GCC_SILENCE_POWER (1e-12: below the
-    noise floor of any recording, above what a transform that packs two frames leaves in an all-zero frame -- about
-    1e-7 of its neighbour's amplitude).  Without the rule numpy's angle() of a zero depends on the SIGNS of its zero
+    noise floor of any recording).  An all-zero frame has spectrum exactly 0 here; a transform that packs two frames
+    leaves about 1e-7 of its neighbour's amplitude in it, which is under the threshold only while the neighbour is
+    quiet -- the kernel therefore decides all-zero frames before the transform.
+    Without the rule numpy's angle() of a zero depends on the SIGNS of its zero
     components (angle(-0.0 + 0j) = pi), an artefact no definition of the feature intends, and the phase of rounding
     residue would be compared.  The kernel (csrc/spatial.hip) implements the same rule."""
     spec = stft_f64(pcm)                                            # [C, 481, F]

@@ -39,6 +39,17 @@ __device__ __forceinline__ float lane_below(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
 }
 
+// The verdict of the all-zero rule (logmel_core.h kLiveA) for this lane's half-wavefront: a frame of the packed pair is
+// live if any of the half's 32 lanes holds a non-zero sample of it -- two ballots, the half picked by a mask.  Returns
+// whether any of the wavefront's four frames is dead: wavefront-uniform, the branch to the phase_c_zero_* block.
+__device__ __forceinline__ bool pair_live(unsigned bits, int lane, bool& live_a, bool& live_b) {
+  const unsigned long long ma = __ballot((bits & kLiveA) != 0), mb = __ballot((bits & kLiveB) != 0);
+  const unsigned long long half = 0xffffffffull << (lane & 32);
+  live_a = (ma & half) != 0;
+  live_b = (mb & half) != 0;
+  return static_cast<unsigned>(ma) == 0 || (ma >> 32) == 0 || static_cast<unsigned>(mb) == 0 || (mb >> 32) == 0;
+}
+
 #define SELD_WAVE_SYNC()                                   \
   do {                                                     \
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); \
@@ -59,6 +70,8 @@ __device__ __forceinline__ void edge_iteration(const LogmelArgs& a, long e, int 
 
   float s[48];
   load_samples<T, false>(lane, pcm + row * a.L, a.L, tf + 2 * h, s);
+  bool live_a, live_b;
+  const bool any_dead = pair_live(lane_live_bits(s), lane, live_a, live_b);
   phase_a(lane, s, consts, lds);
   SELD_WAVE_SYNC();
   cf z[kN2];
@@ -72,15 +85,18 @@ __device__ __forceinline__ void edge_iteration(const LogmelArgs& a, long e, int 
     const long fa = tf + 2 * h;
     float* base = a.spec + (row * a.F + fa) * (2 * kBins);
     phase_c_spectrum(lane, z, m, fa < a.F ? base : nullptr, fa + 1 < a.F ? base + 2 * kBins : nullptr);
+    if (any_dead) phase_c_zero_spectrum(lane, fa < a.F ? base : nullptr, fa + 1 < a.F ? base + 2 * kBins : nullptr, live_a, live_b);
   }
   if (kSpec == 2) {
     const long fa = tf + 2 * h;
     unsigned* base = reinterpret_cast<unsigned*>(a.spec) + (row * a.F + tf) * kPhasorPitch;
-    phase_c_store_phasors(lane, pp, z, m, base, static_cast<unsigned>(2 * h * kPhasorPitch + (lane & 31)), fa < a.F,
-                          fa + 1 < a.F);
+    const unsigned off_a = static_cast<unsigned>(2 * h * kPhasorPitch + (lane & 31));
+    phase_c_store_phasors(lane, pp, z, m, base, off_a, fa < a.F, fa + 1 < a.F);
+    if (any_dead) phase_c_zero_phasors(lane, base, off_a, fa < a.F, fa + 1 < a.F, live_a, live_b);
   } else {
     phase_c_store(lane, pp, z, m);
   }
+  if (any_dead) phase_c_zero_rows(lane, pp, live_a, live_b);
   SELD_WAVE_SYNC();
   LaneAcc acc;
   phase_d_accumulate(lane, lds, tab, seg, acc);
@@ -162,6 +178,8 @@ __global__ __launch_bounds__(kMainWaves * 64, 2) void logmel_main_kernel(LogmelA
       }
     }
     float* outp = out_lane + (clip * a.sN + chan * a.sC + itr * kFramesPerIter * a.sT);
+    bool live_a, live_b;
+    const bool any_dead = pair_live(lane_live_bits(s), lane, live_a, live_b);
     phase_a(lane, s, consts, lds);
     SELD_WAVE_SYNC();
     cf z[kN2];
@@ -178,13 +196,17 @@ __global__ __launch_bounds__(kMainWaves * 64, 2) void logmel_main_kernel(LogmelA
     if (kSpec == 1) {                                        // interior iterations: all four frames exist
       float* base = a.spec + ((row * a.F + itr * kFramesPerIter) * kBins) * 2 + h * (2 * 2 * kBins);
       phase_c_spectrum(lane, z, m, base, base + 2 * kBins);
+      if (any_dead) phase_c_zero_spectrum(lane, base, base + 2 * kBins, live_a, live_b);
     }
     if (kSpec == 2) {
       unsigned* base = reinterpret_cast<unsigned*>(a.spec) + (row * a.F + itr * kFramesPerIter) * kPhasorPitch;   // scalar
       phase_c_store_phasors(lane, pp, z, m, base, static_cast<unsigned>(2 * h * kPhasorPitch + (lane & 31)), true, true);
+      if (any_dead)
+        phase_c_zero_phasors(lane, base, static_cast<unsigned>(2 * h * kPhasorPitch + (lane & 31)), true, true, live_a, live_b);
     } else {
       phase_c_store(lane, pp, z, m);
     }
+    if (any_dead) phase_c_zero_rows(lane, pp, live_a, live_b);
     if (kLatePrefetch) load_samples<T, true>(lane, pcm + nrow * a.L, a.L, nitr * kFramesPerIter + 2 * h, s);
     SELD_WAVE_SYNC();
     LaneAcc acc;
@@ -260,6 +282,8 @@ __global__ __launch_bounds__(kEdgeWaves * 64, 2) void stft_kernel(LogmelArgs a) 
     float s[48];
     if (interior) load_samples<T, true>(lane, pcm + row * a.L, a.L, tf + 2 * h, s);
     else load_samples<T, false>(lane, pcm + row * a.L, a.L, tf + 2 * h, s);
+    bool live_a, live_b;
+    const bool any_dead = pair_live(lane_live_bits(s), lane, live_a, live_b);
     phase_a(lane, s, consts, lds);
     SELD_WAVE_SYNC();
     cf z[kN2];
@@ -272,6 +296,7 @@ __global__ __launch_bounds__(kEdgeWaves * 64, 2) void stft_kernel(LogmelArgs a) 
     const long fa = tf + 2 * h;
     float* base = a.out + (row * a.F + fa) * (2 * kBins);
     phase_c_spectrum(lane, z, m, fa < a.F ? base : nullptr, fa + 1 < a.F ? base + 2 * kBins : nullptr);
+    if (any_dead) phase_c_zero_spectrum(lane, fa < a.F ? base : nullptr, fa + 1 < a.F ? base + 2 * kBins : nullptr, live_a, live_b);
     SELD_WAVE_SYNC();
   }
 }
@@ -328,6 +353,8 @@ __global__ __launch_bounds__(kIvChannels * 64, 1) void logmel_iv_kernel(LogmelAr
       if (++nitr == a.iters_per_row) { nitr = 0; ++nclip; }
     }
     const long tf = itr * kFramesPerIter;
+    bool live_a, live_b;
+    const bool any_dead = pair_live(lane_live_bits(s), lane, live_a, live_b);
     phase_a(lane, s, consts, lds);
     SELD_WAVE_SYNC();
     cf z[kN2];
@@ -340,6 +367,7 @@ __global__ __launch_bounds__(kIvChannels * 64, 1) void logmel_iv_kernel(LogmelAr
     phase_c_load(lane, lds, m);
     cf xa[16], xb[16];
     phase_c_unpack(lane, pp, z, m, xa, xb);
+    if (any_dead) phase_c_zero_unpacked(lane, pp, xa, xb, live_a, live_b);
     if (wave == 0) iv_publish(lane, wspec, xa, xb);
     __syncthreads();
     float ia[16], ib[16];

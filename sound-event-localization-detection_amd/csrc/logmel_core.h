@@ -190,6 +190,32 @@ SELD_HD void stage_a_finish(int lane, const cf (&z)[kN1], const cf (&tw)[10], fl
 // the index as one expression makes the compiler hoist a separate loop-invariant address register for
 // every distinct constant (dozens of VGPRs, which then spill).
 
+// ---- All-zero frames.  Un-mixing a packed pair leaves, in a frame whose 960 samples are all zero, the fp32 rounding
+// residue of its partner (about 1e-7 of the partner's amplitude): next to a loud frame that is above the absolute silence
+// rule (kSilencePower below), and the frame would get phasors of rounding noise.  Such a frame's spectrum is exactly 0, and
+// whether it is one is exact too: lane_live_bits says, per lane, whether any of its 32 samples of the real-part frame
+// (kLiveA) / of the imaginary-part frame (kLiveB) is non-zero; the OR over the 32 lanes of the half-wavefront (a ballot on
+// the GPU, pair_live in logmel.hip) is the frame's verdict, and after phase C has stored what it computed, the phase_c_zero_*
+// functions below overwrite a dead frame's outputs with zeros -- power rows, phasor words, exported spectrum, the FOA
+// pass's spectra.  They run under a wavefront-uniform branch that is not taken unless the iteration holds a dead frame:
+// phase C itself is untouched (selects on its results, 32 - 96 per iteration, were measurably slower: DESIGN.md 7.5), and a
+// live frame's values pass through no arithmetic of this rule.  The bits are taken from the samples as loaded, before
+// phase A needs registers (inside phase A they cost scratch): three running ORs over the bit patterns (the middle 16
+// samples belong to both frames).
+constexpr unsigned kLiveA = 1u, kLiveB = 2u;
+
+SELD_HD unsigned lane_live_bits(const float (&s)[48]) {
+  unsigned lo = 0, mid = 0, hi = 0;
+#pragma unroll
+  for (int m = 0; m < 16; ++m) {
+    lo |= __builtin_bit_cast(unsigned, s[m]);
+    mid |= __builtin_bit_cast(unsigned, s[m + 16]);
+    hi |= __builtin_bit_cast(unsigned, s[m + 32]);
+  }
+  // (the shift drops the sign bit: -0.0 is a zero sample)
+  return (((lo | mid) << 1) != 0 ? kLiveA : 0u) | (((mid | hi) << 1) != 0 ? kLiveB : 0u);
+}
+
 // ---- Phase A: window, pack two frames, 32-pt DFT, twiddle, LDS column store.
 SELD_HD void phase_a(int lane, const float (&s)[48], const LaneConsts& k, float* lds) {
   cf z[kN1];
@@ -321,6 +347,46 @@ SELD_HD void phase_c_spectrum(int lane, const cf (&z)[kN2], const cf (&m)[16], f
   }
 }
 
+// ---- All-zero frames (see lane_live_bits): zeros over what phase C stored for a dead frame of this lane's pair.
+SELD_HD void phase_c_zero_rows(int lane, float* const (&pp)[16], bool live_a, bool live_b) {
+  const int l = lane & 31;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    if (r < 15 || l == 0) {
+      if (!live_a) pp[r][0] = 0.0f;
+      if (!live_b) pp[r][kPPitch] = 0.0f;
+    }
+  }
+}
+
+// arguments as phase_c_store_phasors: word 0 in every bin of a dead frame's row
+SELD_HD void phase_c_zero_phasors(int lane, unsigned* base, unsigned off_a, bool have_a, bool have_b, bool live_a, bool live_b) {
+  const int l = lane & 31;
+  unsigned* pa = have_a && !live_a ? base + off_a : nullptr;
+  unsigned* pb = have_b && !live_b ? base + off_a + kPhasorPitch : nullptr;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    if (r < 15 || l == 0) {
+      if (pa) pa[32 * r] = 0u;
+      if (pb) pb[32 * r] = 0u;
+    }
+  }
+}
+
+// arguments as phase_c_spectrum: 0 + 0j in every bin of a dead frame's row
+SELD_HD void phase_c_zero_spectrum(int lane, float* row_a, float* row_b, bool live_a, bool live_b) {
+  const int l = lane & 31;
+  cf* pa = row_a && !live_a ? reinterpret_cast<cf*>(row_a) + l : nullptr;
+  cf* pb = row_b && !live_b ? reinterpret_cast<cf*>(row_b) + l : nullptr;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    if (r < 15 || l == 0) {
+      if (pa) pa[32 * r] = cf_make(0.0f, 0.0f);
+      if (pb) pb[32 * r] = cf_make(0.0f, 0.0f);
+    }
+  }
+}
+
 // ---- Fused FOA intensity vectors (logmel_iv_kernel, logmel.hip): the four wavefronts of a workgroup are the channels
 // W, X, Y, Z of the SAME four frames, in lock-step.  Every wavefront leaves its |C|^2 rows in its own tile (all four use one
 // mel_pos layout, so a lane finds the other channels' powers of ITS bins at its own offsets, one tile pitch apart), W also
@@ -348,6 +414,16 @@ SELD_HD void phase_c_unpack(int lane, float* const (&pp)[16], const cf (&z)[kN2]
       pp[r][kPPitch] = p.y;
     }
   }
+}
+
+// a dead frame's un-packed spectrum (what iv_publish / iv_compute read) and power row: zeros
+SELD_HD void phase_c_zero_unpacked(int lane, float* const (&pp)[16], cf (&xa)[16], cf (&xb)[16], bool live_a, bool live_b) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    if (!live_a) xa[r] = cf_make(0.0f, 0.0f);
+    if (!live_b) xb[r] = cf_make(0.0f, 0.0f);
+  }
+  phase_c_zero_rows(lane, pp, live_a, live_b);
 }
 
 // W's wavefront: spectrum of (r, frame) at complex index (2 r + frame) * 64 + lane -- linear 8-byte stores / loads

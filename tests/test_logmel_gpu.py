@@ -87,6 +87,12 @@ def test_tones_and_silence_against_float64(gpu_device):
     silent = np.all(pcm.numpy() == 0.0, axis=0)                   # frames fully inside the silent quarter
     t_sil = [t for t in range(got.shape[2]) if silent[max(0, 480 * (t - 1)):480 * (t + 1)].all()]
     assert len(t_sil) > 5 and (got[:, :, t_sil] == -100.0).all()
+    # an all-zero frame is decided before the transform: its spectrum is exactly 0 + 0j, also in the two
+    # frames at the ends of the stretch that share a packed transform with a sounding frame
+    import seld_native
+    spec = seld_native.stft(pcm.to(gpu_device)).cpu().numpy()              # [4, F, 481]
+    assert not np.abs(spec[:, t_sil]).any()
+    assert np.abs(spec[:, t_sil[0] - 1]).max() > 1.0 and np.abs(spec[:, t_sil[-1] + 1]).max() > 1.0
 
 
 def test_full_size_properties_60s_clip(gpu_device):

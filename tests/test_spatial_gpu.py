@@ -110,6 +110,14 @@ def test_gcc_phat_with_a_silent_channel(gpu_device, kernel, monkeypatch):
     pulse = np.zeros(64)
     pulse[32] = 1.0
     assert np.abs(got[dead] - pulse[None, :, None]).max() <= 2e-5         # (frames with a silent bin take the exact route)
+    # frame 11 (samples 4800..5759) is all-zero in every channel: decided before the transform, so exactly -100 dB in every
+    # band, and every pair is the unit pulse (a frame that shares its packed transform with a sounding one: DESIGN.md 7.5)
+    zero = [t for t in range(feat.shape[0]) if not pcm[:, max(0, 480 * (t - 1)):480 * (t + 1)].any()]
+    assert zero == [11]
+    assert (feat[11, :4] == -100.0).all()
+    assert np.abs(got[:, :, 11] - pulse[None, :]).max() <= 2e-5
+    assert not seld_native.stft(pcm.to(gpu_device))[:, 11].cpu().abs().numpy().any()        # its spectrum: exactly 0 + 0j
+    assert not seld_native.stft(pcm.to(gpu_device))[2].cpu().abs().numpy().any()            # and the dead microphone's
 
 
 def test_gcc_phat_full_size_clip_and_kernel_variants(gpu_device, monkeypatch):
