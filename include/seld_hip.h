@@ -360,10 +360,12 @@ int seld_scale_by_device_scalar(void* data, int is_bf16, int64_t n, const float*
  * grad[k]: bf16 when grad_is_bf16[k] (the gradient of a bf16 working weight: no separate cast), else fp32; param / exp_avg /
  * exp_avg_sq fp32; low_bf16[k]: the bf16 working copy rewritten from the new master, or NULL.  All tensors of an entry
  * share one memory layout (the kernel walks the storage).  lr and step are DEVICE scalars (step = the count of THIS
- * update, i.e. already incremented).  HOST arrays of device addresses / lengths, passed to the kernel by value. */
+ * update, i.e. already incremented, a whole number).  beta1 / beta2 are doubles: 1 - beta and 1 - beta^step are formed in
+ * double and rounded to fp32 once, as the framework does.  HOST arrays of device addresses / lengths, passed to the kernel
+ * by value. */
 int seld_multi_adam(const void* const* grad, const int32_t* grad_is_bf16, float* const* param, float* const* exp_avg,
                     float* const* exp_avg_sq, void* const* low_bf16, const int64_t* lengths, int count, const float* lr,
-                    const float* step, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                    const float* step, double beta1, double beta2, float eps, float weight_decay, float grad_scale,
                     void* stream);
 
 /* ---- guarded update: global gradient-norm clipping, non-finite step skip, weight EMA (csrc/guard.hip, csrc/adam.hip) ----
@@ -399,7 +401,7 @@ int seld_multi_grad_norm(const void* const* grad, const int32_t* grad_is_bf16, c
  * caller advances `step` only for applied updates (e.g. step += 1 before the call, step -= guard->skipped after it). */
 int seld_multi_adam_guarded(const void* const* grad, const int32_t* grad_is_bf16, float* const* param,
                             float* const* exp_avg, float* const* exp_avg_sq, void* const* low_bf16, const int64_t* lengths,
-                            int count, const float* lr, const float* step, float beta1, float beta2, float eps,
+                            int count, const float* lr, const float* step, double beta1, double beta2, float eps,
                             float weight_decay, float grad_scale, float* const* ema, float ema_decay,
                             const seld_guard_record* guard, void* stream);
 

@@ -8,11 +8,15 @@
 // (the seld_multi_cast pattern: gradient tensors that autograd re-allocates every iteration need no descriptor upload).
 // Pure HBM-bound elementwise work.
 //
-// Arithmetic = the framework's fused kernel (ATen fused_adam_utils.cuh, ADAM_MODE::ORIGINAL, amsgrad off, maximize off),
-// in fp32:   g += weight_decay * p;   m = m + (1 - beta1) (g - m);   v = beta2 v + (1 - beta2) g g;
+// Arithmetic: the formulas of the framework's fused kernel (ATen fused_adam_utils.cuh, ADAM_MODE::ORIGINAL, amsgrad off,
+// maximize off), in fp32:   g += weight_decay * p;   m = m + (1 - beta1) (g - m);   v = beta2 v + (1 - beta2) g g;
 //            p -= (lr / (1 - beta1^step)) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
 // with lr and step read from DEVICE scalars (graph replay: a ReduceLROnPlateau change needs no re-capture; the caller
-// increments step before the launch).
+// increments step before the launch).  As there, the betas arrive as DOUBLES: 1 - beta and 1 - beta^step are formed in
+// double and rounded once (1 - 0.999f is 1.3e-5 off 0.001, and that error went straight into v and into the step size
+// while everything was float).  The element chain is fp32 with this file's own contractions, so the result agrees with
+// the framework's to rounding, not bit for bit: tests/test_adam_edges_gpu.py holds the update's relative error against
+// float64 Adam to twice the framework kernel's own.
 //
 // multi_adam_guarded_kernel is the same body with three additions (seld_multi_adam_guarded): it reads
 // the guard record of csrc/guard.hip and returns before its first store when the step is skipped, multiplies the gradient
@@ -45,8 +49,22 @@ struct AdamBatch {
 struct AdamScalars {
   const float* lr;
   const float* step;
-  float beta1, beta2, eps, weight_decay, grad_scale;
+  double beta1, beta2;
+  float eps, weight_decay, grad_scale;
 };
+
+// beta^step in double for the optimiser's whole-number step count (< 2^24: exact in the fp32 scalar), by squaring: at most
+// 48 multiplications, wave-uniform.
+__device__ __forceinline__ double adam_beta_power(double beta, float step) {
+  unsigned n = static_cast<unsigned>(step);
+  double r = 1.0;
+  while (n) {
+    if (n & 1u) r *= beta;
+    beta *= beta;
+    n >>= 1;
+  }
+  return r;
+}
 
 __device__ __forceinline__ unsigned adam_pack_bf16x2(float lo, float hi) {
   return static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(lo))) |
@@ -79,8 +97,11 @@ __device__ __forceinline__ void multi_adam_body(const AdamBatch& b, const AdamSc
   unsigned short* low = reinterpret_cast<unsigned short*>(b.low[t]);
   float* ema = kGuarded ? reinterpret_cast<float*>(x->ema[t]) : nullptr;
   const float lr = *s.lr, step = *s.step;
-  const float bc1 = 1.0f - __powf(s.beta1, step), bc2 = 1.0f - __powf(s.beta2, step);
+  const float bc1 = static_cast<float>(1.0 - adam_beta_power(s.beta1, step));
+  const float bc2 = static_cast<float>(1.0 - adam_beta_power(s.beta2, step));
   const float step_size = lr / bc1, bc2_sqrt = sqrtf(bc2);
+  const float beta2 = static_cast<float>(s.beta2);
+  const float rest1 = static_cast<float>(1.0 - s.beta1), rest2 = static_cast<float>(1.0 - s.beta2);
   const bool aligned = ((b.grad[t] | b.param[t] | b.m[t] | b.v[t] | b.low[t] | (kGuarded ? x->ema[t] : 0ull)) & 15ull) == 0;
 #pragma unroll
   for (int k = 0; k < kAdamPerThread / 8; ++k) {
@@ -127,8 +148,8 @@ __device__ __forceinline__ void multi_adam_body(const AdamBatch& b, const AdamSc
       float gj = g[j] * s.grad_scale;
       if (kGuarded) gj *= coef;
       gj = fmaf(s.weight_decay, pp[j], gj);
-      mm[j] = fmaf(1.0f - s.beta1, gj - mm[j], mm[j]);
-      vv[j] = fmaf(s.beta2, vv[j], (1.0f - s.beta2) * gj * gj);
+      mm[j] = fmaf(rest1, gj - mm[j], mm[j]);
+      vv[j] = fmaf(beta2, vv[j], rest2 * gj * gj);
       const float denom = sqrtf(vv[j]) / bc2_sqrt + s.eps;
       pp[j] -= step_size * mm[j] / denom;
       if (kGuarded && ema) ee[j] = fmaf(x->ema_rate, pp[j] - ee[j], ee[j]);
@@ -182,7 +203,7 @@ extern "C" {
 
 int seld_multi_adam(const void* const* grad, const int32_t* grad_is_bf16, float* const* param, float* const* exp_avg,
                     float* const* exp_avg_sq, void* const* low_bf16, const int64_t* lengths, int count, const float* lr,
-                    const float* step, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                    const float* step, double beta1, double beta2, float eps, float weight_decay, float grad_scale,
                     void* stream_) {
   using namespace seld;
   if (!current_state()) return kErrNotInitialised;
@@ -220,7 +241,7 @@ int seld_multi_adam(const void* const* grad, const int32_t* grad_is_bf16, float*
 
 int seld_multi_adam_guarded(const void* const* grad, const int32_t* grad_is_bf16, float* const* param,
                             float* const* exp_avg, float* const* exp_avg_sq, void* const* low_bf16, const int64_t* lengths,
-                            int count, const float* lr, const float* step, float beta1, float beta2, float eps,
+                            int count, const float* lr, const float* step, double beta1, double beta2, float eps,
                             float weight_decay, float grad_scale, float* const* ema, float ema_decay,
                             const seld_guard_record* guard, void* stream_) {
   using namespace seld;

@@ -23,6 +23,15 @@ enabled = True
 # copies gradients as autograd delivers them) they are queued and ``flush_batch`` runs ONE multi-tensor launch of each kind
 # (csrc/glue.hip).  The queued outputs are handed to autograd as fresh aliases: autograd clones a gradient tensor that
 # is referenced elsewhere -- here, before it has been filled.
+# A queued gradient holds NOTHING until the flush, which runs after the backward pass has ended: it may be queued only
+# when no node reads it on its way to a parameter's ``.grad``.  ``_Linear.forward`` decides that for its weight and its
+# bias (``unread_until_leaf``): a leaf parameter, or one reached through nodes that hand a contiguous gradient on as a
+# view (view / squeeze / unsqueeze, seld_pack's join), with ``.grad`` absent as GraphedTrainStep leaves it.  Any other
+# weight -- ``weight * 1.0``, ``weight[:, perm]``, a permuted copy -- has a backward node that reads the gradient as soon
+# as it is returned, and its reductions are launched at once.  The column permutation of
+# ``linear_on_channels_last_features`` happens INSIDE ``_Linear`` for that reason (``columns_cf``): the leaf itself is the
+# input, and the chunk sum writes the gradient's columns back in the leaf's order (launched at once: the mapped reduction
+# has no place in the batched launch; it replaces the permuted copy autograd made of the gradient).
 _batch = None
 
 
@@ -50,6 +59,31 @@ def flush_batch(close=True):
 def abandon_batch():
     global _batch
     _batch = None
+
+
+_VIEW_NODES = ("ViewBackward", "UnsafeViewBackward", "SqueezeBackward", "UnsqueezeBackward")
+
+
+def unread_until_leaf(t):
+    """True when a contiguous gradient returned for ``t`` reaches the ``.grad`` of leaves without being read: ``t`` is a
+    leaf, or every node between it and the leaves turns its gradient into views (the framework's view / squeeze /
+    unsqueeze nodes; a custom Function that says so with ``gradient_passes_as_views``)."""
+    todo = [t.grad_fn]
+    while todo:
+        fn = todo.pop()
+        if fn is None or type(fn).__name__ == "AccumulateGrad":
+            continue
+        if not (type(fn).__name__.startswith(_VIEW_NODES)
+                or getattr(getattr(fn, "_forward_cls", None), "gradient_passes_as_views", False)):
+            return False
+        todo += [nxt for nxt, _ in fn.next_functions]
+    return True
+
+
+def columns_kernel_applies(columns_cf):
+    """csrc/glue.hip sum_chunks_columns_kernel: 2 to 4 frequencies, channels in groups of 8."""
+    c, f = columns_cf
+    return 2 <= f <= 4 and c % 8 == 0
 
 
 def tall_product(a, c, out_dtype=torch.float32, out=None, queue=False, columns_cf=None):
@@ -86,7 +120,9 @@ def tall_product(a, c, out_dtype=torch.float32, out=None, queue=False, columns_c
             and out.dtype in (torch.float32, torch.bfloat16):
         if columns_cf is not None:
             import seld_native
-            return seld_native.sum_chunks(partial, out, columns_cf=columns_cf)
+            if columns_kernel_applies(columns_cf):
+                return seld_native.sum_chunks(partial, out, columns_cf=columns_cf)
+            return permuted(seld_native.sum_chunks(partial, torch.empty_like(out)), out)      # same bits, two launches
         if queue and _batch is not None:
             _batch["sums"].append((partial, out))            # filled by flush_batch (``queue``: the caller allows it)
             return out
@@ -133,11 +169,21 @@ def column_sum(g2, out, queue=False):
 
 class _Linear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, overlap=False):
+    def forward(ctx, x, weight, bias, overlap=False, columns_cf=None):
+        """``columns_cf = (C, F)``: x's features are ordered (frequency, channel) -- f * C + c -- while weight's columns
+        are (channel, frequency): the columns are permuted here, and the weight gradient's are written back in the
+        weight's own order by the reduction that produces it."""
         ctx.overlap = overlap
+        ctx.columns_cf = columns_cf
+        # may backward hand out a gradient that only flush_batch fills?  (the note on _batch above)
+        ctx.queue_w = columns_cf is None and unread_until_leaf(weight)
+        ctx.queue_b = bias is not None and unread_until_leaf(bias)
         cdt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else x.dtype
         with torch.autocast(device_type="cuda", enabled=False):
             xc, wc = x.to(cdt), weight.to(cdt)
+            if columns_cf is not None:
+                c, f = columns_cf
+                wc = wc.reshape(wc.shape[0], c, f).transpose(1, 2).reshape(wc.shape[0], f * c)
             y = F.linear(xc, wc, None if bias is None else bias.to(cdt))
         ctx.save_for_backward(xc, wc)
         ctx.has_bias = bias is not None
@@ -166,21 +212,22 @@ class _Linear(torch.autograd.Function):
 
                 def job():
                     if dw is not None:
-                        tall_product(g2, x2, out=dw)
+                        tall_product(g2, x2, out=dw, columns_cf=ctx.columns_cf)
                     if db is not None:
                         column_sum(g2, db)
 
                 seld_overlap.submit(grad.device, [t for t in (g2, x2, dw, db) if t is not None], job)
             else:
-                dw = tall_product(g2, x2, out_dtype=ctx.w_dtype, queue=True) if want_w else None
-                db = column_sum(g2, torch.empty((g2.shape[1],), dtype=ctx.b_dtype, device=grad.device), queue=True) \
-                    if want_b else None
+                dw = tall_product(g2, x2, out_dtype=ctx.w_dtype, queue=ctx.queue_w, columns_cf=ctx.columns_cf) \
+                    if want_w else None
+                db = column_sum(g2, torch.empty((g2.shape[1],), dtype=ctx.b_dtype, device=grad.device),
+                                queue=ctx.queue_b) if want_b else None
                 if _batch is not None:                      # possibly queued: fresh aliases for autograd (see above)
                     dw = dw.view_as(dw) if dw is not None else None
                     db = db.view_as(db) if db is not None else None
         if dx is not None and dx.dtype != ctx.in_dtype:
             dx = dx.to(ctx.in_dtype)
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
 class SeldLinear(nn.Linear):
@@ -206,8 +253,7 @@ def linear_on_channels_last_features(linear, y):
     if linear.in_features != c * f:
         return None
     feats = y.permute(0, 2, 3, 1).reshape(b, t, f * c)                       # a view: (f, c) order
-    w = linear.weight.view(linear.out_features, c, f).transpose(1, 2).reshape(linear.out_features, f * c)
-    return _Linear.apply(feats, w, linear.bias)
+    return _Linear.apply(feats, linear.weight, linear.bias, False, (c, f))       # the leaf goes in: the columns move inside
 
 
 conv1x1_as_gemm = True        # Config.CONV1X1_AS_GEMM via trainer.prepare_model_for_device

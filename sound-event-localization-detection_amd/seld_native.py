@@ -120,10 +120,11 @@ def _declare(lib):
     lib.seld_column_sums.argtypes = [_ptr, _int, _i64, _i64, _ptr, _ptr, _int, _ptr]
     _pp, _pi64, _pi32 = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
     _f = ctypes.c_float
-    lib.seld_multi_adam.argtypes = [_pp, _pi32, _pp, _pp, _pp, _pp, _pi64, _int, _ptr, _ptr, _f, _f, _f, _f, _f, _ptr]
+    _d = ctypes.c_double          # the betas: 1 - beta and 1 - beta^step are formed in double (csrc/adam.hip)
+    lib.seld_multi_adam.argtypes = [_pp, _pi32, _pp, _pp, _pp, _pp, _pi64, _int, _ptr, _ptr, _d, _d, _f, _f, _f, _ptr]
     lib.seld_multi_grad_norm_scratch.argtypes = [_pi64, _int, _pi64]
     lib.seld_multi_grad_norm.argtypes = [_pp, _pi32, _pi64, _int, _f, _f, _int, _ptr, _i64, _ptr, _ptr]
-    lib.seld_multi_adam_guarded.argtypes = [_pp, _pi32, _pp, _pp, _pp, _pp, _pi64, _int, _ptr, _ptr, _f, _f, _f, _f, _f, _pp, _f,
+    lib.seld_multi_adam_guarded.argtypes = [_pp, _pi32, _pp, _pp, _pp, _pp, _pi64, _int, _ptr, _ptr, _d, _d, _f, _f, _f, _pp, _f,
                                             _ptr, _ptr]
     lib.seld_multi_sum_chunks.argtypes = [_pp, _pp, _pi64, _pi32, _pi32, _int, _ptr]
     lib.seld_multi_column_sums_scratch.argtypes = [_pi64, _pi64, _int, _pi64]
@@ -1064,13 +1065,15 @@ def multi_adam(grads, params, exp_avgs, exp_avg_sqs, lows, lr: torch.Tensor, ste
     the new values; ``lr`` / ``step`` are fp32 device scalars (``step`` already incremented).  Returns False -- having done
     nothing -- when a tensor does not qualify (layout / dtype), so that the caller can take the framework's path.
     ``cache``: dict of a caller that passes the same lists every iteration (descriptor arrays reused while no address
-    changed)."""
+    changed; the key covers every cached address: grad, param, exp_avg, exp_avg_sq, low -- ``load_state_dict`` replaces
+    the moment tensors while the gradients of the exchange path stay where they are)."""
     n = len(params)
     if n == 0:
         return True
     key = None
     if cache is not None:
         key = tuple(t.data_ptr() for t in grads) + tuple(t.data_ptr() for t in params) + \
+            tuple(t.data_ptr() for t in exp_avgs) + tuple(t.data_ptr() for t in exp_avg_sqs) + \
             tuple(0 if t is None else t.data_ptr() for t in lows)
         if cache.get("key") == key:
             args = cache["args"]

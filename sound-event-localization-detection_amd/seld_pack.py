@@ -11,6 +11,8 @@ import torch
 class _Joined(torch.autograd.Function):
     """torch.cat(tensors, 0) for parameters that are ADJACENT slices of one buffer: the concatenation is a view."""
 
+    gradient_passes_as_views = True          # backward only splits: seld_linear may queue a gradient behind this node
+
     @staticmethod
     def forward(ctx, *tensors):
         a = tensors[0]

@@ -532,7 +532,7 @@ class MasterWeightAdam(torch.optim.Adam):
     def _own_step(self):
         """The whole update as ONE multi-tensor launch per 48 tensors (csrc/adam.hip): the bf16 gradients are read as they
         are and the bf16 working copies written from the new masters in the same pass -- 28 B per parameter instead of the
-        40 B of cast + fused Adam + cast.  Same arithmetic as the framework's fused Adam; the state keeps its format
+        40 B of cast + fused Adam + cast.  The framework's fused Adam formulas (agreement to rounding); the state keeps its format
         (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``), so ``state_dict`` is unchanged.  Returns False when the
         call does not qualify (then the three-launch path below runs)."""
         import seld_native
