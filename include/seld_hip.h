@@ -316,6 +316,38 @@ int seld_window_gather_mix_standardised(const float* src, int64_t total_rows, in
 int seld_window_mix_mask(const uint16_t* src, int64_t total_rows, int I, int J, const int64_t* starts, const int32_t* params,
                          const int64_t* partners, int64_t B, int64_t window, uint16_t* dst, void* stream);
 
+/* ---- windows of microphone-array features under a channel swap (csrc/micswap.hip) ---------- */
+/* seld_window_gather_augment(_affine) for the feature sets of a microphone array whose geometry is known.  A spatial pattern
+ * that maps the array onto itself permutes the microphones: the transformed scene's channel j is the recording's channel
+ * sigma_p(j).  mic_perm: HOST pointer, int8 [SELD_AUGMENT_PATTERNS][mics], row p = sigma_p, or all -1 when pattern p is no
+ * symmetry of the array (a window with such a pattern is written with the identity transform).  Row 0 is the identity.
+ * src float32 [total_rows][channels][64] -> dst float32 [B][window][channels][64], per output channel, sigma = sigma_p:
+ *   log-mel c < mics:  the stored channel sigma(c), copied.
+ *   SELD_MIC_GCC  (channels = mics + mics (mics - 1) / 2; pairs lexicographic, lags -32..31 at indices 0..63, as seld_gcc_phat):
+ *     pair (a, b), a < b, with u = sigma(a), v = sigma(b):  u < v: the stored pair (u, v), copied;  u > v: the stored pair
+ *     (v, u) with the lags reversed, out[j] = in[64 - j] for j = 1..63 and out[0] = in[0] (lag +32 is not stored: the -32
+ *     slot of a reversed pair keeps the stored -32 value, the one element that is not the transformed field's).
+ *   SELD_MIC_NIPD (channels = 2 mics - 1; channel mics + m - 1 = NIPD of microphone m = 1..mics-1 against microphone 0):
+ *     N(sigma(m)) - N(sigma(0)), one fp32 subtraction, N(0) = +0.0f, N(i) the stored NIPD of microphone i; a plain copy when
+ *     sigma(0) = 0.  Exact for phase differences that do not wrap, an approximation where they do.
+ * Then scale / shift (the _standardised export, the map of the _affine gathers above: fmaf(v, scale[c][f], shift[c][f]),
+ * both float32 [channels][64] on the device), then the masks of params[b] as seld_window_gather_augment; rows outside
+ * [0, total_rows) are +0.0.  The operations go to the kernel by value; it reduces the pattern modulo 16 and only compares
+ * the mask fields: no row can make it read or write out of bounds.  No allocation, no synchronisation (graph-capture
+ * safe); a window's output depends on (source, starts[b], params[b]) only.  Refused, in this order and before anything is
+ * written: mics outside 2..8, an unknown kind, freq_channels outside 0..channels (-1, with the other extents); a mic_perm
+ * row that is neither a permutation nor all -1, a row 0 that is not the identity (-1); a window too large (-4); null
+ * pointers (-1). */
+#define SELD_MIC_GCC 0
+#define SELD_MIC_NIPD 1
+int seld_window_gather_mic(const float* src, int64_t total_rows, int mics, int kind, int freq_channels, const int64_t* starts,
+                           const int32_t* params, int64_t B, int64_t window, const int8_t* mic_perm, float mask_value,
+                           float* dst, void* stream);
+int seld_window_gather_mic_standardised(const float* src, int64_t total_rows, int mics, int kind, int freq_channels,
+                                  const int64_t* starts, const int32_t* params, int64_t B, int64_t window,
+                                  const int8_t* mic_perm, float mask_value, const float* scale, const float* shift,
+                                  float* dst, void* stream);
+
 /* ---- loss: loss.py:43-54 class_mse_loss (+ its backward) ---------------------------------- */
 /* logits [n_cells][14] (fp32, or bf16 when logits_is_bf16), labels as EITHER the compact mask
  * (uint16 [n_cells]) OR dense float32 [n_cells][14] (exactly one non-NULL).  Writes

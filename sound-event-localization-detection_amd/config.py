@@ -184,6 +184,12 @@ class Config:
                                 # 'logmel_iv' only; not together with AUGMENT_ROTATE
     AUGMENT_MIX_GAIN_DB = 6.0   # the partner's level relative to the window: uniform in +- this many dB
     FOA_CHANNEL_ORDER = "WYZX"  # which input channel is which: 'WYZX' (STARSS / DCASE FOA recordings) or 'WXYZ'
+    MIC_POSITIONS = None        # microphone-array recordings: the microphone positions, which define the array's channel swaps
+                                # (seld_augment.py, csrc/micswap.hip).  None = unknown (FOA rules: an
+                                # array gets masks only), the preset "tetra_starss" (the STARSS22 tetrahedron, 4.2 cm), or C
+                                # rows of (x, y, z) in metres, x towards azimuth 0, y towards azimuth +90, z up.  With them
+                                # AUGMENT_SPATIAL and SELD_TTA_PATTERNS work on 'logmel', 'logmel_gcc' and 'logmel_nipd' over
+                                # the patterns that map the array onto itself ("all" = those); saved in the checkpoint
     # Per-bin feature standardisation inside the device window gathers (seld_standardise.py, csrc/standardise.hip; DESIGN.md
     # section 22).  Off by default: every entry point, checkpoint and benchmark figure is then what it was
     STANDARDISE_FEATURES = False  # train_model reduces mean / std of every (channel, mel bin or lag) over the TRAINING timeline

@@ -438,6 +438,8 @@ class SELDDataset(Dataset):
         self.use_gaussian_augmentation = bool(config.GAUSSIAN_AUGMENT)
         self.with_rotation = bool(getattr(config, "AUGMENT_ROTATE", False))   # as of construction: decides whether rot_tm exists
         self.rot_tm = None
+        # Config.MIC_POSITIONS as of construction: float64 [C, 3], or None (no array: the FOA rules of the augmenting gathers)
+        self.mic_array = seld_augment.mic_positions(getattr(config, "MIC_POSITIONS", None))
         self._feature_statistics = None          # statistics of THIS timeline (feature_statistics), computed once
         self.feature_stats = None                # the statistics device_batch applies (set_feature_statistics), or None
         self._feature_scale = self._feature_shift = None
@@ -517,7 +519,11 @@ class SELDDataset(Dataset):
         ``mix``: None, or the windows' partners (``seld_augment.draw_mix``: partner window index or -1, the partner's spatial
         pattern, its linear power gain): the batch is produced by the mixing pair (csrc/mix.hip) --
         powers added on the stored features, labels united; a window without a partner is the augmenting pair's, bit for
-        bit.  Needs ``augment`` rows (identity rows will do); not available on a dataset that holds rotation terms."""
+        bit.  Needs ``augment`` rows (identity rows will do); not available on a dataset that holds rotation terms.
+        On a dataset constructed with Config.MIC_POSITIONS (``mic_array``) the augmenting pair is the
+        array's: 'logmel_gcc' / 'logmel_nipd' features go through the array gather (csrc/micswap.hip), 'logmel' through
+        the augmenting gather with the array's channel table, labels through the same cell permutation.  A host row that
+        names a pattern which is no symmetry of the array is refused before anything is launched; no ``mix``."""
         if self.spec_tm is None:
             raise RuntimeError("device_batch needs keep_on_device=True")
         if mix is not None:
@@ -537,6 +543,12 @@ class SELDDataset(Dataset):
         if augment is not None:
             table, freq_channels, mask_value = self._augment_tables()
             starts = starts.to(self.device, non_blocking=True)
+            if getattr(self, "mic_array", None) is not None:
+                if mix is None:
+                    return self._mic_batch(starts, w, augment, bufs, scale, shift)
+                # mixing on an array is defined without a swap only (check_settings refuses AUGMENT_MIX_PROB together with
+                # AUGMENT_SPATIAL): every pattern 0, and the mixing pair below is then what it is without positions
+                self._check_mix_on_array(augment, mix)
             if getattr(self, "rot_tm", None) is not None:
                 params = seld_native.augment_params(augment, len(starts), w, self.device, steps=self.J)
                 spec = seld_native.gather_windows_rotate(self.spec_tm, self.rot_tm, starts, w, params, table,
@@ -574,6 +586,54 @@ class SELDDataset(Dataset):
         else:
             spec = seld_native.gather_windows(self.spec_tm, starts, w, out=bufs[0] if bufs else None)
         mask = seld_native.gather_windows(self.mask_tm, starts, w, out=bufs[1] if bufs else None)
+        return spec, mask
+
+    def _check_mix_on_array(self, augment, mix):
+        """``device_batch(augment=..., mix=...)`` on a dataset that knows its microphone array: host rows and partner patterns
+        must all be the identity (a device-resident parameter table is trusted, as everywhere)."""
+        if not (isinstance(augment, torch.Tensor) and augment.is_cuda):
+            rows = np.asarray(torch.as_tensor(augment))
+            if rows.ndim == 2 and rows.shape[1] >= 1 and rows[:, 0].any():
+                raise ValueError("device_batch: mixing on a microphone array (this dataset was constructed with MIC_POSITIONS) "
+                                 "is defined without a channel swap only: every window's spatial pattern must be 0")
+        if len(mix) == 3 and np.asarray(mix[1]).any():
+            raise ValueError("device_batch: mixing on a microphone array (this dataset was constructed with MIC_POSITIONS) is "
+                             "defined without a channel swap only: every partner's spatial pattern must be 0")
+
+    def _mic_batch(self, starts, w, augment, bufs, scale, shift):
+        """``device_batch`` with ``augment`` rows and no ``mix`` on a dataset that knows its microphone array (DESIGN.md
+        section 25)."""
+        if getattr(self, "rot_tm", None) is not None:
+            raise ValueError("device_batch: no rotation is defined for a microphone array (this dataset was constructed with "
+                             "MIC_POSITIONS)")
+        feature_set = getattr(config, "FEATURE_SET", "logmel")
+        key = (feature_set, self.n_channels)
+        if getattr(self, "_mic_key", None) != key:
+            seld_augment.check_settings(config, feature_set, self.n_channels, array=self.mic_array)
+            self._mic_perm = seld_augment.mic_permutations(self.mic_array)
+            self._mic_table = seld_augment.mic_channel_table(self.mic_array)
+            self._mic_freq_channels = seld_augment.freq_mask_channels(feature_set, self.n_channels)
+            self._mic_key = key
+        if not (isinstance(augment, torch.Tensor) and augment.is_cuda):     # (a device table is trusted: no synchronise; the
+            patterns = np.asarray(torch.as_tensor(augment))[:, 0]           #  kernel writes its bad rows untransformed)
+            known = (patterns >= 0) & (patterns < seld_augment.PATTERNS)
+            bad = sorted({int(p) for p in patterns[known] if self._mic_perm[int(p), 0] < 0})
+            if bad:
+                valid = [int(p) for p in np.flatnonzero(self._mic_perm[:, 0] >= 0)]
+                raise ValueError(f"device_batch: spatial patterns {bad} are no symmetries of this microphone array (valid: "
+                                 f"{valid}): the features would stay put while the labels move")
+        params = seld_native.augment_params(augment, len(starts), w, self.device)
+        mask_value = float(getattr(config, "AUGMENT_MASK_VALUE", 0.0))
+        if feature_set == "logmel":
+            spec = seld_native.gather_windows_augment(self.spec_tm, starts, w, params, self._mic_table,
+                                                      self._mic_freq_channels, mask_value, out=bufs[0] if bufs else None,
+                                                      scale=scale, shift=shift)
+        else:
+            spec = seld_native.gather_windows_mic(self.spec_tm, starts, w, params, self._mic_perm, feature_set,
+                                                  self._mic_freq_channels, mask_value, out=bufs[0] if bufs else None,
+                                                  scale=scale, shift=shift)
+        mask = seld_native.gather_windows_permute(self.mask_tm, starts, w, params, self.I, self.J,
+                                                  out=bufs[1] if bufs else None)
         return spec, mask
 
     def _augment_tables(self):

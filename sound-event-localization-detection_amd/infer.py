@@ -90,7 +90,10 @@ def main(argv=None):
     nipd = {k: float(own[k]) for k in trainer.NIPD_SETTINGS if k in own}
     if nipd:
         logging.getLogger(__name__).info("NIPD settings of the checkpoint: " + ", ".join(f"{k} = {v:g}" for k, v in nipd.items()))
-    patterns = seld_augment.tta_patterns(getattr(trainer.config, "SELD_TTA_PATTERNS", ()) if args.tta is None else args.tta)
+    # a microphone array's geometry (Config.MIC_POSITIONS) travels in the checkpoint like the NIPD settings
+    array = seld_augment.mic_positions(own.get("MIC_POSITIONS", getattr(trainer.config, "MIC_POSITIONS", None)))
+    patterns = seld_augment.tta_patterns(getattr(trainer.config, "SELD_TTA_PATTERNS", ()) if args.tta is None else args.tta,
+                                         array=array)
     track = {"gate_deg": args.track_gate_deg, "max_gap": args.track_max_gap, "min_len": args.track_min_len} \
         if args.track else False
     per_class = None
@@ -106,6 +109,9 @@ def main(argv=None):
         saved_nipd = {k: getattr(dataset.config, k) for k in nipd}
         for k, v in nipd.items():
             setattr(dataset.config, k, v)
+        own_array = "MIC_POSITIONS" in vars(dataset.config)      # (restored below without leaving an instance attribute)
+        saved_array = vars(dataset.config).get("MIC_POSITIONS")
+        dataset.config.MIC_POSITIONS = array
         try:
             ds = dataset.SELDDataset.from_pcm([pcm], [np.zeros((0, 5), dtype=np.int64)], sample_rate=rate, device=device,
                                               use_gaussian_augmentation=False)
@@ -113,7 +119,11 @@ def main(argv=None):
             dataset.config.RESAMPLE_INPUT = saved
             for k, v in saved_nipd.items():
                 setattr(dataset.config, k, v)
-        seld_augment.check_tta(patterns, getattr(trainer.config, "FEATURE_SET", "logmel"), ds.n_channels)
+            if own_array:
+                dataset.config.MIC_POSITIONS = saved_array
+            else:
+                del dataset.config.MIC_POSITIONS
+        seld_augment.check_tta(patterns, getattr(trainer.config, "FEATURE_SET", "logmel"), ds.n_channels, array=array)
         # a checkpoint trained on standardised features carries their statistics: the recording's gathers apply them
         # (Config.STANDARDISE_FEATURES on and none in the checkpoint: an error, as in evaluate_seld)
         trainer.apply_checkpoint_statistics(checkpoint, ds)

@@ -18,6 +18,10 @@ Parameter row of one window (int32 x 12, ``include/seld_hip.h``):
 Rotation in azimuth steps (``csrc/rotate.hip``): on the I x J grid a rotation about the vertical axis by
 a multiple of one cell (10 degrees) is still an exact cyclic shift of the label cells.  A window's transform is then
 mirror m, s = (k J/4 + r) mod J cells of azimuth (phi = 2 pi s / J), elevation flip e: 2 x J x 2 = 144 transforms.
+
+Microphone arrays (``csrc/micswap.hip``): with the microphone positions known (``Config.MIC_POSITIONS``),
+every pattern that maps the array onto itself is an exact permutation of the recording's channels -- ``mic_permutations``
+-- and the label-cell permutation above applies unchanged.  ``draw`` then picks among the array's valid patterns only.
 """
 from __future__ import annotations
 
@@ -32,6 +36,12 @@ NEGATE = 0x80                     # channel-table flag: the output channel is MI
 
 STEP = 9                          # parameter-row slot of the azimuth step r
 MAX_STEPS = 72                    # SELD_ROTATE_MAX_STEPS
+
+MIC_MIN, MIC_MAX = 2, 8          # microphones the array gather takes (csrc/micswap.hip)
+MIC_MATCH_TOLERANCE = 1e-3        # a moved microphone matches a position within this share of the largest |r_j|
+MIC_FEATURE_SETS = ("logmel", "logmel_gcc", "logmel_nipd")      # the feature sets with a defined swap on an array
+# (azimuth, elevation) in degrees and radius in metres of the preset arrays
+MIC_PRESETS = {"tetra_starss": (((45.0, 35.0), (-45.0, -35.0), (135.0, -35.0), (-135.0, 35.0)), 0.042)}
 
 SWITCHES = ("AUGMENT_SPATIAL", "AUGMENT_TIME_MASKS", "AUGMENT_FREQ_MASKS", "AUGMENT_ROTATE", "AUGMENT_MIX_PROB")
 
@@ -160,6 +170,112 @@ def cell_source_rot(m: int, s: int, e: int, I: int = 18, J: int = 36) -> np.ndar
     return src
 
 
+# ------------------------------------------------------------------------------------------ microphone arrays
+
+def mic_positions(spec):
+    """Microphone positions as float64 [C, 3] (x, y, z in metres, the DOA frame of the labels: x towards azimuth 0 /
+    elevation 0, y towards azimuth +90 degrees, z up) from a Config.MIC_POSITIONS value: None stays None (no array: FOA
+    rules), the preset name 'tetra_starss' (the STARSS22 tetrahedron), or C rows of (x, y, z)."""
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        if spec not in MIC_PRESETS:
+            raise ValueError(f"MIC_POSITIONS: unknown preset {spec!r}; the presets are {sorted(MIC_PRESETS)}")
+        angles, radius = MIC_PRESETS[spec]
+        az, el = np.radians(np.asarray(angles, dtype=np.float64)).T
+        return radius * np.stack([np.cos(az) * np.cos(el), np.sin(az) * np.cos(el), np.sin(el)], axis=1)
+    try:
+        pos = np.array(spec, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("MIC_POSITIONS must be None, a preset name or rows of (x, y, z) in metres") from None
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError(f"MIC_POSITIONS must be rows of (x, y, z) in metres, got shape {pos.shape}")
+    if pos.shape[0] < 2:
+        raise ValueError(f"MIC_POSITIONS: an array has at least 2 microphones, got {pos.shape[0]}")
+    if not np.isfinite(pos).all():
+        raise ValueError("MIC_POSITIONS: positions must be finite")
+    scale = float(np.sqrt((pos * pos).sum(axis=1)).max())
+    gaps = np.sqrt(((pos[:, None, :] - pos[None, :, :]) ** 2).sum(axis=2)) + np.eye(len(pos)) * (scale + 1.0)
+    if gaps.min() <= MIC_MATCH_TOLERANCE * scale:
+        raise ValueError("MIC_POSITIONS: two microphones share a position")
+    return pos
+
+
+def pattern_matrix(p: int) -> np.ndarray:
+    """float64 [3, 3]: T_p, the orthogonal map of pattern p on a direction (x, y, z): mirror y -> -y, then k quarter turns
+    (x, y) -> (-y, x), then flip z -> -z."""
+    m, k, e = decode(p)
+    mirror = np.diag([1.0, -1.0 if m else 1.0, 1.0])
+    turn = np.linalg.matrix_power(np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]]), k)
+    flip = np.diag([1.0, 1.0, -1.0 if e else 1.0])
+    return flip @ turn @ mirror
+
+
+def mic_permutations(positions) -> np.ndarray:
+    """int8 [16, C]: row p = sigma_p with r[sigma_p(j)] = T_p^-1 r[j] when pattern p maps the array onto itself (every point
+    matched exactly once, within MIC_MATCH_TOLERANCE of the largest |r_j|), else all -1.  The transformed scene's channel j
+    is the recording's channel sigma_p(j)."""
+    pos = mic_positions(positions)
+    if pos is None:
+        raise ValueError("mic_permutations: no microphone positions")
+    n = len(pos)
+    tolerance = MIC_MATCH_TOLERANCE * float(np.sqrt((pos * pos).sum(axis=1)).max())
+    table = np.full((PATTERNS, n), -1, dtype=np.int8)
+    for p in range(PATTERNS):
+        moved = pos @ pattern_matrix(p)                             # rows T_p^T r_j = T_p^-1 r_j
+        gaps = np.sqrt(((moved[:, None, :] - pos[None, :, :]) ** 2).sum(axis=2))
+        sigma = gaps.argmin(axis=1)
+        if (gaps[np.arange(n), sigma] <= tolerance).all() and len(set(sigma.tolist())) == n:
+            table[p] = sigma
+    return table
+
+
+def mic_valid_patterns(positions) -> tuple:
+    """The patterns that are symmetries of the array, ascending; 0 is always one."""
+    return tuple(int(p) for p in np.flatnonzero(mic_permutations(positions)[:, 0] >= 0))
+
+
+def mic_channel_table(positions) -> np.ndarray:
+    """uint8 [16, C] for 'logmel' on an array: the channel table of ``seld_window_gather_augment`` whose row p is sigma_p
+    (log-mel channels are copied, never negated); rows of patterns that are no symmetry are the identity."""
+    perm = mic_permutations(positions)
+    table = np.tile(np.arange(perm.shape[1], dtype=np.uint8), (PATTERNS, 1))
+    valid = perm[:, 0] >= 0
+    table[valid] = perm[valid].astype(np.uint8)
+    return table
+
+
+def mic_count(feature_set: str, n_channels: int) -> int:
+    """Microphones behind ``n_channels`` feature channels: C for 'logmel', C + C(C-1)/2 for 'logmel_gcc', 2C - 1 for
+    'logmel_nipd'; 0 when the count fits no array."""
+    n = int(n_channels)
+    if feature_set == "logmel":
+        return n
+    if feature_set == "logmel_gcc":
+        c = int(round((math.sqrt(8 * n + 1) - 1) / 2))
+        return c if c * (c + 1) // 2 == n else 0
+    if feature_set == "logmel_nipd":
+        return (n + 1) // 2 if n % 2 == 1 else 0
+    return 0
+
+
+def _array_of(cfg, array):
+    """The array an entry point works with: the one it was handed, else the Config's."""
+    return mic_positions(array if array is not None else getattr(cfg, "MIC_POSITIONS", None))
+
+
+def _check_array_features(array, feature_set, n_channels):
+    if feature_set not in MIC_FEATURE_SETS:
+        raise ValueError(
+            f"MIC_POSITIONS describes a microphone array: its channel swap is defined for FEATURE_SET 'logmel', "
+            f"'logmel_gcc' and 'logmel_nipd', not for {feature_set!r} (first-order-Ambisonics features have no microphone "
+            f"positions; leave MIC_POSITIONS at None for them)")
+    if n_channels is not None and mic_count(feature_set, int(n_channels)) != len(array):
+        raise ValueError(
+            f"MIC_POSITIONS holds {len(array)} microphones, FEATURE_SET={feature_set!r} with {n_channels} feature channels "
+            f"comes from {mic_count(feature_set, int(n_channels))}")
+
+
 # ------------------------------------------------------------------------------------------ configuration
 
 def settings(cfg):
@@ -183,9 +299,12 @@ def enabled(cfg) -> bool:
     return s["spatial"] or s["rotate"] or s["time_masks"] > 0 or s["freq_masks"] > 0 or s["mix_prob"] > 0
 
 
-def check_settings(cfg, feature_set: str | None = None, n_channels: int | None = None):
-    """Raise ValueError for switches outside their range or a spatial swap the feature set does not define."""
+def check_settings(cfg, feature_set: str | None = None, n_channels: int | None = None, array=None):
+    """Raise ValueError for switches outside their range or a spatial swap the feature set does not define.  ``array``:
+    microphone positions (``mic_positions``; None reads Config.MIC_POSITIONS) -- with them the spatial rules are those of
+    the array in place of the FOA ones."""
     s = settings(cfg)
+    array = _array_of(cfg, array)
     for key in ("time_masks", "freq_masks"):
         if not 0 <= s[key] <= 2:
             raise ValueError(f"AUGMENT_{key.upper()} must be 0, 1 or 2, got {s[key]}")
@@ -194,12 +313,22 @@ def check_settings(cfg, feature_set: str | None = None, n_channels: int | None =
     if not np.isfinite(s["mask_value"]):
         raise ValueError("AUGMENT_MASK_VALUE must be finite")
     check_channel_order(s["order"])
-    if s["spatial"] and feature_set is not None and not spatial_supported(feature_set, int(n_channels)):
+    if array is not None:
+        if feature_set is not None:
+            _check_array_features(array, feature_set, n_channels)
+        if s["rotate"]:
+            raise ValueError("AUGMENT_ROTATE is not defined for a microphone array (MIC_POSITIONS is set): no array is "
+                             "symmetric under 10-degree steps; AUGMENT_SPATIAL draws among the array's own symmetries")
+        if s["mix_prob"] > 0 and s["spatial"]:
+            raise ValueError("AUGMENT_MIX_PROB cannot be combined with AUGMENT_SPATIAL on a microphone array (MIC_POSITIONS is "
+                             "set): the partner's pattern is drawn over all 16, not over the array's symmetries")
+    foa_rules = array is None and feature_set is not None           # an array has its own rules, above
+    if s["spatial"] and foa_rules and not spatial_supported(feature_set, int(n_channels)):
         raise ValueError(
             f"AUGMENT_SPATIAL is defined for 4-channel FOA features ('logmel' with 4 channels, 'logmel_iv'), not for "
             f"FEATURE_SET={feature_set!r} with {n_channels} feature channels: a microphone array's geometry is unknown here, "
             f"so no channel swap is defined (time / frequency masks work for every feature set)")
-    if s["rotate"] and feature_set is not None and not spatial_supported(feature_set, int(n_channels)):
+    if s["rotate"] and foa_rules and not spatial_supported(feature_set, int(n_channels)):
         raise ValueError(
             f"AUGMENT_ROTATE is defined for 4-channel FOA features ('logmel' with 4 channels, 'logmel_iv'), not for "
             f"FEATURE_SET={feature_set!r} with {n_channels} feature channels: a microphone array's geometry is unknown here, "
@@ -226,10 +355,11 @@ def identity_rows(n: int) -> np.ndarray:
 
 # ------------------------------------------------------------------------------------------ test-time augmentation
 
-def tta_patterns(spec) -> tuple:
+def tta_patterns(spec, array=None) -> tuple:
     """The pattern list of test-time augmentation from a Config value or a command-line string:
     None, (), 0, False and "" give () (off); "all" the 16 patterns; an iterable of ints or a comma-separated string is
-    checked (each in 0..15, no duplicates) and its order kept."""
+    checked (each in 0..15, no duplicates) and its order kept.  ``array``: microphone positions (``mic_positions``) --
+    "all" is then the array's valid patterns (``check_tta`` refuses listed ones that are not)."""
     if spec is None or spec is False or (isinstance(spec, (int, np.integer)) and not isinstance(spec, bool) and spec == 0):
         return ()
     if spec is True:
@@ -237,7 +367,7 @@ def tta_patterns(spec) -> tuple:
     if isinstance(spec, str):
         text = spec.strip()
         if text.lower() == "all":
-            return tuple(range(PATTERNS))
+            return tuple(range(PATTERNS)) if array is None else mic_valid_patterns(array)
         if text == "":
             return ()
         try:
@@ -265,8 +395,19 @@ def tta_rows(p: int, n: int) -> np.ndarray:
     return rows
 
 
-def check_tta(patterns, feature_set: str, n_channels: int):
-    """Raise ValueError when a non-empty pattern list meets a feature set without a defined channel swap."""
+def check_tta(patterns, feature_set: str, n_channels: int, array=None):
+    """Raise ValueError when a non-empty pattern list meets a feature set without a defined channel swap.  ``array``:
+    microphone positions (``mic_positions``) -- the feature set must then be one of the array's and every pattern one of
+    its symmetries."""
+    array = mic_positions(array)
+    if patterns and array is not None:
+        _check_array_features(array, feature_set, n_channels)
+        valid = mic_valid_patterns(array)
+        wrong = [int(p) for p in patterns if int(p) not in valid]
+        if wrong:
+            raise ValueError(f"test-time augmentation patterns {wrong} are no symmetries of this microphone array; its valid "
+                             f"patterns are {list(valid)}")
+        return
     if patterns and not spatial_supported(feature_set, int(n_channels)):
         raise ValueError(
             f"test-time augmentation over the spatial patterns is defined for 4-channel FOA features ('logmel' with 4 "
@@ -275,7 +416,7 @@ def check_tta(patterns, feature_set: str, n_channels: int):
 
 
 def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, bins: int = N_BINS,
-         steps: int | None = None) -> np.ndarray:
+         steps: int | None = None, array=None) -> np.ndarray:
     """int32 [B, 12] parameter rows for the windows ``window_indices`` (dataset window indices) of ``epoch``.
 
     A window's row is a function of (seed, epoch, window index) and the switches ONLY -- not of the rank, the batch size
@@ -285,8 +426,14 @@ def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, 
 
     With AUGMENT_ROTATE the spatial part is drawn over the 4 J transforms instead: mirror and elevation flip uniform, no
     quarter turns in the pattern (m << 3 | e), the azimuth step [9] uniform in 0..steps-1 (``steps``: the grid's J, default
-    360 // GRID_CELL_DEGREES).  With it off the generator is asked exactly what it was asked before the switch existed."""
-    s = check_settings(cfg)
+    360 // GRID_CELL_DEGREES).  With it off the generator is asked exactly what it was asked before the switch existed.
+
+    With Config.MIC_POSITIONS (a microphone array) AUGMENT_SPATIAL draws uniformly among the array's
+    valid patterns, ``valid[rng.integers(0, len(valid))]``; with it None the generator is asked exactly what it was asked
+    before arrays existed.  ``array``: the positions to draw for in place of the Config's (a feed hands over its dataset's)."""
+    s = check_settings(cfg, array=array)
+    array = _array_of(cfg, array)
+    valid = mic_valid_patterns(array) if array is not None and s["spatial"] else None
     if steps is None:
         steps = int(360 // getattr(cfg, "GRID_CELL_DEGREES", 10))
     if window is None:
@@ -300,6 +447,8 @@ def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, 
         if s["rotate"]:
             rows[r, 0] = (int(rng.integers(0, 2)) << 3) | int(rng.integers(0, 2))
             rows[r, STEP] = rng.integers(0, int(steps))
+        elif valid is not None:
+            rows[r, 0] = valid[int(rng.integers(0, len(valid)))]
         elif s["spatial"]:
             rows[r, 0] = rng.integers(0, PATTERNS)
         for first, count, longest, axis in ((1, s["time_masks"], s["time_max"], int(window)),

@@ -97,6 +97,10 @@ def _declare(lib):
     lib.seld_window_gather_mix_standardised.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _ptr, _i64, _i64, _ptr, ctypes.c_float,
                                                   _int, _ptr, _ptr, _ptr, _ptr]
     lib.seld_window_mix_mask.argtypes = [_ptr, _i64, _int, _int, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr]
+    lib.seld_window_gather_mic.argtypes = [_ptr, _i64, _int, _int, _int, _ptr, _ptr, _i64, _i64, _ptr, ctypes.c_float, _ptr,
+                                           _ptr]
+    lib.seld_window_gather_mic_standardised.argtypes = [_ptr, _i64, _int, _int, _int, _ptr, _ptr, _i64, _i64, _ptr, ctypes.c_float,
+                                                  _ptr, _ptr, _ptr, _ptr]
     lib.seld_softmax_mse_workspace_bytes.restype = _i64
     lib.seld_softmax_mse_workspace_bytes.argtypes = []
     lib.seld_softmax_mse.argtypes = [_ptr, _int, _ptr, _ptr, _i64, _int, ctypes.c_float, _ptr, _ptr, _ptr, _ptr]
@@ -672,6 +676,44 @@ def gather_windows_permute(src: torch.Tensor, starts: torch.Tensor, window: int,
     with _device_guard(index):
         check(load_library().seld_window_permute_mask(_p(src), src.shape[0], I, J, _p(starts), _p(params), starts.numel(),
                                                       window, _p(out), _stream_ptr(src.device)), "seld_window_permute_mask")
+    return out
+
+
+MIC_KINDS = {"logmel_gcc": 0, "logmel_nipd": 1}        # SELD_MIC_GCC, SELD_MIC_NIPD
+
+
+def gather_windows_mic(src: torch.Tensor, starts: torch.Tensor, window: int, params: torch.Tensor, mic_perm, kind: str,
+                       freq_channels: int | None = None, mask_value: float = 0.0, out: torch.Tensor | None = None,
+                       scale: torch.Tensor | None = None, shift: torch.Tensor | None = None) -> torch.Tensor:
+    """``gather_windows_augment`` for the features of a microphone array under its channel swaps (csrc/micswap.hip, DESIGN.md
+    section 25): src [T, channels, 64] of ``kind`` 'logmel_gcc' (C + C(C-1)/2 channels) or 'logmel_nipd' (2C - 1);
+    ``mic_perm``: int8 [16, C] host array (``seld_augment.mic_permutations``), row p the microphone permutation of pattern
+    p or all -1 (no symmetry of the array: such a window is gathered untransformed).  Log-mel channels are copied, a
+    GCC-PHAT pair that comes out of order has its lag axis reversed, an NIPD channel whose reference moved is the difference
+    of two stored ones.  ``scale`` / ``shift`` and the masks as ``gather_windows_augment``."""
+    import numpy as np
+    src, index, starts, out = _window_call("gather_windows_mic", src, torch.float32, (None, N_MELS),
+                                           "a float32 GPU tensor [T, C, 64]", starts, window, params, out)
+    if kind not in MIC_KINDS:
+        raise ValueError(f"gather_windows_mic: kind must be one of {sorted(MIC_KINDS)}, got {kind!r}")
+    perm = np.ascontiguousarray(mic_perm, dtype=np.int8)
+    if perm.ndim != 2 or perm.shape[0] != AUGMENT_PATTERNS:
+        raise ValueError("gather_windows_mic: mic_perm must be int8 [16, microphones]")
+    mics, channels = int(perm.shape[1]), int(src.shape[1])
+    expected = mics + mics * (mics - 1) // 2 if kind == "logmel_gcc" else 2 * mics - 1
+    if channels != expected:        # the library takes the channel count from (mics, kind): the source must have that many
+        raise ValueError(f"gather_windows_mic: {kind!r} of {mics} microphones has {expected} feature channels, src has "
+                         f"{channels}")
+    freq_channels = channels if freq_channels is None else int(freq_channels)
+    scale, shift = _affine_tables("gather_windows_mic", scale, shift, src)
+    head = (_p(src), src.shape[0], mics, MIC_KINDS[kind], freq_channels, _p(starts), _p(params), starts.numel(), window,
+            ctypes.c_void_p(perm.ctypes.data), float(mask_value))
+    with _device_guard(index):
+        if scale is not None:
+            check(load_library().seld_window_gather_mic_standardised(*head, _p(scale), _p(shift), _p(out),
+                                                               _stream_ptr(src.device)), "seld_window_gather_mic_standardised")
+        else:
+            check(load_library().seld_window_gather_mic(*head, _p(out), _stream_ptr(src.device)), "seld_window_gather_mic")
     return out
 
 

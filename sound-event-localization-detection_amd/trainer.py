@@ -313,8 +313,16 @@ class DeviceFeed:
         self.shuffle = isinstance(loader.sampler, RandomSampler)
         self.device, self.rank, self.world, self.seed = device, rank, world, seed
         # a spatial swap the feature set does not define is refused when the feed is built, not at the first batch
+        # the array is the DATASET's (Config.MIC_POSITIONS as of its construction: what its gathers work with)
+        self.array = getattr(self.dataset, "mic_array", None)
         if seld_augment.enabled(config):
-            seld_augment.check_settings(config, getattr(config, "FEATURE_SET", "logmel"), self.dataset.n_channels)
+            # a Config that says otherwise by now would have the draw and the gathers disagree
+            now = seld_augment.mic_positions(getattr(config, "MIC_POSITIONS", None))
+            if (self.array is None) != (now is None) or (now is not None and not np.array_equal(self.array, now)):
+                raise ValueError("Config.MIC_POSITIONS differs from the positions this dataset was constructed with "
+                                 "(SELDDataset.mic_array): construct the dataset under the setting the training runs with")
+            seld_augment.check_settings(config, getattr(config, "FEATURE_SET", "logmel"), self.dataset.n_channels,
+                                        array=self.array)
             if seld_augment.settings(config)["rotate"] and getattr(self.dataset, "rot_tm", None) is None:
                 raise ValueError("AUGMENT_ROTATE needs a dataset constructed with the switch on and kept on the device: the "
                                  "rotating gather reads three extra mel rows per frame of the timeline (SELDDataset.rot_tm)")
@@ -338,8 +346,8 @@ class DeviceFeed:
         # AUGMENT_MIX_PROB: a partner per window from a stream of its own (seld_augment.draw_mix; csrc/mix.hip)
         mixing = augment and seld_augment.settings(config)["mix_prob"] > 0
         for idx in batched(self._order(epoch), self.batch_size, self.drop_last):
-            params = seld_augment.draw(self.seed, epoch, idx, config, window=self.dataset.window_length_frames) \
-                if augment else None
+            params = seld_augment.draw(self.seed, epoch, idx, config, window=self.dataset.window_length_frames,
+                                       array=self.array) if augment else None
             if not mixing:
                 yield self.dataset.device_batch(idx, out=out, augment=params)
                 continue
@@ -817,6 +825,9 @@ def checkpoint_payload(epoch, model, optimizer, train_loss, test_loss, feature_s
         # infer.py reads them from the file and not from whatever the class says on the day it runs
         for name in NIPD_SETTINGS:
             setattr(config, name, getattr(config, name))
+    if getattr(config, "MIC_POSITIONS", None) is not None:
+        # likewise the array's geometry: infer.py --tta swaps channels by the positions in the file
+        setattr(config, "MIC_POSITIONS", getattr(config, "MIC_POSITIONS"))
     payload = {"epoch": epoch, "model_state_dict": model_state_dict(model),
                "optimizer_state_dict": opt_state, "train_loss": train_loss, "test_loss": test_loss,
                "config": config}
@@ -1146,7 +1157,7 @@ def timeline_logits(model, dataset, batch_size, device, patterns=None):
     of the usual size, into one buffer that is reused from batch to batch -- a yielded tensor is valid until the next
     one is asked for.  Needs the device timeline (no CPU fallback)."""
     on_device = device.type == "cuda" and getattr(dataset, "spec_tm", None) is not None
-    patterns = seld_augment.tta_patterns(patterns)
+    patterns = seld_augment.tta_patterns(patterns, array=getattr(dataset, "mic_array", None))
     if not patterns:
         return _plain_logits(model, dataset, batch_size, device, on_device)
     if not on_device:
@@ -1210,8 +1221,11 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
     import seld_eval
     seld_eval.segment_setting(segment, jackknife)          # (jackknife without segment: raise before the checkpoint is read)
     test_dataset = test_loader.dataset
-    patterns = seld_augment.tta_patterns(getattr(config, "SELD_TTA_PATTERNS", ()) if tta is None else tta)
-    seld_augment.check_tta(patterns, getattr(config, "FEATURE_SET", "logmel"), getattr(test_dataset, "n_channels", 0))
+    # a dataset of a microphone array (Config.MIC_POSITIONS): "all" = the array's symmetries
+    array = getattr(test_dataset, "mic_array", None)
+    patterns = seld_augment.tta_patterns(getattr(config, "SELD_TTA_PATTERNS", ()) if tta is None else tta, array=array)
+    seld_augment.check_tta(patterns, getattr(config, "FEATURE_SET", "logmel"), getattr(test_dataset, "n_channels", 0),
+                           array=array)
     batch_size = batch_size or getattr(test_loader, "batch_size", None) or config.BATCH_SIZE
     model_path = Path(model_path or (config.CHECKPOINT_PATH / "best_model.pth"))
     device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
