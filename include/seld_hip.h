@@ -644,7 +644,7 @@ int seld_dwconv1d_wgrad(const void* x, const void* dy, int is_bf16, int64_t B, i
 
 /* ---- recurrence: nn.GRU(2048, 256, num_layers=2, bidirectional) at model_crnn.py:65-72 ------- */
 /* One bidirectional GRU layer's recurrence, all T steps in one launch (both directions), H = 256.
- * The batch is processed in tiles of S = seld_gru_tile_rows() sequences (4 in this build; tiles = ceil(B / S)):
+ * The batch is processed in tiles of S = seld_gru_tile_rows() sequences (2 in this build; tiles = ceil(B / S)):
  * one workgroup per (tile, direction); the other columns of each 16-column MFMA are padding so that the
  * per-CU vector-memory and gate-math work of a step -- what bounds it once the weights are resident -- is
  * spread over more CUs.

@@ -16,16 +16,18 @@
 //     conflict-free B-fragment reads, see kHPitch), one barrier per step;
 //   * v_mfma_f32_16x16x32_bf16: per step 48 MFMAs per wavefront, fp32 accumulate, fp32 gates.
 //
-// WHY ONLY kSeqs = 4 SEQUENCES PER 16-COLUMN MFMA TILE.  With the weights resident, a step is bound by what ONE CU
+// WHY ONLY kSeqs = 2 SEQUENCES PER 16-COLUMN MFMA TILE.  With the weights resident, a step is bound by what ONE CU
 // can do besides the MFMAs: its vector-memory path sustains only ~10-15 B/clk (MI355X_MICROARCH.md: "~10
 // B/cyc/CU", stores issue-bound), and the gate math (6 transcendentals per element) issues on the same 4 SIMDs.
 // Both scale with sequences per CU while the MFMA time (96 per SIMD, ~1.5k cycles) does not -- so the batch is
 // spread over MORE CUs: the other columns of every MFMA are padding (they repeat a valid column), and after the
-// MFMAs the 16 / kSeqs lanes that share a sequence split the column's 2 x 4 accumulators among themselves with one
-// DPP row shift per value.  Every lane then owns ONE (sequence, kU units) group: a fraction of the gate
-// instructions and of the bytes per CU per step, all 64 lanes active in every load and store.  Measured
-// (B = 32, T = 250, us per step forward / backward): 16 sequences 1.68 / 3.33, 8 sequences 1.28 / 1.57,
-// 4 sequences 1.18 / 1.40.
+// MFMAs the 16 / kSeqs lanes that share a sequence split the column's 2 x 4 accumulators among themselves (one DPP
+// row shift per value; with 2 sequences a select among the lane's own registers, see own_values).  Every lane then
+// owns ONE (sequence, kU units) group: a fraction of the gate instructions and of the bytes per CU per step, all
+// 64 lanes active in every load and store.  Measured (B = 32, T = 250, us per step forward / backward): 16 sequences
+// 1.68 / 3.33, 8 sequences 1.28 / 1.57, 4 sequences 1.18 / 1.40; after the LDS pitch fix and the direct-layout
+// backward 4 sequences 1.14 / 1.24, 2 sequences 1.09 / 1.17.  2 is the last halving of
+// this scheme: a lane cannot own less than one unit.  SELD_GRU_SEQS = 4 and 8 still build.
 //
 // The backward kernel mirrors it: dgh (bf16) goes through LDS as the B operand, W_hh^T fragments
 // are register / LDS resident, dh is carried in registers; it emits the per-step gate gradients
@@ -36,7 +38,7 @@
 #include "seld_common.h"
 
 #ifndef SELD_GRU_SEQS
-#define SELD_GRU_SEQS 4
+#define SELD_GRU_SEQS 2
 #endif
 
 namespace seld {
@@ -51,13 +53,14 @@ constexpr int kGruThreads = 512;   // 8 wavefronts
 // Row pitches of the LDS tiles the MFMA B fragments are read from: 32 B more than a multiple of 256 B.  A ds_read_b128 is
 // served in four groups of 16 lanes that are NOT contiguous (MI355X_MICROARCH.md, LDS: {0-3, 12-15, 20-27}, ...): with 4
 // sequences per tile a group holds the rows of all 4 sequences at TWO neighbouring 16-B columns (q, q + 1), so the rows
-// must start 32 B apart modulo the 256-B bank row.  The pitches used until round 9 (528 / 1552 B: 16 B apart) made every
+// must start 32 B apart modulo the 256-B bank row (with 2 sequences: rows 0 and 1 at the two columns, the same four
+// 16-B segments 0 / 16 / 32 / 48 B).  The pitches used until round 9 (528 / 1552 B: 16 B apart) made every
 // fragment read a 2-way conflict; measured at B = 32, T = 250: backward 1.27 -> 1.21 us per step, forward 1.15 -> 1.14.
 constexpr int kHPitch = kH + 16;   // bf16 elements per h row in LDS (544 B)
 constexpr int kDghPitch = kG + 16; // bf16 elements per dgh row in LDS (1568 B)
 constexpr int kDghDirectPitch = kG + kH + 16;  // direct-layout backward: da_r | da_z | da_n r | da_n (2080 B)
 constexpr int kWnBytes = 8 * 2 * 8 * 64 * 16;   // [wave][tile][kstep][lane] x 16 B = 131072
-static_assert(kSeqs == 8 || kSeqs == 4, "8 or 4 sequences per tile");
+static_assert(kSeqs == 8 || kSeqs == 4 || kSeqs == 2, "8, 4 or 2 sequences per tile");
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -77,22 +80,36 @@ template <int kPart> __device__ __forceinline__ float shifted_part(float old, fl
   constexpr int banks = kSeqs == 8 ? 0xc : (1 << kPart);                            // banks = groups of 4 lanes
   return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), ctrl, 0xf, banks, false));
 }
-// v[s][i]: this column's accumulators; returns the kU values this lane owns
-__device__ __forceinline__ void own_values(const f32x4 (&v)[2], float (&out)[kU]) {
+//
+// kSeqs = 2 (8 parts of 2 lanes): bank_mask cannot address 2 lanes.  No lane needs another lane's registers, though: a
+// padding column c reads row c % kSeqs of the B tile, so its 8 accumulators ARE the valid column's, bit for bit, and
+// part p keeps flat index p of its own: a three-level select on the bits of p (4 + 2 + 1 v_cndmask_b32 against three
+// lane masks that live in SGPR pairs, compared once outside the step loop).
+// v[s][i]: this column's accumulators; returns the kU values this lane owns (part = (lane & 15) / kSeqs)
+__device__ __forceinline__ void own_values(const f32x4 (&v)[2], float (&out)[kU], int part) {
+  if constexpr (kParts == 8) {
+    const bool b0 = part & 1, b1 = part & 2, b2 = part & 4;
+    const float s0 = b0 ? v[0][1] : v[0][0], s1 = b0 ? v[0][3] : v[0][2];
+    const float s2 = b0 ? v[1][1] : v[1][0], s3 = b0 ? v[1][3] : v[1][2];
+    const float t0 = b1 ? s1 : s0, t1 = b1 ? s3 : s2;
+    out[0] = b2 ? t1 : t0;
+  } else {
 #pragma unroll
-  for (int j = 0; j < kU; ++j) {
-    float r = v[j >> 2][j & 3];                                                      // part 0: flat index j
-    if (kParts >= 2) r = shifted_part<1>(r, v[(kU + j) >> 2][(kU + j) & 3]);
-    if (kParts == 4) {
-      r = shifted_part<2>(r, v[(2 * kU + j) >> 2][(2 * kU + j) & 3]);
-      r = shifted_part<3>(r, v[(3 * kU + j) >> 2][(3 * kU + j) & 3]);
+    for (int j = 0; j < kU; ++j) {
+      float r = v[j >> 2][j & 3];                                                    // part 0: flat index j
+      r = shifted_part<1>(r, v[(kU + j) >> 2][(kU + j) & 3]);
+      if constexpr (kParts == 4) {
+        r = shifted_part<2>(r, v[(2 * kU + j) >> 2][(2 * kU + j) & 3]);
+        r = shifted_part<3>(r, v[(3 * kU + j) >> 2][(3 * kU + j) & 3]);
+      }
+      out[j] = r;
     }
-    out[j] = r;
   }
 }
 
 // ---- storage of a lane's kU-unit group ---------------------------------------------------------------------------
 template <int kBytes> struct Raw;
+template <> struct alignas(2) Raw<2> { unsigned short w[1]; };      // one 2-byte unit (kU = 1)
 template <> struct alignas(4) Raw<4> { unsigned w[1]; };
 template <> struct alignas(8) Raw<8> { unsigned w[2]; };
 template <> struct alignas(16) Raw<16> { unsigned w[4]; };
@@ -160,21 +177,52 @@ template <> struct Types<__hip_bfloat16> { typedef AsBF16 Data; typedef AsF16 Sa
 // (r|z, n|gh_n) and the gate gradients as 2 (da_r|da_z, da_n|da_n*r).
 template <typename C> using Group = Raw<C::kBytes * kU>;
 template <typename C> using PairOf = Raw<2 * C::kBytes * kU>;
+// A single 2-byte unit (kU = 1) is half a word: the group is the low half of the codec's pair {a, 0} (each element is
+// rounded on its own, so the bits are those of the wider groups), and a pair of groups is the codec's pair {a, b}.
+template <typename C> constexpr bool kHalfWord = C::kBytes * kU == 2;
 template <typename C> __device__ __forceinline__ Group<C> enc1(const float (&a)[kU]) {
   Group<C> g;
-  C::template enc<kU>(a, g.w);
+  if constexpr (kHalfWord<C>) {
+    const float two[2] = {a[0], 0.0f};
+    unsigned w;
+    C::template enc<2>(two, &w);
+    g.w[0] = static_cast<unsigned short>(w);
+  } else {
+    C::template enc<kU>(a, g.w);
+  }
   return g;
 }
-template <typename C> __device__ __forceinline__ void dec1(const Group<C>& g, float (&a)[kU]) { C::template dec<kU>(g.w, a); }
+template <typename C> __device__ __forceinline__ void dec1(const Group<C>& g, float (&a)[kU]) {
+  if constexpr (kHalfWord<C>) {
+    const unsigned w = g.w[0];
+    float two[2];
+    C::template dec<2>(&w, two);
+    a[0] = two[0];
+  } else {
+    C::template dec<kU>(g.w, a);
+  }
+}
 template <typename C> __device__ __forceinline__ PairOf<C> enc2(const float (&a)[kU], const float (&b)[kU]) {
   PairOf<C> p;
-  C::template enc<kU>(a, p.w);
-  C::template enc<kU>(b, p.w + C::kBytes * kU / 4);
+  if constexpr (kHalfWord<C>) {
+    const float two[2] = {a[0], b[0]};
+    C::template enc<2>(two, p.w);
+  } else {
+    C::template enc<kU>(a, p.w);
+    C::template enc<kU>(b, p.w + C::kBytes * kU / 4);
+  }
   return p;
 }
 template <typename C> __device__ __forceinline__ void dec2(const PairOf<C>& p, float (&a)[kU], float (&b)[kU]) {
-  C::template dec<kU>(p.w, a);
-  C::template dec<kU>(p.w + C::kBytes * kU / 4, b);
+  if constexpr (kHalfWord<C>) {
+    float two[2];
+    C::template dec<2>(p.w, two);
+    a[0] = two[0];
+    b[0] = two[1];
+  } else {
+    C::template dec<kU>(p.w, a);
+    C::template dec<kU>(p.w + C::kBytes * kU / 4, b);
+  }
 }
 
 // ---- private "tile" layout of every per-step tensor the kernels stream (gi, saved gates, dy, dg) --------
@@ -214,8 +262,9 @@ __device__ __forceinline__ void gru_forward_steps(const GruFwdArgs& a, bf16x8* w
   constexpr bool kLdsY = sizeof(T) == 2;   // bf16: y rows are written from the LDS h tile (512-B runs)
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
+  const int copy_wave = __builtin_amdgcn_readfirstlane(wave);   // in an SGPR: conditions on it are scalar branches
   const int q = lane >> 4, c = lane & 15;
-  const int seq = c % kSeqs;
+  const int seq = c % kSeqs, part = c / kSeqs;
   const int unit0 = lane_unit0(wave, lane);               // the kU units this lane post-processes
   const int dir = blockIdx.y;
   const long tile = blockIdx.x;
@@ -291,9 +340,9 @@ __device__ __forceinline__ void gru_forward_steps(const GruFwdArgs& a, bf16x8* w
       wn1 = wn1_n;
     }
     // ---- gates for this lane's (sequence, kU units)
-    own_values(acc_r, ghr);
-    own_values(acc_z, ghz);
-    own_values(acc_n, gg);
+    own_values(acc_r, ghr, part);
+    own_values(acc_z, ghz, part);
+    own_values(acc_n, gg, part);
 #pragma unroll
     for (int i = 0; i < kU; ++i) {
       gg[i] += bias_n[i];
@@ -315,12 +364,18 @@ __device__ __forceinline__ void gru_forward_steps(const GruFwdArgs& a, bf16x8* w
     __syncthreads();
     if (kLdsY) {
       // y[b][tt][dir*H .. +H) is a 512-B run: the 8 wavefronts write the kSeqs rows of the fresh h tile, one row
-      // (kSeqs = 8) or half a row (kSeqs = 4) each, as one contiguous run per wavefront
-      constexpr int kPer = 4 * kSeqs / 8;                    // bf16 elements per lane
-      const int row = wave * kSeqs / 8, col = (wave % (8 / kSeqs)) * (64 * kPer) + lane * kPer;
-      typedef Raw<2 * kPer> Piece;
-      const Piece v = *reinterpret_cast<const Piece*>(hbuf + (nxt * kSeqs + row) * kHPitch + col);
-      *reinterpret_cast<Piece*>(y + ((tile * kSeqs + row) * a.T + tt) * (2 * kH) + dir * kH + col) = v;
+      // (kSeqs = 8) or half a row (kSeqs = 4, 2) each, as one contiguous run per wavefront.  kSeqs = 2 has only four
+      // half rows: wavefronts 0-3 write them, 4 bytes per lane (eight wavefronts at 2 bytes per lane would issue twice
+      // the stores for the same bytes); the condition is wavefront-uniform, a scalar branch
+      constexpr int kPer = kSeqs == 8 ? 4 : 2;               // bf16 elements per lane
+      constexpr int kPerRow = kH / (64 * kPer);              // wavefronts per row
+      constexpr int kCopyWaves = kSeqs * kPerRow;
+      if (kCopyWaves >= 8 || copy_wave < kCopyWaves) {
+        const int row = wave / kPerRow, col = (wave % kPerRow) * (64 * kPer) + lane * kPer;
+        typedef Raw<2 * kPer> Piece;
+        const Piece v = *reinterpret_cast<const Piece*>(hbuf + (nxt * kSeqs + row) * kHPitch + col);
+        *reinterpret_cast<Piece*>(y + ((tile * kSeqs + row) * a.T + tt) * (2 * kH) + dir * kH + col) = v;
+      }
     }
   };
 
@@ -405,7 +460,7 @@ __device__ __forceinline__ void gru_backward_steps(const GruBwdArgs& a, bf16x8* 
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int q = lane >> 4, c = lane & 15;
-  const int seq = c % kSeqs;
+  const int seq = c % kSeqs, part = c / kSeqs;
   const int unit0 = lane_unit0(wave, lane);
   const int dir = blockIdx.y;
   const long tile = blockIdx.x;
@@ -425,7 +480,11 @@ __device__ __forceinline__ void gru_backward_steps(const GruBwdArgs& a, bf16x8* 
   // direct: the pieces of the dgh tile this lane copies out after the barrier.  Piece p (16 B) of tile row `row`:
   // p < 64 -> dgi r, z; 64..95 -> dghn; 96..127 -> dgi n.  A wavefront copies half a row: runs of 1 KB, or 512 B + 512 B.
   // A row past the batch copies row B-1 once more instead (the same bytes to the same place): no branch in the step.
-  constexpr int kPieces = kDirect ? kSeqs / 4 : 1;
+  // kSeqs = 2: the tile has only 256 pieces per step.  Wavefronts 4-7 copy the pieces of wavefronts 0-3 once more (the
+  // same bytes to the same place, like a row past the batch) instead of skipping the copy: a wavefront-uniform branch
+  // around the store cuts the MFMA loop into basic blocks, and measured at B = 32, T = 250 the kernel then took 322 us
+  // against 293 us without the branch (309 us with 4-sequence tiles).
+  constexpr int kPieces = kDirect && kSeqs > 4 ? kSeqs / 4 : 1;
   int out_lds[kPieces];
   T* out_ptr[kPieces];
   long out_step[kPieces];
@@ -433,7 +492,7 @@ __device__ __forceinline__ void gru_backward_steps(const GruBwdArgs& a, bf16x8* 
 #pragma unroll
     for (int k = 0; k < kPieces; ++k) {
       const int p = tid & 127;
-      long ob = tile * kSeqs + (tid >> 7) + 4 * k;
+      long ob = tile * kSeqs + ((tid >> 7) + 4 * k) % kSeqs;
       ob = ob < a.B ? ob : a.B - 1;
       out_lds[k] = static_cast<int>(ob - tile * kSeqs) * kPitch + 8 * p;
       // (b, t of the first step processed, dir); from there one time step per step, backwards for direction 0
@@ -472,7 +531,13 @@ __device__ __forceinline__ void gru_backward_steps(const GruBwdArgs& a, bf16x8* 
   // operands of the step after the next one (two register sets, used alternately): every global load has two whole
   // steps (~3 us) to arrive, so the recurrence keeps its pace when weight-gradient GEMMs run beside it on the other
   // CUs (seld_overlap.py) and the memory system answers late.
+  //
+  // Which products are fused with the sum behind them is written out, not left to the compiler (contraction is off in
+  // the step): it chose differently per tile geometry and per instantiation, and bit-exact results across them are what
+  // the tests hold the kernels to.  The two fused operations are the ones the 4-sequence build has always had:
+  // 1 - n^2 = fma(-n, n, 1) and dh = fma(dtot, z, W_hh^T dgh); the bias sums add the rounded gate gradients.
   auto step = [&](long t, GruStepIn<T>& in) {
+#pragma clang fp contract(off)
     const long tt = time_of(t);
     float r[kU], z[kU], n[kU], g[kU], hp[kU], d[kU];
     dec2<S>(in.rz, r, z);
@@ -493,11 +558,11 @@ __device__ __forceinline__ void gru_backward_steps(const GruBwdArgs& a, bf16x8* 
       const float dtot = d[i] + dh[i];
       const float dn = dtot * (1.0f - z[i]);
       const float dz = dtot * (hprev - n[i]);
-      da_n[i] = dn * (1.0f - n[i] * n[i]);
+      da_n[i] = dn * fmaf(-n[i], n[i], 1.0f);
       da_z[i] = dz * z[i] * (1.0f - z[i]);
       da_r[i] = da_n[i] * g[i] * r[i] * (1.0f - r[i]);
       dghn[i] = da_n[i] * r[i];
-      keep[i] = dtot * z[i];
+      keep[i] = dtot;
       bsum[0][i] += da_r[i];
       bsum[1][i] += da_z[i];
       bsum[2][i] += da_n[i];
@@ -566,9 +631,9 @@ __device__ __forceinline__ void gru_backward_steps(const GruBwdArgs& a, bf16x8* 
 #pragma unroll
     for (int s = 0; s < 2; ++s) total[s] = acc[s][0] + acc[s][1];
     float mine[kU];
-    own_values(total, mine);
+    own_values(total, mine, part);
 #pragma unroll
-    for (int i = 0; i < kU; ++i) dh[i] = keep[i] + mine[i];
+    for (int i = 0; i < kU; ++i) dh[i] = fmaf(keep[i], z[i], mine[i]);
   };
 
   GruStepIn<T> in_a, in_b;
@@ -591,7 +656,7 @@ __device__ __forceinline__ void gru_backward_steps(const GruBwdArgs& a, bf16x8* 
     for (int i = 0; i < kU; ++i) {
       float v = bsum[k][i];
       v += __shfl_xor(v, 1);
-      v += __shfl_xor(v, 2);
+      if (kSeqs >= 4) v += __shfl_xor(v, 2);
       if (kSeqs == 8) v += __shfl_xor(v, 4);
       bsum[k][i] = v;
     }
@@ -676,10 +741,15 @@ __global__ __launch_bounds__(256) void gru_from_pair_tile_kernel(const Raw<2 * k
     if (b >= B) continue;
     const Raw<2 * kGroupBytes> p = src[blk * (8 * 2 * 64) + g];
     Raw<kGroupBytes> lo, hi;
+    if constexpr (kGroupBytes == 2) {                      // one 2-byte unit per group: the halves of one word
+      lo.w[0] = static_cast<unsigned short>(p.w[0]);
+      hi.w[0] = static_cast<unsigned short>(p.w[0] >> 16);
+    } else {
 #pragma unroll
-    for (int k = 0; k < kWords; ++k) {
-      lo.w[k] = p.w[k];
-      hi.w[k] = p.w[kWords + k];
+      for (int k = 0; k < kWords; ++k) {
+        lo.w[k] = p.w[k];
+        hi.w[k] = p.w[kWords + k];
+      }
     }
     const long row = (b * T + t) * 2 + dir;
     if (ps == 0) {
@@ -833,7 +903,7 @@ int seld_gru_backward_direct(const void* dy, const void* saved_tile, const void*
   if (H != kH) return fail(kErrUnsupported, "seld_gru_backward_direct: built for hidden size 256 (config.py:45)");
   if (!is_bf16) return fail(kErrUnsupported, "seld_gru_backward_direct: bf16 only (fp32 takes seld_gru_backward)");
   // (8-sequence tiles: 128 KB + 2 x 8 x 2080 B of LDS is over the CU's 160 KB, and the second prefetch set spills)
-  if (kSeqs != 4) return fail(kErrUnsupported, "seld_gru_backward_direct: 4-sequence tiles only (SELD_GRU_SEQS)");
+  if (kSeqs > 4) return fail(kErrUnsupported, "seld_gru_backward_direct: 4- or 2-sequence tiles only (SELD_GRU_SEQS)");
   if (B <= 0 || T <= 0) return fail(kErrInvalidArgument, "seld_gru_backward_direct: B and T must be positive");
   if (!dy || !saved_tile || !y || !w_hh_t_bf16 || !dgi || !dghn || !dbias)
     return fail(kErrInvalidArgument, "seld_gru_backward_direct: null pointer");

@@ -1393,11 +1393,12 @@ def dwconv1d_wgrad(x: torch.Tensor, dy: torch.Tensor, k: int):
 # --------------------------------------------------------------------------- GRU recurrence
 
 GRU_H = 256
-GRU_TILE = 4          # sequences per workgroup; set from seld_gru_tile_rows() by load_library()
+GRU_TILE = 2          # sequences per workgroup; set from seld_gru_tile_rows() by load_library()
 
 
 def _tile_geometry():
-    """(sequences per tile, lanes sharing a sequence, units per lane) of the loaded library (8, 2, 4) or (4, 4, 2).
+    """(sequences per tile, lanes sharing a sequence, units per lane) of the loaded library: (8, 2, 4), (4, 4, 2) or
+    (2, 8, 1).
     Without a built library (CPU-only checks of the torch layout definitions) the default build's geometry."""
     if LIB_PATH.exists():
         load_library()
@@ -1479,7 +1480,7 @@ def gru_previous_state(y: torch.Tensor) -> torch.Tensor:
 def gru_forward(gi: torch.Tensor, w_hh: torch.Tensor, b_hn: torch.Tensor, need_saved: bool):
     """gi [B, T, 2, 3H] (fp32 / bf16; must already include b_ih and the r/z part of b_hh), w_hh [2, 3H, H],
     b_hn [2, H] (n-gate recurrent bias) -> (y [B, T, 2H], saved (tile layout, opaque) or None).  y is a view of
-    the first B rows of a buffer padded to whole 8-sequence tiles."""
+    the first B rows of a buffer padded to whole tiles of GRU_TILE sequences."""
     if not gi.is_cuda:
         raise SeldNativeError("gru_forward: tensors must live on the GPU")
     b, t, two, g3 = gi.shape
@@ -1524,7 +1525,7 @@ def gru_backward(dy: torch.Tensor, saved: torch.Tensor, y: torch.Tensor, w_hh: t
         if w_hh_t.dtype != torch.bfloat16 or tuple(w_hh_t.shape) != (2, h, 3 * h) or not w_hh_t.is_contiguous():
             raise ValueError("gru_backward: w_hh_t must be contiguous bf16 [2, H, 3H]")
         w_t = w_hh_t
-    if direct and dy.dtype == torch.bfloat16 and GRU_TILE == 4:           # (the 8-sequence build has no direct kernel)
+    if direct and dy.dtype == torch.bfloat16 and GRU_TILE <= 4:           # (the 8-sequence build has no direct kernel)
         tiles = (b + GRU_TILE - 1) // GRU_TILE
         dy, y = dy.contiguous(), y.contiguous()
         dgi = torch.empty((b, t, 2, 3, h), dtype=dy.dtype, device=dy.device)
