@@ -1019,9 +1019,46 @@ def layernorm_supported(d: int) -> bool:
     return bool(load_library().seld_layernorm_supported(int(d)))
 
 
-def layernorm_forward(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, relu: bool):
-    """x [..., D] contiguous fp32 / bf16; weight, bias [D] fp32 -> (y like x, mean_rstd [rows, 2] fp32)."""
+def _layernorm_refuse(what, x, weight, bias, dy, stats):
+    """Name the argument the LayerNorm kernels cannot take (they read raw pointers: a wrong layout is silent garbage)."""
+    def bad(msg):
+        raise SeldNativeError(f"{what}: {msg}")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        bad(f"x must be float32 or bfloat16, got {x.dtype}")
+    if x.dim() < 1 or x.shape[-1] == 0:
+        bad(f"x must be [..., D], got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        bad("x must be contiguous")
     d = x.shape[-1]
+    others = [("weight", weight, (d,), torch.float32), ("bias", bias, (d,), torch.float32)]
+    if dy is not None:
+        others.append(("dy", dy, tuple(x.shape), x.dtype))
+    if stats is not None:
+        others.append(("stats", stats, (x.numel() // d, 2), torch.float32))
+    for name, t, shape, dtype in others:
+        if t.device != x.device:
+            bad(f"{name} is on {t.device}, x on {x.device}")
+        if t.dtype != dtype:
+            bad(f"{name} must be {dtype}, got {t.dtype}")
+        if tuple(t.shape) != shape:
+            bad(f"{name} must be {shape}, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            bad(f"{name} must be contiguous")
+    bad("arguments refused")
+
+
+def _layernorm_ok(x, t, dtype):
+    return t.dtype == dtype and t.device == x.device and t.is_contiguous()
+
+
+def layernorm_forward(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, relu: bool):
+    """x [..., D] contiguous fp32 / bf16; weight, bias [D] fp32 contiguous, all on one device
+    -> (y like x, mean_rstd [rows, 2] fp32).  Anything else is refused before a launch (SeldNativeError)."""
+    d = x.shape[-1] if x.dim() else 0
+    if not (d and x.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous()
+            and weight.shape == (d,) and bias.shape == (d,)
+            and _layernorm_ok(x, weight, torch.float32) and _layernorm_ok(x, bias, torch.float32)):
+        _layernorm_refuse("layernorm_forward", x, weight, bias, None, None)
     rows = x.numel() // d
     y = torch.empty_like(x)
     stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
@@ -1034,8 +1071,15 @@ def layernorm_forward(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
 
 def layernorm_backward(x: torch.Tensor, dy: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
                        stats: torch.Tensor, relu: bool):
-    """-> (dx like x, dweight [D] fp32, dbias [D] fp32)."""
-    d = x.shape[-1]
+    """dy like x (dtype, shape, contiguous); stats [rows, 2] fp32 as layernorm_forward returned it
+    -> (dx like x, dweight [D] fp32, dbias [D] fp32).  Anything else is refused before a launch (SeldNativeError)."""
+    d = x.shape[-1] if x.dim() else 0
+    if not (d and x.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous()
+            and weight.shape == (d,) and bias.shape == (d,) and dy.shape == x.shape
+            and stats.shape == (x.numel() // d, 2)
+            and _layernorm_ok(x, weight, torch.float32) and _layernorm_ok(x, bias, torch.float32)
+            and _layernorm_ok(x, dy, x.dtype) and _layernorm_ok(x, stats, torch.float32)):
+        _layernorm_refuse("layernorm_backward", x, weight, bias, dy, stats)
     rows = x.numel() // d
     lib = load_library()
     dx = torch.empty_like(x)
