@@ -348,6 +348,38 @@ int seld_window_gather_mic_standardised(const float* src, int64_t total_rows, in
                                   const int8_t* mic_perm, float mask_value, const float* scale, const float* shift,
                                   float* dst, void* stream);
 
+/* ---- frequency shift, gain curve and cutouts in place on a gathered batch (csrc/spectral.hip) -- */
+/* One stage for all the feature gathers above: batch float32 [B][window][channels][64], as any of them wrote it WITHOUT masks
+ * and WITHOUT scale / shift, is rewritten in place.  spectral: int32 [B][SELD_SPECTRAL_PARAM_INTS] on the device =
+ *   [0] frequency shift s in bins (signed)      [1] flags, bit 0: this window has a gain curve
+ *   [2] [3] [4] [5] cutout 0 (first frame, frames, first bin, bins)      [6] [7] [8] [9] cutout 1      [10] [11] padding.
+ * curves: float32 [B][64] on the device (dB per destination bin), or NULL: no window has a curve.  params: the parameter
+ * rows of the gathers above (only their mask fields [1..8] are read), or NULL: no masks.  Per window b, frame w, channel c,
+ * bin f, in this order:
+ *   1. row starts[b] + w outside [0, total_rows): the row is left as the gather wrote it (zeros);
+ *   2. c < freq_channels:  v = batch[b][w][c][clamp(f - s, 0, 63)]  (edge replication; an exact copy), else v = batch[b][w][c][f];
+ *   3. c < logmel_channels and the window has a curve:  v <= -100 (power_to_db's floor: power 0) stays, else
+ *      v = max(v + curves[b][f], -100)  (one fp32 addition);
+ *   4. the _standardised export:  v = fmaf(v, scale[c][f], shift[c][f]), the map of the _affine gathers above;
+ *   5. the time / frequency masks of params[b] as seld_window_gather_augment, then the two cutouts: an element with w in
+ *      [t, t + tl), f in [f0, f0 + fl) and c < freq_channels becomes mask_value.  A masked element is exactly mask_value.
+ * With s = 0, no curve and no cutout the result is bit for bit what the gather's own masking / standardising export writes.
+ * A window with s = 0, no curve, no cutout and no mask is not touched by the export without scale / shift.
+ * In place and race-free: every lane loads only the 16 bytes it stores; shifted bins move between the 16 lanes of a 256-byte
+ * row in registers.  The shift only selects a bin through the clamp, cutouts and masks are only compared, a curve value is
+ * only added, starts only pass the row-in-timeline test: no row can move a load or a store out of the batch.  No allocation,
+ * no synchronisation (graph-capture safe).  Refused: the extents, channels <= 0 or not 0 <= logmel_channels <= freq_channels
+ * <= channels (-1); a window too large (-4); B == 0 returns 0 before any pointer is looked at; batch, starts, spectral (and
+ * scale, shift) null (-1). */
+#define SELD_SPECTRAL_PARAM_INTS 12
+int seld_window_spectral(float* batch, int64_t total_rows, int channels, int logmel_channels, int freq_channels,
+                         const int64_t* starts, const int32_t* params, const int32_t* spectral, const float* curves,
+                         int64_t B, int64_t window, float mask_value, void* stream);
+int seld_window_spectral_standardised(float* batch, int64_t total_rows, int channels, int logmel_channels, int freq_channels,
+                                      const int64_t* starts, const int32_t* params, const int32_t* spectral,
+                                      const float* curves, int64_t B, int64_t window, float mask_value, const float* scale,
+                                      const float* shift, void* stream);
+
 /* ---- loss: loss.py:43-54 class_mse_loss (+ its backward) ---------------------------------- */
 /* logits [n_cells][14] (fp32, or bf16 when logits_is_bf16), labels as EITHER the compact mask
  * (uint16 [n_cells]) OR dense float32 [n_cells][14] (exactly one non-NULL).  Writes

@@ -183,6 +183,19 @@ class Config:
                                 # united (csrc/mix.hip): powers add on the stored features.  'logmel' and
                                 # 'logmel_iv' only; not together with AUGMENT_ROTATE
     AUGMENT_MIX_GAIN_DB = 6.0   # the partner's level relative to the window: uniform in +- this many dB
+    # One in-place stage on the gathered batch (csrc/spectral.hip), after any of the gathers above and
+    # before standardisation and masks; every feature set; all off by default (then no launch is added)
+    AUGMENT_FREQ_SHIFT_MAX = 0  # frequency shifting: the window moved by s mel bands, s uniform in [-max, max] (<= 63), the edge
+                                # band replicated; mel-axis channels only (not GCC-PHAT lags)
+    AUGMENT_LEVEL_DB = 0.0      # a random overall level per window, uniform in +- this many dB, added to the log-mel channels
+    AUGMENT_FILTER_PROB = 0.0   # FilterAugment: probability that a window gets a random piecewise gain curve over the mel bands
+    AUGMENT_FILTER_DB = 6.0     # its gains: uniform in +- this many dB
+    AUGMENT_FILTER_BANDS = (3, 6)   # its number of bands: uniform in [fewest, most]
+    AUGMENT_FILTER_TYPE = "linear"  # 'linear' (a gain per band edge, interpolated) or 'step' (a gain per band)
+    AUGMENT_CUTOUTS = 0         # random cutout: time x frequency rectangles per window, 0..2, set to AUGMENT_MASK_VALUE on the
+                                # mel-axis channels
+    AUGMENT_CUTOUT_TIME_MAX = 0 # longest cutout in frames (a length is uniform in [0, max])
+    AUGMENT_CUTOUT_FREQ_MAX = 0 # widest cutout in mel bins
     FOA_CHANNEL_ORDER = "WYZX"  # which input channel is which: 'WYZX' (STARSS / DCASE FOA recordings) or 'WXYZ'
     MIC_POSITIONS = None        # microphone-array recordings: the microphone positions, which define the array's channel swaps
                                 # (seld_augment.py, csrc/micswap.hip).  None = unknown (FOA rules: an

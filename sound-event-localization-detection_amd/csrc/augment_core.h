@@ -122,6 +122,46 @@ __device__ __forceinline__ Partner load_partner(const int64_t* __restrict__ part
   return p;
 }
 
+// The spectral row of window b in the in-place stage (spectral.hip): int32 x SELD_SPECTRAL_PARAM_INTS =
+// [0] frequency shift s, [1] flags (bit 0: the window has a gain curve), [2..5] / [6..9] two cutouts (t, tl, f0, fl).  Nothing
+// is trusted: the shift is clamped to +-64 (beyond +-63 every bin is an edge copy anyway) and then only selects a bin through
+// a second clamp, the cutout fields are only compared.
+constexpr int kSpectralInts = SELD_SPECTRAL_PARAM_INTS;
+
+struct SpectralParams {
+  int shift;
+  bool curve;
+  int t0, tl0, f0, fl0, t1, tl1, f1, fl1;
+};
+
+__device__ __forceinline__ SpectralParams load_spectral(const int32_t* __restrict__ spectral, long b) {
+  const int32_t* row = spectral + b * kSpectralInts;
+  SpectralParams s;
+  s.shift = row[0] < -kFeatureBins ? -kFeatureBins : row[0] > kFeatureBins ? kFeatureBins : row[0];
+  s.curve = (row[1] & 1) != 0;
+  s.t0 = row[2]; s.tl0 = row[3]; s.f0 = row[4]; s.fl0 = row[5];
+  s.t1 = row[6]; s.tl1 = row[7]; s.f1 = row[8]; s.fl1 = row[9];
+  return s;
+}
+
+// neither cutout of the row can hit an element
+__device__ __forceinline__ bool no_cutouts(const SpectralParams& s) {
+  return (s.tl0 <= 0 || s.fl0 <= 0) && (s.tl1 <= 0 || s.fl1 <= 0);
+}
+
+// the two cutout rectangles on one 16-byte chunk (bins 4 fc .. 4 fc + 3) of frame w of output channel c
+__device__ __forceinline__ uint4 cut_out(uint4 v, int w, int c, int fc, const SpectralParams& s, int freq_channels,
+                                         unsigned mask_bits) {
+  if (c >= freq_channels) return v;
+  const bool in0 = in_span(w, s.t0, s.tl0), in1 = in_span(w, s.t1, s.tl1);
+  const int f = fc * 4;
+  if ((in0 && in_span(f + 0, s.f0, s.fl0)) || (in1 && in_span(f + 0, s.f1, s.fl1))) v.x = mask_bits;
+  if ((in0 && in_span(f + 1, s.f0, s.fl0)) || (in1 && in_span(f + 1, s.f1, s.fl1))) v.y = mask_bits;
+  if ((in0 && in_span(f + 2, s.f0, s.fl0)) || (in1 && in_span(f + 2, s.f1, s.fl1))) v.z = mask_bits;
+  if ((in0 && in_span(f + 3, s.f0, s.fl0)) || (in1 && in_span(f + 3, s.f1, s.fl1))) v.w = mask_bits;
+  return v;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 static inline unsigned mask_bits(float mask_value) {
   unsigned bits;

@@ -506,7 +506,7 @@ class SELDDataset(Dataset):
         return spec, torch.from_numpy(_expand_mask_host(mask, self.num_classes))
 
     # -- device feed (used by trainer when DEVICE_FEED is on) -----------------------------------
-    def device_batch(self, indices, out=None, augment=None, mix=None):
+    def device_batch(self, indices, out=None, augment=None, mix=None, spectral=None):
         """Window indices -> (spec [B, 250, C, 64] f32, mask [B, 250, 648] u16) on the device, gathered
         by seld_window_gather straight from the device timeline (no host round trip, no dense labels).
         ``out``: callable (spec_shape, spec_dtype, mask_shape, mask_dtype) -> (spec_buffer, mask_buffer) or None --
@@ -523,7 +523,40 @@ class SELDDataset(Dataset):
         On a dataset constructed with Config.MIC_POSITIONS (``mic_array``) the augmenting pair is the
         array's: 'logmel_gcc' / 'logmel_nipd' features go through the array gather (csrc/micswap.hip), 'logmel' through
         the augmenting gather with the array's channel table, labels through the same cell permutation.  A host row that
-        names a pattern which is no symmetry of the array is refused before anything is launched; no ``mix``."""
+        names a pattern which is no symmetry of the array is refused before anything is launched; no ``mix``.
+        ``spectral``: None, or the windows' (spectral rows int32 [B, 12], gain curves float32 [B, 64] or None) of
+        ``seld_augment.draw_spectral``: frequency shift, gain curve and cutouts, applied by ONE in-place stage on the gathered
+        batch (csrc/spectral.hip) whichever of the gathers above produced it.  The order stays
+        transform, mix, shift, gain, standardise, masks: the gather runs without masks and without the standardising map, and
+        the stage applies both after its own steps.  With identity rows the batch is what it is without ``spectral``, bit
+        for bit.  With ``augment`` None the plain gather feeds the stage."""
+        if spectral is None:
+            return self._gather_batch(indices, out, augment, mix)
+        if self.spec_tm is None:
+            raise RuntimeError("device_batch needs keep_on_device=True")
+        if not (isinstance(spectral, (tuple, list)) and len(spectral) == 2):
+            raise ValueError("device_batch: spectral must be (rows, curves) as seld_augment.draw_spectral returns them")
+        n, w = len(np.asarray(indices, dtype=np.int64).reshape(-1)), self.window_length_frames
+        rows, curves = seld_native.spectral_params(spectral[0], spectral[1], n, w, self.device)   # refused before any launch
+        unmasked = params = None
+        if augment is not None:                                      # the gather transforms (and mixes); the stage masks
+            steps = self.J if getattr(self, "rot_tm", None) is not None else None
+            params = seld_native.augment_params(augment, n, w, self.device, steps=steps)      # the rows as they were drawn
+            unmasked = augment.clone() if isinstance(augment, torch.Tensor) else np.array(augment, dtype=np.int32)
+            unmasked[:, 1:9] = 0
+        spec, mask = self._gather_batch(indices, out, unmasked, mix, standardise=False)
+        feature_set = getattr(config, "FEATURE_SET", "logmel")
+        starts = torch.as_tensor(self.window_starts[np.asarray(indices, dtype=np.int64).reshape(-1)])
+        seld_native.window_spectral(spec, starts, int(self.spec_tm.shape[0]), params, rows, curves,
+                                    seld_augment.logmel_channels(feature_set, self.n_channels),
+                                    seld_augment.freq_mask_channels(feature_set, self.n_channels),
+                                    float(getattr(config, "AUGMENT_MASK_VALUE", 0.0)),
+                                    scale=getattr(self, "_feature_scale", None), shift=getattr(self, "_feature_shift", None))
+        return spec, mask
+
+    def _gather_batch(self, indices, out, augment, mix, standardise=True):
+        """``device_batch`` without the spectral stage; ``standardise`` False: the gathers' plain exports although the dataset
+        has statistics (the stage applies them)."""
         if self.spec_tm is None:
             raise RuntimeError("device_batch needs keep_on_device=True")
         if mix is not None:
@@ -540,6 +573,8 @@ class SELDDataset(Dataset):
                        (len(starts), w) + tuple(self.mask_tm.shape[1:]), self.mask_tm.dtype)
         # set_feature_statistics: the same three gathers through their standardising exports (None: the exports they were)
         scale, shift = getattr(self, "_feature_scale", None), getattr(self, "_feature_shift", None)
+        if not standardise:
+            scale = shift = None
         if augment is not None:
             table, freq_channels, mask_value = self._augment_tables()
             starts = starts.to(self.device, non_blocking=True)

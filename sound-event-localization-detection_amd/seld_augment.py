@@ -43,7 +43,12 @@ MIC_FEATURE_SETS = ("logmel", "logmel_gcc", "logmel_nipd")      # the feature se
 # (azimuth, elevation) in degrees and radius in metres of the preset arrays
 MIC_PRESETS = {"tetra_starss": (((45.0, 35.0), (-45.0, -35.0), (135.0, -35.0), (-135.0, 35.0)), 0.042)}
 
-SWITCHES = ("AUGMENT_SPATIAL", "AUGMENT_TIME_MASKS", "AUGMENT_FREQ_MASKS", "AUGMENT_ROTATE", "AUGMENT_MIX_PROB")
+SPECTRAL_PARAM_INTS = 12          # SELD_SPECTRAL_PARAM_INTS: the spectral row of the in-place stage (csrc/spectral.hip)
+SPECTRAL_CURVE = 1                # flag bit 0 of slot [1]: the window has a gain curve
+FILTER_TYPES = ("linear", "step")
+
+SPECTRAL_SWITCHES = ("AUGMENT_FREQ_SHIFT_MAX", "AUGMENT_LEVEL_DB", "AUGMENT_FILTER_PROB", "AUGMENT_CUTOUTS")
+SWITCHES = ("AUGMENT_SPATIAL", "AUGMENT_TIME_MASKS", "AUGMENT_FREQ_MASKS", "AUGMENT_ROTATE", "AUGMENT_MIX_PROB") + SPECTRAL_SWITCHES
 
 
 def decode(p: int):
@@ -113,6 +118,17 @@ def freq_mask_channels(feature_set: str, n_channels: int) -> int:
         c = int(round((np.sqrt(8 * n_channels + 1) - 1) / 2))
         return c if c * (c + 1) // 2 == n_channels else 0
     return n_channels
+
+
+def logmel_channels(feature_set: str, n_channels: int) -> int:
+    """The leading channels that are log-mel in dB -- the ones a gain curve of the spectral stage is added to (DESIGN.md
+    section 26): every channel of 'logmel', 4 of 'logmel_iv', the microphones of 'logmel_gcc' / 'logmel_nipd'; 0 for a
+    channel count that fits no such set."""
+    if feature_set == "logmel":
+        return int(n_channels)
+    if feature_set == "logmel_iv":
+        return 4
+    return mic_count(feature_set, n_channels)
 
 
 def cell_dest(p: int, I: int = 18, J: int = 36) -> np.ndarray:
@@ -291,12 +307,29 @@ def settings(cfg):
         "order": str(getattr(cfg, "FOA_CHANNEL_ORDER", "WYZX")),
         "mix_prob": float(getattr(cfg, "AUGMENT_MIX_PROB", 0.0)),
         "mix_gain_db": float(getattr(cfg, "AUGMENT_MIX_GAIN_DB", 6.0)),
+        # the in-place spectral stage (csrc/spectral.hip)
+        "freq_shift_max": int(getattr(cfg, "AUGMENT_FREQ_SHIFT_MAX", 0)),
+        "level_db": float(getattr(cfg, "AUGMENT_LEVEL_DB", 0.0)),
+        "filter_prob": float(getattr(cfg, "AUGMENT_FILTER_PROB", 0.0)),
+        "filter_db": float(getattr(cfg, "AUGMENT_FILTER_DB", 6.0)),
+        "filter_bands": tuple(getattr(cfg, "AUGMENT_FILTER_BANDS", (3, 6))),
+        "filter_type": str(getattr(cfg, "AUGMENT_FILTER_TYPE", "linear")),
+        "cutouts": int(getattr(cfg, "AUGMENT_CUTOUTS", 0)),
+        "cutout_time_max": int(getattr(cfg, "AUGMENT_CUTOUT_TIME_MAX", 0)),
+        "cutout_freq_max": int(getattr(cfg, "AUGMENT_CUTOUT_FREQ_MAX", 0)),
     }
+
+
+def spectral_enabled(cfg) -> bool:
+    """A switch of the in-place spectral stage is on: the feed then draws spectral rows (``draw_spectral``)."""
+    s = settings(cfg)
+    return s["freq_shift_max"] != 0 or s["level_db"] != 0 or s["filter_prob"] != 0 or s["cutouts"] != 0
 
 
 def enabled(cfg) -> bool:
     s = settings(cfg)
-    return s["spatial"] or s["rotate"] or s["time_masks"] > 0 or s["freq_masks"] > 0 or s["mix_prob"] > 0
+    return (s["spatial"] or s["rotate"] or s["time_masks"] > 0 or s["freq_masks"] > 0 or s["mix_prob"] > 0
+            or spectral_enabled(cfg))
 
 
 def check_settings(cfg, feature_set: str | None = None, n_channels: int | None = None, array=None):
@@ -346,7 +379,30 @@ def check_settings(cfg, feature_set: str | None = None, n_channels: int | None =
             f"AUGMENT_MIX_PROB is defined for power features ('logmel' with any channel count, 'logmel_iv'), not for "
             f"FEATURE_SET={feature_set!r} with {n_channels} feature channels: the powers of two recordings add, the phase cues "
             f"of two sound fields (GCC-PHAT lags, NIPD) do not add in any stored form, so no mix is defined")
+    _check_spectral_settings(s)
     return s
+
+
+def _check_spectral_settings(s):
+    """The switches of the in-place spectral stage."""
+    if not 0 <= s["freq_shift_max"] <= N_BINS - 1:
+        raise ValueError(f"AUGMENT_FREQ_SHIFT_MAX must be 0..{N_BINS - 1} bins, got {s['freq_shift_max']}")
+    if not (np.isfinite(s["level_db"]) and s["level_db"] >= 0):
+        raise ValueError(f"AUGMENT_LEVEL_DB must be finite and not negative, got {s['level_db']}")
+    if not 0.0 <= s["filter_prob"] <= 1.0:              # a NaN fails both comparisons
+        raise ValueError(f"AUGMENT_FILTER_PROB must be a probability in [0, 1], got {s['filter_prob']}")
+    if not (np.isfinite(s["filter_db"]) and s["filter_db"] >= 0):
+        raise ValueError(f"AUGMENT_FILTER_DB must be finite and not negative, got {s['filter_db']}")
+    bands = s["filter_bands"]
+    if not (len(bands) == 2 and all(isinstance(n, (int, np.integer)) and not isinstance(n, bool) for n in bands)
+            and 1 <= bands[0] <= bands[1] <= N_BINS):
+        raise ValueError(f"AUGMENT_FILTER_BANDS must be (fewest, most) bands with 1 <= fewest <= most <= {N_BINS}, got {bands}")
+    if s["filter_type"] not in FILTER_TYPES:
+        raise ValueError(f"AUGMENT_FILTER_TYPE must be 'linear' or 'step', got {s['filter_type']!r}")
+    if not 0 <= s["cutouts"] <= 2:
+        raise ValueError(f"AUGMENT_CUTOUTS must be 0, 1 or 2, got {s['cutouts']}")
+    if s["cutout_time_max"] < 0 or s["cutout_freq_max"] < 0:
+        raise ValueError("AUGMENT_CUTOUT_TIME_MAX / AUGMENT_CUTOUT_FREQ_MAX must not be negative")
 
 
 def identity_rows(n: int) -> np.ndarray:
@@ -490,3 +546,76 @@ def draw_mix(seed: int, epoch: int, window_indices, cfg, n_windows: int):
             partner[r], gain[r] = other, np.float32(10.0 ** (level / 10.0))
             pattern[r] = p if s["spatial"] else 0
     return partner, pattern, gain
+
+
+# ------------------------------------------------------------------------------------------ the in-place spectral stage
+
+def identity_spectral_rows(n: int) -> np.ndarray:
+    """int32 [n, 12] spectral rows that change nothing: no shift, no curve, no cutout."""
+    return np.zeros((int(n), SPECTRAL_PARAM_INTS), dtype=np.int32)
+
+
+def _uniform_int(u: float, count: int) -> int:
+    """u in [0, 1) -> an integer uniform over 0..count-1 (count >= 1); one draw whatever the count."""
+    return min(int(u * count), count - 1)
+
+
+def filter_curve(rng, s, bins: int = N_BINS) -> np.ndarray:
+    """float64 [bins]: one FilterAugment curve from ``rng`` -- n bands, n uniform in AUGMENT_FILTER_BANDS; edges
+    0 = e_0 < ... < e_n = bins, the interior ones a sorted sample without replacement from 1..bins-1; 'step': one gain per
+    band, 'linear': one gain per edge, interpolated linearly inside each band; gains uniform in +-AUGMENT_FILTER_DB."""
+    lo, hi = s["filter_bands"]
+    n = int(rng.integers(int(lo), int(hi) + 1))
+    inner = np.sort(rng.choice(np.arange(1, bins), size=n - 1, replace=False)) if n > 1 else np.zeros(0, dtype=np.int64)
+    edges = np.concatenate([[0], inner, [bins]]).astype(np.int64)
+    f = np.arange(bins)
+    if s["filter_type"] == "step":
+        gains = rng.uniform(-s["filter_db"], s["filter_db"], n)
+        return gains[np.searchsorted(edges, f, side="right") - 1]
+    gains = rng.uniform(-s["filter_db"], s["filter_db"], n + 1)
+    k = np.searchsorted(edges, f, side="right") - 1     # the band of bin f: g_k + (g_k+1 - g_k) (f - e_k) / (e_k+1 - e_k)
+    return gains[k] + (gains[k + 1] - gains[k]) * (f - edges[k]) / (edges[k + 1] - edges[k]).astype(np.float64)
+
+
+def draw_spectral(seed: int, epoch: int, window_indices, cfg, window: int | None = None, bins: int = N_BINS):
+    """(rows int32 [B, 12], curves float32 [B, 64] or None) of the in-place spectral stage (csrc/spectral.hip, DESIGN.md
+    section 26) for the windows ``window_indices`` of ``epoch``: row = [0] frequency shift, [1] flags (bit 0: the window has a
+    curve), [2..5] / [6..9] two cutouts (first frame, frames, first bin, bins).  ``curves`` is None when no window has one.
+
+    A window's draw comes from ``np.random.default_rng([seed, epoch, index, 2])`` -- a stream of its own, so ``draw`` and
+    ``draw_mix`` ask their generators exactly what they ask without it -- and is a function of (seed, epoch, window index)
+    only.  EVERY question is asked, in one fixed order, whatever is switched on, each as one ``random()``: the shift (uniform
+    integer in +-AUGMENT_FREQ_SHIFT_MAX), the level (uniform in +-AUGMENT_LEVEL_DB dB), for each of the two cutouts its
+    frames (uniform integer in [0, min(AUGMENT_CUTOUT_TIME_MAX, window)]), first frame (uniform over the positions that
+    fit), bins and first bin likewise, then u (a filter iff u < AUGMENT_FILTER_PROB) and, only with a filter, its
+    variable-length part (``filter_curve``).  So switching one component on never changes another's draw.  The curve of a
+    window is level + filter, evaluated in double precision and rounded once; the flag is clear when both are off for it."""
+    s = check_settings(cfg)
+    if window is None:
+        window = int(int(cfg.WINDOW_LENGTH) / int(cfg.SPECTROGRAM_HOP_LENGTH))
+    window = int(window)
+    idx = np.asarray(window_indices, dtype=np.int64).reshape(-1)
+    rows = identity_spectral_rows(len(idx))
+    curves = np.zeros((len(idx), bins), dtype=np.float32)
+    if not spectral_enabled(cfg):
+        return rows, None
+    for r, i in enumerate(idx):
+        rng = np.random.default_rng([int(seed), int(epoch), int(i), 2])
+        rows[r, 0] = _uniform_int(rng.random(), 2 * s["freq_shift_max"] + 1) - s["freq_shift_max"]
+        level = (2.0 * rng.random() - 1.0) * s["level_db"]
+        for n in range(2):
+            u = rng.random(4)
+            frames = _uniform_int(u[0], min(s["cutout_time_max"], window) + 1)
+            first_frame = _uniform_int(u[1], window - frames + 1)
+            width = _uniform_int(u[2], min(s["cutout_freq_max"], bins) + 1)
+            first_bin = _uniform_int(u[3], bins - width + 1)
+            if n < s["cutouts"]:
+                rows[r, 2 + 4 * n:6 + 4 * n] = (first_frame, frames, first_bin, width)
+        filtered = rng.random() < s["filter_prob"]
+        if filtered or s["level_db"] != 0:
+            curve = np.full(bins, level, dtype=np.float64)
+            if filtered:
+                curve = curve + filter_curve(rng, s, bins)
+            rows[r, 1] |= SPECTRAL_CURVE
+            curves[r] = curve.astype(np.float32)
+    return rows, (curves if (rows[:, 1] & SPECTRAL_CURVE).any() else None)

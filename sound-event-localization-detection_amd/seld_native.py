@@ -17,6 +17,7 @@ import torch
 # SELD_AUGMENT_PARAM_INTS (pattern, 2 x (time start, length), 2 x (frequency start, length), azimuth step, padding) and
 # SELD_AUGMENT_PATTERNS: defined once, in seld_augment (numpy only, so no import cycle)
 from seld_augment import PARAM_INTS as AUGMENT_PARAM_INTS, PATTERNS as AUGMENT_PATTERNS, check_channel_order
+from seld_augment import SPECTRAL_PARAM_INTS          # SELD_SPECTRAL_PARAM_INTS: the spectral row of csrc/spectral.hip
 
 _HERE = Path(__file__).resolve().parent
 # SELD_HIP_LIB: developer override to load an experimental build of the SAME library (A/B kernel experiments)
@@ -101,6 +102,9 @@ def _declare(lib):
                                            _ptr]
     lib.seld_window_gather_mic_standardised.argtypes = [_ptr, _i64, _int, _int, _int, _ptr, _ptr, _i64, _i64, _ptr, ctypes.c_float,
                                                   _ptr, _ptr, _ptr, _ptr]
+    lib.seld_window_spectral.argtypes = [_ptr, _i64, _int, _int, _int, _ptr, _ptr, _ptr, _ptr, _i64, _i64, ctypes.c_float, _ptr]
+    lib.seld_window_spectral_standardised.argtypes = [_ptr, _i64, _int, _int, _int, _ptr, _ptr, _ptr, _ptr, _i64, _i64,
+                                                      ctypes.c_float, _ptr, _ptr, _ptr]
     lib.seld_softmax_mse_workspace_bytes.restype = _i64
     lib.seld_softmax_mse_workspace_bytes.argtypes = []
     lib.seld_softmax_mse.argtypes = [_ptr, _int, _ptr, _ptr, _i64, _int, ctypes.c_float, _ptr, _ptr, _ptr, _ptr]
@@ -866,6 +870,93 @@ def gather_windows_mix_mask(src: torch.Tensor, starts: torch.Tensor, window: int
                                                   starts.numel(), window, _p(out), _stream_ptr(src.device)),
               "seld_window_mix_mask")
     return out
+
+
+def spectral_params(rows, curves, B: int, window: int, device):
+    """The spectral rows and gain curves of the in-place stage (csrc/spectral.hip) on the device:
+    (int32 [B, 12], float32 [B, 64] or None).  Host tables (numpy arrays / CPU tensors) are checked here -- |shift| <= 63,
+    both cutouts inside the window and the 64 bins, curves finite -- and uploaded with one small asynchronous copy each;
+    device tensors are trusted (no synchronise; the kernel clamps whatever it is given)."""
+    t = torch.as_tensor(rows)
+    if tuple(t.shape) != (B, SPECTRAL_PARAM_INTS):
+        raise ValueError(f"spectral rows must be [{B}, {SPECTRAL_PARAM_INTS}], got {tuple(t.shape)}")
+    if t.is_cuda:
+        if t.dtype != torch.int32:
+            raise TypeError("spectral rows on the device must be int32")
+        t = t.contiguous()
+    else:
+        t = t.to(torch.int32).contiguous()
+        if B:
+            if int(t[:, 0].abs().max()) > N_MELS - 1:
+                raise ValueError(f"spectral rows: frequency shift outside +-{N_MELS - 1} bins")
+            for first in (2, 6):
+                for axis, what, at in ((window, "frames", first), (N_MELS, "bins", first + 2)):
+                    start, length = t[:, at], t[:, at + 1]
+                    if int(start.min()) < 0 or int(length.min()) < 0 or int((start + length).max()) > axis:
+                        raise ValueError(f"spectral rows: cutout outside the {axis} {what}")
+        t = t.to(device, non_blocking=True)
+    if curves is None:
+        return t, None
+    g = torch.as_tensor(curves)
+    if tuple(g.shape) != (B, N_MELS):
+        raise ValueError(f"gain curves must be [{B}, {N_MELS}], got {tuple(g.shape)}")
+    if g.is_cuda:
+        if g.dtype != torch.float32:
+            raise TypeError("gain curves on the device must be float32")
+        return t, g.contiguous()
+    g = g.to(torch.float32).contiguous()
+    if not bool(torch.isfinite(g).all()):
+        raise ValueError("gain curves must be finite")
+    return t, g.to(device, non_blocking=True)
+
+
+def window_spectral(batch: torch.Tensor, starts: torch.Tensor, total_rows: int, params: torch.Tensor | None,
+                    spectral: torch.Tensor, curves: torch.Tensor | None, logmel_channels: int, freq_channels: int,
+                    mask_value: float = 0.0, scale: torch.Tensor | None = None, shift: torch.Tensor | None = None) -> torch.Tensor:
+    """The in-place spectral stage on a gathered batch [B, window, C, 64] (float32, as a feature gather wrote it WITHOUT
+    masks and WITHOUT ``scale`` / ``shift``; csrc/spectral.hip): per window the frequency shift of its
+    spectral row (edge replication, channels < ``freq_channels``), its gain curve added to the log-mel channels (channels <
+    ``logmel_channels``; the -100 dB floor kept), ``scale`` / ``shift`` (the map of the standardising gathers), the masks of
+    ``params`` (None: no masks) and the two cutouts.  ``starts`` / ``total_rows``: what the gather was called with -- rows
+    outside the timeline stay zero.  ``spectral`` / ``curves``: ``spectral_params``.  Returns ``batch``."""
+    name = "window_spectral"
+    if not (isinstance(batch, torch.Tensor) and batch.is_cuda and batch.dtype == torch.float32 and batch.dim() == 4
+            and batch.shape[3] == N_MELS and batch.is_contiguous()):
+        raise SeldNativeError(f"{name}: batch must be a contiguous float32 GPU tensor [B, window, C, 64]")
+    B, window, channels = int(batch.shape[0]), int(batch.shape[1]), int(batch.shape[2])
+    if window == 0 or channels == 0:
+        raise ValueError(f"{name}: empty batch")
+    index = ensure_init(batch.device)
+    starts = starts.to(device=batch.device, dtype=torch.int64).contiguous()
+    if starts.numel() != B:
+        raise ValueError(f"{name}: starts must hold one frame per window, {B} here")
+    for what, t, dtype, width in (("params", params, torch.int32, AUGMENT_PARAM_INTS),
+                                  ("spectral", spectral, torch.int32, SPECTRAL_PARAM_INTS), ("curves", curves, torch.float32, N_MELS)):
+        if t is None and what != "spectral":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == batch.device and t.dtype == dtype
+                and t.is_contiguous() and tuple(t.shape) == (B, width)):
+            kind = str(dtype).replace("torch.", "")
+            raise ValueError(f"{name}: {what} must be a contiguous {kind} [B, {width}] GPU tensor")
+    if scale is None and shift is None:
+        tables = None
+    elif scale is None or shift is None:
+        raise ValueError(f"{name}: scale and shift come together")
+    else:
+        for what, t in (("scale", scale), ("shift", shift)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == batch.device and t.dtype == torch.float32
+                    and tuple(t.shape) == (channels, N_MELS)):
+                raise SeldNativeError(f"{name}: {what} must be a float32 tensor {[channels, N_MELS]} on {batch.device}")
+        tables = scale.contiguous(), shift.contiguous()
+    head = (_p(batch), int(total_rows), channels, int(logmel_channels), int(freq_channels), _p(starts), _p(params), _p(spectral),
+            _p(curves), B, window, float(mask_value))
+    with _device_guard(index):
+        if tables is not None:
+            check(load_library().seld_window_spectral_standardised(*head, _p(tables[0]), _p(tables[1]),
+                                                                   _stream_ptr(batch.device)), "seld_window_spectral_standardised")
+        else:
+            check(load_library().seld_window_spectral(*head, _stream_ptr(batch.device)), "seld_window_spectral")
+    return batch
 
 
 # --------------------------------------------------------------------------- fused loss

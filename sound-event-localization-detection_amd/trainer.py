@@ -345,14 +345,21 @@ class DeviceFeed:
         augment = bool(augment) and seld_augment.enabled(config)
         # AUGMENT_MIX_PROB: a partner per window from a stream of its own (seld_augment.draw_mix; csrc/mix.hip)
         mixing = augment and seld_augment.settings(config)["mix_prob"] > 0
+        # frequency shift, level / filter curve, cutouts: a third stream per window (seld_augment.draw_spectral), applied by
+        # one in-place stage behind whichever gather produced the batch (csrc/spectral.hip)
+        shaping = augment and seld_augment.spectral_enabled(config)
         for idx in batched(self._order(epoch), self.batch_size, self.drop_last):
             params = seld_augment.draw(self.seed, epoch, idx, config, window=self.dataset.window_length_frames,
                                        array=self.array) if augment else None
+            more = {}
+            if shaping:
+                more["spectral"] = seld_augment.draw_spectral(self.seed, epoch, idx, config,
+                                                              window=self.dataset.window_length_frames)
             if not mixing:
-                yield self.dataset.device_batch(idx, out=out, augment=params)
+                yield self.dataset.device_batch(idx, out=out, augment=params, **more)
                 continue
             mix = seld_augment.draw_mix(self.seed, epoch, idx, config, len(self.dataset))
-            yield self.dataset.device_batch(idx, out=out, augment=params, mix=mix)
+            yield self.dataset.device_batch(idx, out=out, augment=params, mix=mix, **more)
 
 
 def make_feed(loader, device, rank, world):
