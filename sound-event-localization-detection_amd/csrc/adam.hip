@@ -22,8 +22,7 @@
 // the guard record of csrc/guard.hip and returns before its first store when the step is skipped, multiplies the gradient
 // by the clip coefficient after grad_scale (a coefficient of exactly 1 gives the plain kernel's bits), and keeps an fp32
 // exponential moving average of the new masters in the same pass: + 8 B per parameter (ema read and written) on the 28 B.
-#include <hip/hip_bf16.h>
-
+#include "seld_bf16.h"
 #include "seld_common.h"
 #include "seld_hip.h"
 
@@ -66,11 +65,6 @@ __device__ __forceinline__ double adam_beta_power(double beta, float step) {
   return r;
 }
 
-__device__ __forceinline__ unsigned adam_pack_bf16x2(float lo, float hi) {
-  return static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(lo))) |
-         (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(hi))) << 16);
-}
-
 struct AdamGuard {
   unsigned long long ema[kAdamBatch];                    // fp32 moving average of the master, or 0
   const seld_guard_record* guard;                        // or nullptr: always apply, coefficient 1
@@ -110,33 +104,17 @@ __device__ __forceinline__ void multi_adam_body(const AdamBatch& b, const AdamSc
     float g[8], pp[8], mm[8], vv[8], ee[8];
     const bool full = aligned && i + 8 <= n;
     if (full) {
-      if (grad_bf16) {
-        const uint4 w = *reinterpret_cast<const uint4*>(gh + i);
-        const unsigned ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          g[2 * j] = __uint_as_float(ww[j] << 16);
-          g[2 * j + 1] = __uint_as_float(ww[j] & 0xffff0000u);
-        }
-      } else {
-        const float4 a = *reinterpret_cast<const float4*>(gf + i), c = *reinterpret_cast<const float4*>(gf + i + 4);
-        g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w; g[4] = c.x; g[5] = c.y; g[6] = c.z; g[7] = c.w;
-      }
-      const float4 p0 = *reinterpret_cast<const float4*>(p + i), p1 = *reinterpret_cast<const float4*>(p + i + 4);
-      const float4 m0 = *reinterpret_cast<const float4*>(m + i), m1 = *reinterpret_cast<const float4*>(m + i + 4);
-      const float4 v0 = *reinterpret_cast<const float4*>(v + i), v1 = *reinterpret_cast<const float4*>(v + i + 4);
-      pp[0] = p0.x; pp[1] = p0.y; pp[2] = p0.z; pp[3] = p0.w; pp[4] = p1.x; pp[5] = p1.y; pp[6] = p1.z; pp[7] = p1.w;
-      mm[0] = m0.x; mm[1] = m0.y; mm[2] = m0.z; mm[3] = m0.w; mm[4] = m1.x; mm[5] = m1.y; mm[6] = m1.z; mm[7] = m1.w;
-      vv[0] = v0.x; vv[1] = v0.y; vv[2] = v0.z; vv[3] = v0.w; vv[4] = v1.x; vv[5] = v1.y; vv[6] = v1.z; vv[7] = v1.w;
-      if (kGuarded && ema) {
-        const float4 e0 = *reinterpret_cast<const float4*>(ema + i), e1 = *reinterpret_cast<const float4*>(ema + i + 4);
-        ee[0] = e0.x; ee[1] = e0.y; ee[2] = e0.z; ee[3] = e0.w; ee[4] = e1.x; ee[5] = e1.y; ee[6] = e1.z; ee[7] = e1.w;
-      }
+      if (grad_bf16) Row<__hip_bfloat16, 8>::load(gh, i, g);
+      else Row<float, 8>::load(gf, i, g);
+      Row<float, 8>::load(p, i, pp);
+      Row<float, 8>::load(m, i, mm);
+      Row<float, 8>::load(v, i, vv);
+      if (kGuarded && ema) Row<float, 8>::load(ema, i, ee);
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const long e = i + j < n ? i + j : n - 1;
-        g[j] = grad_bf16 ? __uint_as_float(static_cast<unsigned>(gh[e]) << 16) : gf[e];
+        g[j] = grad_bf16 ? bf16_lo(gh[e]) : gf[e];
         pp[j] = p[e];
         mm[j] = m[e];
         vv[j] = v[e];
@@ -155,24 +133,11 @@ __device__ __forceinline__ void multi_adam_body(const AdamBatch& b, const AdamSc
       if (kGuarded && ema) ee[j] = fmaf(x->ema_rate, pp[j] - ee[j], ee[j]);
     }
     if (full) {
-      *reinterpret_cast<float4*>(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
-      *reinterpret_cast<float4*>(p + i + 4) = make_float4(pp[4], pp[5], pp[6], pp[7]);
-      *reinterpret_cast<float4*>(m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-      *reinterpret_cast<float4*>(m + i + 4) = make_float4(mm[4], mm[5], mm[6], mm[7]);
-      *reinterpret_cast<float4*>(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-      *reinterpret_cast<float4*>(v + i + 4) = make_float4(vv[4], vv[5], vv[6], vv[7]);
-      if (low) {
-        uint4 w;
-        w.x = adam_pack_bf16x2(pp[0], pp[1]);
-        w.y = adam_pack_bf16x2(pp[2], pp[3]);
-        w.z = adam_pack_bf16x2(pp[4], pp[5]);
-        w.w = adam_pack_bf16x2(pp[6], pp[7]);
-        *reinterpret_cast<uint4*>(low + i) = w;
-      }
-      if (kGuarded && ema) {
-        *reinterpret_cast<float4*>(ema + i) = make_float4(ee[0], ee[1], ee[2], ee[3]);
-        *reinterpret_cast<float4*>(ema + i + 4) = make_float4(ee[4], ee[5], ee[6], ee[7]);
-      }
+      Row<float, 8>::store(p, i, pp);
+      Row<float, 8>::store(m, i, mm);
+      Row<float, 8>::store(v, i, vv);
+      if (low) Row<__hip_bfloat16, 8>::store(low, i, pp);
+      if (kGuarded && ema) Row<float, 8>::store(ema, i, ee);
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -180,7 +145,7 @@ __device__ __forceinline__ void multi_adam_body(const AdamBatch& b, const AdamSc
           p[i + j] = pp[j];
           m[i + j] = mm[j];
           v[i + j] = vv[j];
-          if (low) low[i + j] = __bfloat16_as_ushort(__float2bfloat16(pp[j]));
+          if (low) low[i + j] = bf16_bits(pp[j]);
           if (kGuarded && ema) ema[i + j] = ee[j];
         }
       }

@@ -6,8 +6,7 @@
 // 8192-element chunk of it; the (source, destination, length) descriptors travel BY VALUE in the kernel arguments
 // (2.3 KB), so gradient tensors that autograd re-allocates every iteration need no descriptor upload.
 // HBM-bound (6 bytes per element), round-to-nearest-even like the framework's casts.
-#include <hip/hip_bf16.h>
-
+#include "seld_bf16.h"
 #include "seld_common.h"
 
 namespace seld {
@@ -15,11 +14,6 @@ namespace seld {
 constexpr int kCastThreads = 256;
 constexpr int kCastPerThread = 32;                       // 4 x 8 elements
 constexpr int kCastChunk = kCastThreads * kCastPerThread;
-
-__device__ __forceinline__ unsigned cast_pack_bf16x2(float lo, float hi) {
-  return static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(lo))) |
-         (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(hi))) << 16);
-}
 
 constexpr int kCastBatch = 96;
 struct CastBatch {
@@ -45,30 +39,18 @@ __global__ __launch_bounds__(kCastThreads) void multi_cast_kernel(const CastBatc
     const long i = base + (static_cast<long>(k) * kCastThreads + threadIdx.x) * 8;
     if (i >= n) break;
     if (aligned && i + 8 <= n) {
+      float f[8];
       if (kToFloat) {
-        const uint4 v = *reinterpret_cast<const uint4*>(hsrc + i);
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-        float4 a, b;
-        a.x = __uint_as_float(w[0] << 16); a.y = __uint_as_float(w[0] & 0xffff0000u);
-        a.z = __uint_as_float(w[1] << 16); a.w = __uint_as_float(w[1] & 0xffff0000u);
-        b.x = __uint_as_float(w[2] << 16); b.y = __uint_as_float(w[2] & 0xffff0000u);
-        b.z = __uint_as_float(w[3] << 16); b.w = __uint_as_float(w[3] & 0xffff0000u);
-        *reinterpret_cast<float4*>(fdst + i) = a;
-        *reinterpret_cast<float4*>(fdst + i + 4) = b;
+        Row<__hip_bfloat16, 8>::load(hsrc, i, f);
+        Row<float, 8>::store(fdst, i, f);
       } else {
-        const float4 a = *reinterpret_cast<const float4*>(fsrc + i);
-        const float4 b = *reinterpret_cast<const float4*>(fsrc + i + 4);
-        uint4 v;
-        v.x = cast_pack_bf16x2(a.x, a.y);
-        v.y = cast_pack_bf16x2(a.z, a.w);
-        v.z = cast_pack_bf16x2(b.x, b.y);
-        v.w = cast_pack_bf16x2(b.z, b.w);
-        *reinterpret_cast<uint4*>(hdst + i) = v;
+        Row<float, 8>::load(fsrc, i, f);
+        Row<__hip_bfloat16, 8>::store(hdst, i, f);
       }
     } else {
       for (long j = i; j < n && j < i + 8; ++j) {
-        if (kToFloat) fdst[j] = __uint_as_float(static_cast<unsigned>(hsrc[j]) << 16);
-        else hdst[j] = __bfloat16_as_ushort(__float2bfloat16(fsrc[j]));
+        if (kToFloat) fdst[j] = bf16_lo(hsrc[j]);
+        else hdst[j] = bf16_bits(fsrc[j]);
       }
     }
   }

@@ -38,9 +38,8 @@
 // writes them as row `chunk` of partials[stat][chunks][Cn].
 #pragma once
 
-#include <hip/hip_bf16.h>
-
 #include "conv3x3_image.h"
+#include "seld_bf16.h"
 
 namespace seld {
 namespace conv3x3 {
@@ -239,10 +238,6 @@ __device__ __forceinline__ void conv3x3_loop(const unsigned short* __restrict__ 
   // instructions of 16 bytes (the tail of 8-byte stores was issue-bound), the same bytes at the same addresses.
   const int rows_left = (T - t0) * F;                           // positions of the chunk inside the clip
   unsigned short* const out = dst + ((clip_row + t0) * F) * Cn + n0 + wn * (NT / 2) + 4 * (g & ~1);
-  auto pack = [](float a, float c) {
-    return static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(a))) |
-           (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(c))) << 16);
-  };
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int pos = wm * 128 + (2 * k + (g & 1)) * 16 + l15;
@@ -251,8 +246,10 @@ __device__ __forceinline__ void conv3x3_loop(const unsigned short* __restrict__ 
       const f32x4 v0 = acc[2 * k][n], v1 = acc[2 * k + 1][n];
       // [0]: rows 0, 2 keep their value of tile 2k, rows 1, 3 receive rows 0, 2's value of tile 2k + 1;
       // [1]: rows 0, 2 receive rows 1, 3's value of tile 2k, rows 1, 3 keep their value of tile 2k + 1
-      const u32x2 lo = __builtin_amdgcn_permlane16_swap(pack(v0[0], v0[1]), pack(v1[0], v1[1]), false, false);
-      const u32x2 hi = __builtin_amdgcn_permlane16_swap(pack(v0[2], v0[3]), pack(v1[2], v1[3]), false, false);
+      const u32x2 lo =
+          __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[0], v0[1]), pack_bf16x2(v1[0], v1[1]), false, false);
+      const u32x2 hi =
+          __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[2], v0[3]), pack_bf16x2(v1[2], v1[3]), false, false);
       if (pos < rows_left)
         *reinterpret_cast<u32x4*>(out + static_cast<long>(pos) * Cn + n * 16) = u32x4{lo[0], hi[0], lo[1], hi[1]};
     }
@@ -269,7 +266,7 @@ __device__ __forceinline__ void conv3x3_loop(const unsigned short* __restrict__ 
         float r[8], s[8];
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
-          const float v = __uint_as_float(static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(acc[m][n][j]))) << 16);
+          const float v = round_bf16(acc[m][n][j]);
           r[m] = wm * 128 + m * 16 + l15 < rows_left ? v : 0.0f;
           s[m] = r[m] * r[m];                                   // exact: 8-bit significands
         }

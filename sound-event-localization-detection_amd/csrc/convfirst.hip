@@ -35,8 +35,7 @@
 // tile nt is channel 4 n + nt, so a lane ends up with FOUR ADJACENT CHANNELS (4 c .. 4 c + 3, c = lane & 15) of four
 // adjacent positions (4 g .. 4 g + 3): both bins of a pooling pair are in the lane, a pooled output's 4 channels are
 // one 8-byte access and 16 lanes cover a full 128-byte row of y / dy.
-#include <hip/hip_bf16.h>
-
+#include "seld_bf16.h"
 #include "seld_common.h"
 
 namespace seld {
@@ -44,8 +43,6 @@ namespace seld {
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((ext_vector_type(2))) short s16x2;
@@ -77,17 +74,9 @@ struct CfWeights {                          // the convolution weight [64][4][3]
   long sco, sci, sr, ss;
 };
 
-__device__ __forceinline__ unsigned pack_bf16_pair(float lo, float hi) {
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));       // v_cvt_pk_bf16_f32 (RNE)
-}
-__device__ __forceinline__ float round_bf16(float z) { return __uint_as_float(pack_bf16_pair(z, 0.0f) << 16); }
-__device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-
 __device__ __forceinline__ float cf_weight(const CfWeights& w, int co, int tap, int ci) {
   const long i = co * w.sco + ci * w.sci + (tap / 3) * w.sr + (tap % 3) * w.ss;
-  if (w.is_bf16) return __uint_as_float(static_cast<unsigned>(static_cast<const unsigned short*>(w.w)[i]) << 16);
+  if (w.is_bf16) return bf16_lo(static_cast<const unsigned short*>(w.w)[i]);
   return round_bf16(static_cast<const float*>(w.w)[i]);       // the cast autocast would do
 }
 
@@ -117,10 +106,10 @@ __device__ __forceinline__ void cf_load_weights(const CfWeights& w, int lane, bf
       v0[e] = cf_weight(w, co, 2 * g + (e >> 2), e & 3);
       v1[e] = (g == 0 && e < 4) ? cf_weight(w, co, 8, e & 3) : 0.0f;
     }
-    const u32x4 p0 = {pack_bf16_pair(v0[0], v0[1]), pack_bf16_pair(v0[2], v0[3]), pack_bf16_pair(v0[4], v0[5]),
-                      pack_bf16_pair(v0[6], v0[7])};
-    const u32x4 p1 = {pack_bf16_pair(v1[0], v1[1]), pack_bf16_pair(v1[2], v1[3]), pack_bf16_pair(v1[4], v1[5]),
-                      pack_bf16_pair(v1[6], v1[7])};
+    const u32x4 p0 = {pack_bf16x2(v0[0], v0[1]), pack_bf16x2(v0[2], v0[3]), pack_bf16x2(v0[4], v0[5]),
+                      pack_bf16x2(v0[6], v0[7])};
+    const u32x4 p1 = {pack_bf16x2(v1[0], v1[1]), pack_bf16x2(v1[2], v1[3]), pack_bf16x2(v1[4], v1[5]),
+                      pack_bf16x2(v1[6], v1[7])};
     wb[nt][0] = __builtin_bit_cast(bf16x8, p0);
     wb[nt][1] = __builtin_bit_cast(bf16x8, p1);
   }
@@ -174,8 +163,8 @@ __device__ __forceinline__ void cf_conv_tile(const uint2* img, const CfLane& ln,
     f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, wb[nt][0], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, wb[nt][1], acc, 0, 0, 0);
-    xp[nt][0] = pack_bf16_pair(acc[0], acc[1]);
-    xp[nt][1] = pack_bf16_pair(acc[2], acc[3]);
+    xp[nt][0] = pack_bf16x2(acc[0], acc[1]);
+    xp[nt][1] = pack_bf16x2(acc[2], acc[3]);
   }
 }
 
@@ -201,7 +190,7 @@ __device__ __forceinline__ unsigned cf_relu_pair(unsigned p) {
 
 // relu(round_bf16(a x + b)) of both bins of a pooling pair (tail_apply_kernel<bf16, 2> / route<bf16, 2>), packed
 __device__ __forceinline__ unsigned cf_activate(unsigned xpair, float a, float b) {
-  return cf_relu_pair(pack_bf16_pair(fmaf(bf16_lo(xpair), a, b), fmaf(bf16_hi(xpair), a, b)));
+  return cf_relu_pair(pack_bf16x2(fmaf(bf16_lo(xpair), a, b), fmaf(bf16_hi(xpair), a, b)));
 }
 
 struct CfChunk {
@@ -637,7 +626,7 @@ __global__ __launch_bounds__(kCfThreads, 2) void convfirst_wgrad_kernel(
             const float g0 = (pass && !second) ? gv : 0.0f, g1 = (pass && second) ? gv : 0.0f;
             const float d0 = fmaf(a[nt], g0, fmaf(q[nt], bf16_lo(xp[nt][jp]), p[nt]));
             const float d1 = fmaf(a[nt], g1, fmaf(q[nt], bf16_hi(xp[nt][jp]), p[nt]));
-            dxp[u][nt][jp] = pack_bf16_pair(d0, d1);
+            dxp[u][nt][jp] = pack_bf16x2(d0, d1);
           }
         }
       }
@@ -708,7 +697,7 @@ __global__ __launch_bounds__(kCfSumThreads) void convfirst_wgrad_sum_kernel(cons
   const float v[4] = {s.x, s.y, s.z, s.w};
 #pragma unroll
   for (int ci = 0; ci < kCfCin; ++ci) {
-    if (dw_is_bf16) static_cast<unsigned short*>(dw)[o + ci * sci] = static_cast<unsigned short>(pack_bf16_pair(v[ci], 0.0f) & 0xffffu);
+    if (dw_is_bf16) static_cast<unsigned short*>(dw)[o + ci * sci] = bf16_bits(v[ci]);
     else static_cast<float*>(dw)[o + ci * sci] = v[ci];
   }
 }

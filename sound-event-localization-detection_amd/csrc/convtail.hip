@@ -26,6 +26,7 @@
 // deterministic, no float atomics.
 #include <hip/hip_bf16.h>
 
+#include "seld_bf16.h"
 #include "seld_common.h"
 
 namespace seld {
@@ -35,53 +36,8 @@ constexpr int kTailStatBlocks = 1024;    // partial-sum rows per statistic (4 bl
 constexpr int kFinalChannels = 16;       // channels per finalise block
 constexpr int kFinalThreads = 1024;      // 32 (statistic, channel) items x 32 partial rows in flight
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack_bf16_pair(float lo, float hi) {
-  const f32x2_t v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));     // v_cvt_pk_bf16_f32 (RNE)
-}
-
-// ---- 8 consecutive channels of one row
-template <typename T> struct Row8;
-template <> struct Row8<__hip_bfloat16> {
-  static __device__ __forceinline__ void load(const void* base, long elem, float (&f)[8]) {
-    const uint4 v = *reinterpret_cast<const uint4*>(static_cast<const unsigned short*>(base) + elem);
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __uint_as_float(w[i] << 16);
-      f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ void store(void* base, long elem, const float (&f)[8]) {
-    uint4 v;
-    v.x = pack_bf16_pair(f[0], f[1]);
-    v.y = pack_bf16_pair(f[2], f[3]);
-    v.z = pack_bf16_pair(f[4], f[5]);
-    v.w = pack_bf16_pair(f[6], f[7]);
-    *reinterpret_cast<uint4*>(static_cast<unsigned short*>(base) + elem) = v;
-  }
-  // the value the unfused modules would hold after BatchNorm wrote its bf16 output
-  static __device__ __forceinline__ float round(float z) {
-    return __uint_as_float(pack_bf16_pair(z, 0.0f) << 16);
-  }
-};
-template <> struct Row8<float> {
-  static __device__ __forceinline__ void load(const void* base, long elem, float (&f)[8]) {
-    const float4* p = reinterpret_cast<const float4*>(static_cast<const float*>(base) + elem);
-    const float4 a = p[0], b = p[1];
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
-    f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-  }
-  static __device__ __forceinline__ void store(void* base, long elem, const float (&f)[8]) {
-    float4* p = reinterpret_cast<float4*>(static_cast<float*>(base) + elem);
-    p[0] = make_float4(f[0], f[1], f[2], f[3]);
-    p[1] = make_float4(f[4], f[5], f[6], f[7]);
-  }
-  static __device__ __forceinline__ float round(float z) { return z; }
-};
+// Row<T, 8> (seld_bf16.h): 8 consecutive channels of one row; its round() is the value the unfused modules would hold
+// after BatchNorm wrote its output in the activation dtype.
 
 // Sum `acc[kN]` (per thread: 8 channels x kN/8 statistics) over the row slots of the block and write the block's
 // partial sums to partials[stat][block][C].  Threads are laid out tid = slot * groups + cg.
@@ -118,7 +74,7 @@ __global__ __launch_bounds__(kTailThreads) void tail_stats_kernel(const void* __
   const long slot = (static_cast<long>(blockIdx.x) * kTailThreads + threadIdx.x) / groups;
   const long slots_total = static_cast<long>(gridDim.x) * kTailThreads / groups;
   float shift[8];
-  Row8<T>::load(x, 8 * cg, shift);                    // row 0 of this channel group (same for every block)
+  Row<T, 8>::load(x, 8 * cg, shift);                    // row 0 of this channel group (same for every block)
   float acc[2][8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[0][i] = acc[1][i] = 0.0f;
@@ -126,7 +82,7 @@ __global__ __launch_bounds__(kTailThreads) void tail_stats_kernel(const void* __
   for (; r + 3 * slots_total < rows; r += 4 * slots_total) {       // 4 independent 16-byte loads in flight
     float v[4][8];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) Row8<T>::load(x, (r + u * slots_total) * C + 8 * cg, v[u]);
+    for (int u = 0; u < 4; ++u) Row<T, 8>::load(x, (r + u * slots_total) * C + 8 * cg, v[u]);
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -138,7 +94,7 @@ __global__ __launch_bounds__(kTailThreads) void tail_stats_kernel(const void* __
   }
   for (; r < rows; r += slots_total) {
     float v[8];
-    Row8<T>::load(x, r * C + 8 * cg, v);
+    Row<T, 8>::load(x, r * C + 8 * cg, v);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float d = v[i] - shift[i];
@@ -189,7 +145,7 @@ __global__ __launch_bounds__(kFinalThreads) void tail_stats_final_kernel(const v
       double shift = 0.0;
       if constexpr (kShifted) {
         float first[8];
-        Row8<T>::load(x, ch & ~7, first);
+        Row<T, 8>::load(x, ch & ~7, first);
         shift = static_cast<double>(first[ch & 7]);
       }
       const double m1 = red[tid] / n, m2 = red[tid + 16] / n;
@@ -249,12 +205,12 @@ __global__ __launch_bounds__(kTailThreads) void tail_apply_kernel(const void* __
     float out[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      float z = Row8<T>::round(fmaf(x0[i], a[i], b[i]));
-      if (kPool == 2) z = fmaxf(z, Row8<T>::round(fmaf(x1[i], a[i], b[i])));
-      if (kPool == 3) z = Row8<T>::round(z + x1[i]);
+      float z = Row<T, 8>::round(fmaf(x0[i], a[i], b[i]));
+      if (kPool == 2) z = fmaxf(z, Row<T, 8>::round(fmaf(x1[i], a[i], b[i])));
+      if (kPool == 3) z = Row<T, 8>::round(z + x1[i]);
       out[i] = kPool == 4 ? silu_f(z) : fmaxf(z, 0.0f);     // max(relu(z0), relu(z1)) == relu(max(z0, z1))
     }
-    Row8<T>::store(y, o * C + 8 * cg, out);
+    Row<T, 8>::store(y, o * C + 8 * cg, out);
   };
   long o = slot;
   for (; o + slots_total < out_rows; o += 2 * slots_total) {       // two output rows (4 loads) in flight
@@ -262,18 +218,18 @@ __global__ __launch_bounds__(kTailThreads) void tail_apply_kernel(const void* __
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const long oo = o + u * slots_total;
-      Row8<T>::load(x, (kStride * oo) * C + 8 * cg, x0[u]);
-      if (kPool == 2) Row8<T>::load(x, (kStride * oo + 1) * C + 8 * cg, x1[u]);
-      if (kPool == 3) Row8<T>::load(res, oo * C + 8 * cg, x1[u]);
+      Row<T, 8>::load(x, (kStride * oo) * C + 8 * cg, x0[u]);
+      if (kPool == 2) Row<T, 8>::load(x, (kStride * oo + 1) * C + 8 * cg, x1[u]);
+      if (kPool == 3) Row<T, 8>::load(res, oo * C + 8 * cg, x1[u]);
     }
     one(x0[0], x1[0], o);
     one(x0[1], x1[1], o + slots_total);
   }
   for (; o < out_rows; o += slots_total) {
     float x0[8], x1[8];
-    Row8<T>::load(x, (kStride * o) * C + 8 * cg, x0);
-    if (kPool == 2) Row8<T>::load(x, (kStride * o + 1) * C + 8 * cg, x1);
-    if (kPool == 3) Row8<T>::load(res, o * C + 8 * cg, x1);
+    Row<T, 8>::load(x, (kStride * o) * C + 8 * cg, x0);
+    if (kPool == 2) Row<T, 8>::load(x, (kStride * o + 1) * C + 8 * cg, x1);
+    if (kPool == 3) Row<T, 8>::load(res, o * C + 8 * cg, x1);
     one(x0, x1, o);
   }
 }
@@ -284,10 +240,10 @@ __global__ __launch_bounds__(kTailThreads) void tail_apply_kernel(const void* __
 // and whether the ReLU lets it through.  Returns the receiving element's index (0 / 1) or -1.
 template <typename T, int kPool>
 __device__ __forceinline__ int route(float x0, float x1, float a, float b) {
-  if (kPool == 3) return fmaxf(Row8<T>::round(Row8<T>::round(fmaf(x0, a, b)) + x1), 0.0f) > 0.0f ? 0 : -1;
-  const float r0 = fmaxf(Row8<T>::round(fmaf(x0, a, b)), 0.0f);
+  if (kPool == 3) return fmaxf(Row<T, 8>::round(Row<T, 8>::round(fmaf(x0, a, b)) + x1), 0.0f) > 0.0f ? 0 : -1;
+  const float r0 = fmaxf(Row<T, 8>::round(fmaf(x0, a, b)), 0.0f);
   if (kPool == 1) return r0 > 0.0f ? 0 : -1;
-  const float r1 = fmaxf(Row8<T>::round(fmaf(x1, a, b)), 0.0f);
+  const float r1 = fmaxf(Row<T, 8>::round(fmaf(x1, a, b)), 0.0f);
   const int sel = r1 > r0 ? 1 : 0;
   return (sel ? r1 : r0) > 0.0f ? sel : -1;
 }
@@ -320,7 +276,7 @@ __global__ __launch_bounds__(kTailThreads) void tail_bwd_reduce_kernel(const voi
     for (int i = 0; i < 8; ++i) {
       float dz, xs;
       if (kPool == 4) {
-        dz = g[i] * silu_grad_f(Row8<T>::round(fmaf(x0[i], a[i], b[i])));
+        dz = g[i] * silu_grad_f(Row<T, 8>::round(fmaf(x0[i], a[i], b[i])));
         xs = x0[i];
       } else {
         const int sel = route<T, kPool>(x0[i], x1[i], a[i], b[i]);
@@ -337,20 +293,20 @@ __global__ __launch_bounds__(kTailThreads) void tail_bwd_reduce_kernel(const voi
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const long oo = o + u * slots_total;
-      Row8<T>::load(x, (kStride * oo) * C + 8 * cg, x0[u]);
-      if (kPool == 2) Row8<T>::load(x, (kStride * oo + 1) * C + 8 * cg, x1[u]);
-      if (kPool == 3) Row8<T>::load(res, oo * C + 8 * cg, x1[u]);
-      Row8<T>::load(dy, oo * C + 8 * cg, g[u]);
+      Row<T, 8>::load(x, (kStride * oo) * C + 8 * cg, x0[u]);
+      if (kPool == 2) Row<T, 8>::load(x, (kStride * oo + 1) * C + 8 * cg, x1[u]);
+      if (kPool == 3) Row<T, 8>::load(res, oo * C + 8 * cg, x1[u]);
+      Row<T, 8>::load(dy, oo * C + 8 * cg, g[u]);
     }
     one(x0[0], x1[0], g[0]);
     one(x0[1], x1[1], g[1]);
   }
   for (; o < out_rows; o += slots_total) {
     float x0[8], x1[8], g[8];
-    Row8<T>::load(x, (kStride * o) * C + 8 * cg, x0);
-    if (kPool == 2) Row8<T>::load(x, (kStride * o + 1) * C + 8 * cg, x1);
-    if (kPool == 3) Row8<T>::load(res, o * C + 8 * cg, x1);
-    Row8<T>::load(dy, o * C + 8 * cg, g);
+    Row<T, 8>::load(x, (kStride * o) * C + 8 * cg, x0);
+    if (kPool == 2) Row<T, 8>::load(x, (kStride * o + 1) * C + 8 * cg, x1);
+    if (kPool == 3) Row<T, 8>::load(res, o * C + 8 * cg, x1);
+    Row<T, 8>::load(dy, o * C + 8 * cg, g);
     one(x0, x1, g);
   }
   block_partials<2>(acc, C, partials, lds);
@@ -421,7 +377,7 @@ __global__ __launch_bounds__(kTailThreads) void tail_bwd_apply_kernel(const void
     for (int i = 0; i < 8; ++i) {
       const float base0 = fmaf(q[i], x0[i], p[i]);
       if (kPool == 4) {
-        d0[i] = fmaf(a[i], g[i] * silu_grad_f(Row8<T>::round(fmaf(x0[i], a[i], b[i]))), base0);
+        d0[i] = fmaf(a[i], g[i] * silu_grad_f(Row<T, 8>::round(fmaf(x0[i], a[i], b[i]))), base0);
         continue;
       }
       const int sel = route<T, kPool>(x0[i], x1[i], a[i], b[i]);
@@ -432,9 +388,9 @@ __global__ __launch_bounds__(kTailThreads) void tail_bwd_apply_kernel(const void
       }
       if (kPool == 3) d1[i] = sel == 0 ? g[i] : 0.0f;
     }
-    Row8<T>::store(dx, (kStride * o) * C + 8 * cg, d0);
-    if (kPool == 2) Row8<T>::store(dx, (kStride * o + 1) * C + 8 * cg, d1);
-    if (kPool == 3) Row8<T>::store(dres, o * C + 8 * cg, d1);            // gradient of the residual = masked dy
+    Row<T, 8>::store(dx, (kStride * o) * C + 8 * cg, d0);
+    if (kPool == 2) Row<T, 8>::store(dx, (kStride * o + 1) * C + 8 * cg, d1);
+    if (kPool == 3) Row<T, 8>::store(dres, o * C + 8 * cg, d1);            // gradient of the residual = masked dy
   };
   long o = slot;
   for (; o + slots_total < out_rows; o += 2 * slots_total) {
@@ -442,20 +398,20 @@ __global__ __launch_bounds__(kTailThreads) void tail_bwd_apply_kernel(const void
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const long oo = o + u * slots_total;
-      Row8<T>::load(x, (kStride * oo) * C + 8 * cg, x0[u]);
-      if (kPool == 2) Row8<T>::load(x, (kStride * oo + 1) * C + 8 * cg, x1[u]);
-      if (kPool == 3) Row8<T>::load(res, oo * C + 8 * cg, x1[u]);
-      Row8<T>::load(dy, oo * C + 8 * cg, g[u]);
+      Row<T, 8>::load(x, (kStride * oo) * C + 8 * cg, x0[u]);
+      if (kPool == 2) Row<T, 8>::load(x, (kStride * oo + 1) * C + 8 * cg, x1[u]);
+      if (kPool == 3) Row<T, 8>::load(res, oo * C + 8 * cg, x1[u]);
+      Row<T, 8>::load(dy, oo * C + 8 * cg, g[u]);
     }
     one(x0[0], x1[0], g[0], o);
     one(x0[1], x1[1], g[1], o + slots_total);
   }
   for (; o < out_rows; o += slots_total) {
     float x0[8], x1[8], g[8];
-    Row8<T>::load(x, (kStride * o) * C + 8 * cg, x0);
-    if (kPool == 2) Row8<T>::load(x, (kStride * o + 1) * C + 8 * cg, x1);
-    if (kPool == 3) Row8<T>::load(res, o * C + 8 * cg, x1);
-    Row8<T>::load(dy, o * C + 8 * cg, g);
+    Row<T, 8>::load(x, (kStride * o) * C + 8 * cg, x0);
+    if (kPool == 2) Row<T, 8>::load(x, (kStride * o + 1) * C + 8 * cg, x1);
+    if (kPool == 3) Row<T, 8>::load(res, o * C + 8 * cg, x1);
+    Row<T, 8>::load(dy, o * C + 8 * cg, g);
     one(x0, x1, g, o);
   }
 }

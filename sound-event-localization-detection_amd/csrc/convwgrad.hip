@@ -35,6 +35,7 @@
 #include <hip/hip_bf16.h>
 
 #include "conv3x3_image.h"
+#include "seld_bf16.h"
 #include "seld_common.h"
 
 namespace seld {
@@ -234,15 +235,9 @@ __global__ __launch_bounds__(kWgSumThreads) void conv3x3_wgrad_sum_kernel(const 
     const float4 v = part[r][col];
     s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
   }
-  if (kBf16) {
-    const unsigned lo = static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(s.x))) |
-                        (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(s.y))) << 16);
-    const unsigned hi = static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(s.z))) |
-                        (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(s.w))) << 16);
-    *reinterpret_cast<uint2*>(static_cast<unsigned short*>(dw) + i) = make_uint2(lo, hi);
-  } else {
-    *reinterpret_cast<float4*>(static_cast<float*>(dw) + i) = s;
-  }
+  const float out[4] = {s.x, s.y, s.z, s.w};
+  if (kBf16) Row<__hip_bfloat16, 4>::store(dw, i, out);
+  else Row<float, 4>::store(dw, i, out);
 }
 
 struct WgradPlan {

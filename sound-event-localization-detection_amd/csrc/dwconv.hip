@@ -10,50 +10,12 @@
 // latency-sized (a few microseconds).  Backward data = the same kernel with the taps flipped; backward weight = one
 // block per (batch row, 64 channels, 50 time steps) that slides an 8-tap register window over its LDS-staged chunk
 // (fp32 partials per block, summed by the caller: deterministic).
-#include <hip/hip_bf16.h>
-
+#include "seld_bf16.h"
 #include "seld_common.h"
 
 namespace seld {
 
 constexpr int kDwMaxTaps = 32;
-
-template <typename T> struct Dw8;
-template <> struct Dw8<__hip_bfloat16> {
-  static __device__ __forceinline__ void load(const void* p, long e, float (&f)[8]) {
-    const uint4 v = *reinterpret_cast<const uint4*>(static_cast<const unsigned short*>(p) + e);
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __uint_as_float(w[i] << 16);
-      f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ void store(void* p, long e, const float (&f)[8]) {
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      w[i] = static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(f[2 * i]))) |
-             (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(f[2 * i + 1]))) << 16);
-    *reinterpret_cast<uint4*>(static_cast<unsigned short*>(p) + e) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-  static __device__ __forceinline__ float load1(const void* p, long e) {
-    return __uint_as_float(static_cast<unsigned>(static_cast<const unsigned short*>(p)[e]) << 16);
-  }
-};
-template <> struct Dw8<float> {
-  static __device__ __forceinline__ void load(const void* p, long e, float (&f)[8]) {
-    const float4* q = reinterpret_cast<const float4*>(static_cast<const float*>(p) + e);
-    const float4 a = q[0], b = q[1];
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-  }
-  static __device__ __forceinline__ void store(void* p, long e, const float (&f)[8]) {
-    float4* q = reinterpret_cast<float4*>(static_cast<float*>(p) + e);
-    q[0] = make_float4(f[0], f[1], f[2], f[3]);
-    q[1] = make_float4(f[4], f[5], f[6], f[7]);
-  }
-  static __device__ __forceinline__ float load1(const void* p, long e) { return static_cast<const float*>(p)[e]; }
-};
 
 // y[b][t][d] = bias[d] + sum_k w[d][k] x[b][t + k - pad][d]   (flip: w[d][K-1-k], the data gradient)
 // grid (ceil(T / 32), D / 64, B), 256 threads = 32 time steps x 8 channel groups of 8.
@@ -80,7 +42,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const void* __restrict__ x,
     const int ti = t + k - pad;
     if (ti < 0 || ti >= Tn) continue;
     float xv[8];
-    Dw8<T>::load(x, (row0 + ti) * D + d0 + 8 * cg, xv);
+    Row<T, 8>::load(x, (row0 + ti) * D + d0 + 8 * cg, xv);
     const float4 w0 = *reinterpret_cast<const float4*>(&wl[k][8 * cg]);
     const float4 w1 = *reinterpret_cast<const float4*>(&wl[k][8 * cg + 4]);
     acc[0] = fmaf(w0.x, xv[0], acc[0]); acc[1] = fmaf(w0.y, xv[1], acc[1]);
@@ -88,7 +50,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const void* __restrict__ x,
     acc[4] = fmaf(w1.x, xv[4], acc[4]); acc[5] = fmaf(w1.y, xv[5], acc[5]);
     acc[6] = fmaf(w1.z, xv[6], acc[6]); acc[7] = fmaf(w1.w, xv[7], acc[7]);
   }
-  Dw8<T>::store(y, (row0 + t) * D + d0 + 8 * cg, acc);
+  Row<T, 8>::store(y, (row0 + t) * D + d0 + 8 * cg, acc);
 }
 
 // dw_partial[row][d][k] = sum_{t in chunk} dy[b][t][d] x[b][t + k - pad][d]  (k < K);  slot 31 = sum_t dy (bias);
@@ -115,7 +77,7 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const void* __restric
     const int r = i >> 3, cg = i & 7;
     const int ti = t0 - pad + r;
     float v[8];
-    if (r < len + 2 * pad && ti >= 0 && ti < Tn) Dw8<T>::load(x, (row0 + ti) * D + d0 + 8 * cg, v);
+    if (r < len + 2 * pad && ti >= 0 && ti < Tn) Row<T, 8>::load(x, (row0 + ti) * D + d0 + 8 * cg, v);
     else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = 0.0f;
@@ -126,7 +88,7 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const void* __restric
   for (int i = tid; i < kDwChunk * 8; i += 256) {
     const int r = i >> 3, cg = i & 7;
     float v[8];
-    if (r < len) Dw8<T>::load(dy, (row0 + t0 + r) * D + d0 + 8 * cg, v);
+    if (r < len) Row<T, 8>::load(dy, (row0 + t0 + r) * D + d0 + 8 * cg, v);
     else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = 0.0f;

@@ -9,8 +9,7 @@
 //
 // Reference lines they serve: nn.GRU's bias handling (model_crnn.py:65-72), the Linear / GRU weight gradients autograd
 // computes for trainer.py:178, the data gradient of the encoder's 3x3 convolutions (model_crnn.py:5-17).
-#include <hip/hip_bf16.h>
-
+#include "seld_bf16.h"
 #include "seld_common.h"
 
 namespace seld {
@@ -20,11 +19,10 @@ namespace {
 constexpr int kGlueThreads = 256;
 
 __device__ __forceinline__ float load_as_float(const void* p, long i, bool bf16) {
-  return bf16 ? __uint_as_float(static_cast<unsigned>(static_cast<const unsigned short*>(p)[i]) << 16)
-              : static_cast<const float*>(p)[i];
+  return bf16 ? bf16_lo(static_cast<const unsigned short*>(p)[i]) : static_cast<const float*>(p)[i];
 }
 __device__ __forceinline__ void store_from_float(void* p, long i, bool bf16, float v) {
-  if (bf16) static_cast<unsigned short*>(p)[i] = __bfloat16_as_ushort(__float2bfloat16(v));
+  if (bf16) static_cast<unsigned short*>(p)[i] = bf16_bits(v);
   else static_cast<float*>(p)[i] = v;
 }
 
@@ -69,7 +67,7 @@ __global__ __launch_bounds__(kGlueThreads) void gru_prepare_kernel(const float* 
   for (int y = y0; y < 32; y += kGlueThreads / 32) {
     const long src = in0 + static_cast<long>(r0 + y) * h + k0 + x;
     tile[y][x] = w_bf16 ? static_cast<const unsigned short*>(w_hh)[src]
-                        : __bfloat16_as_ushort(__float2bfloat16(static_cast<const float*>(w_hh)[src]));
+                        : bf16_bits(static_cast<const float*>(w_hh)[src]);
   }
   __syncthreads();
 #pragma unroll
@@ -176,8 +174,7 @@ __global__ __launch_bounds__(kGlueThreads) void sum_chunks_columns_kernel(const 
 #pragma unroll
     for (int k = 0; k < 4 * F; ++k) {
       const int e0 = 2 * k, e1 = 2 * k + 1;
-      packed[k] = static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(acc[e0 % F][e0 / F]))) |
-                  (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(acc[e1 % F][e1 / F]))) << 16);
+      packed[k] = pack_bf16x2(acc[e0 % F][e0 / F], acc[e1 % F][e1 / F]);
     }
     uint4* dst = reinterpret_cast<uint4*>(static_cast<unsigned short*>(out) + o0);
 #pragma unroll

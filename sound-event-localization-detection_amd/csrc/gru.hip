@@ -35,6 +35,7 @@
 #include <hip/hip_bf16.h>
 #include <stdlib.h>
 
+#include "seld_bf16.h"
 #include "seld_common.h"
 
 #ifndef SELD_GRU_SEQS
@@ -117,10 +118,6 @@ template <> struct alignas(16) Raw<32> { unsigned w[8]; };
 
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-  return static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(lo))) |
-         (static_cast<unsigned>(__bfloat16_as_ushort(__float2bfloat16(hi))) << 16);
-}
 __device__ __forceinline__ unsigned pack_f16x2(float lo, float hi) {
   const f32x2 v = {lo, hi};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));            // round to nearest even
@@ -146,8 +143,8 @@ struct AsBF16 {      // bf16 build: streamed data (gi, dy, dg, y)
   template <int N> static __device__ __forceinline__ void dec(const unsigned* w, float (&f)[N]) {
 #pragma unroll
     for (int k = 0; k < N / 2; ++k) {
-      f[2 * k] = __uint_as_float(w[k] << 16);
-      f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
+      f[2 * k] = bf16_lo(w[k]);
+      f[2 * k + 1] = bf16_hi(w[k]);
     }
   }
 };

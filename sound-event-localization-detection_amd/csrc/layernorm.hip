@@ -13,8 +13,7 @@
 // d(weight), d(bias) in registers; the 4 wavefronts of a block add theirs through LDS and write one partial row per
 // block, a second kernel adds the partial rows in a fixed order (deterministic, no atomics; all loads of a thread in
 // flight at once: a serial walk over 512 partial rows cost 42 us, more than everything this file replaces).
-#include <hip/hip_bf16.h>
-
+#include "seld_bf16.h"
 #include "seld_common.h"
 
 namespace seld {
@@ -23,59 +22,6 @@ namespace {
 
 constexpr int kLnWaves = 4;           // wavefronts (rows in flight) per block
 constexpr int kLnMaxBlocks = 512;     // backward: partial rows of the column sums
-
-template <typename T, int V> struct RowIo;
-
-template <int V> struct RowIo<__hip_bfloat16, V> {
-  static_assert(V == 4 || V == 8, "8- or 16-byte pieces");
-  __device__ static void load(const void* base, long index, float (&v)[V]) {
-    if (V == 8) {
-      const uint4 r = static_cast<const uint4*>(base)[index];
-      const unsigned w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        v[2 * i] = __uint_as_float(w[i] << 16);
-        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-      }
-    } else {
-      const uint2 r = static_cast<const uint2*>(base)[index];
-      v[0] = __uint_as_float(r.x << 16);
-      v[1] = __uint_as_float(r.x & 0xffff0000u);
-      v[2] = __uint_as_float(r.y << 16);
-      v[3] = __uint_as_float(r.y & 0xffff0000u);
-    }
-  }
-  __device__ static unsigned pack(float lo, float hi) {
-    const __hip_bfloat16 a = __float2bfloat16(lo), b = __float2bfloat16(hi);      // round to nearest even
-    return static_cast<unsigned>(*reinterpret_cast<const unsigned short*>(&a)) |
-           (static_cast<unsigned>(*reinterpret_cast<const unsigned short*>(&b)) << 16);
-  }
-  __device__ static void store(void* base, long index, const float (&v)[V]) {
-    if (V == 8) {
-      static_cast<uint4*>(base)[index] = make_uint4(pack(v[0], v[1]), pack(v[2], v[3]), pack(v[4], v[5]), pack(v[6], v[7]));
-    } else {
-      static_cast<uint2*>(base)[index] = make_uint2(pack(v[0], v[1]), pack(v[2], v[3]));
-    }
-  }
-};
-
-template <int V> struct RowIo<float, V> {
-  __device__ static void load(const void* base, long index, float (&v)[V]) {
-#pragma unroll
-    for (int i = 0; i < V / 4; ++i) {
-      const float4 r = static_cast<const float4*>(base)[index * (V / 4) + i];
-      v[4 * i] = r.x;
-      v[4 * i + 1] = r.y;
-      v[4 * i + 2] = r.z;
-      v[4 * i + 3] = r.w;
-    }
-  }
-  __device__ static void store(void* base, long index, const float (&v)[V]) {
-#pragma unroll
-    for (int i = 0; i < V / 4; ++i)
-      static_cast<float4*>(base)[index * (V / 4) + i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-  }
-};
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -98,7 +44,7 @@ __global__ __launch_bounds__(64 * kLnWaves) void layernorm_forward_kernel(const 
   float s = 0.0f;
 #pragma unroll
   for (int c = 0; c < kChunks; ++c) {
-    RowIo<T, V>::load(x, row * (kD / V) + c * 64 + lane, v[c]);
+    Row<T, V>::load(x, row * kD + (c * 64 + lane) * V, v[c]);
 #pragma unroll
     for (int j = 0; j < V; ++j) s += v[c][j];
   }
@@ -115,14 +61,14 @@ __global__ __launch_bounds__(64 * kLnWaves) void layernorm_forward_kernel(const 
 #pragma unroll
   for (int c = 0; c < kChunks; ++c) {
     float w[V], b[V], o[V];
-    RowIo<float, V>::load(weight, c * 64 + lane, w);
-    RowIo<float, V>::load(bias, c * 64 + lane, b);
+    Row<float, V>::load(weight, (c * 64 + lane) * V, w);
+    Row<float, V>::load(bias, (c * 64 + lane) * V, b);
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       const float z = fmaf((v[c][j] - mean) * rstd, w[j], b[j]);
       o[j] = kRelu ? fmaxf(z, 0.0f) : z;
     }
-    RowIo<T, V>::store(y, row * (kD / V) + c * 64 + lane, o);
+    Row<T, V>::store(y, row * kD + (c * 64 + lane) * V, o);
   }
   if (lane == 0) mean_rstd[row] = make_float2(mean, rstd);
 }
@@ -143,8 +89,8 @@ __global__ __launch_bounds__(64 * kLnWaves) void layernorm_backward_kernel(const
   float w[kChunks][V], b[kChunks][V], dw[kChunks][V], db[kChunks][V];
 #pragma unroll
   for (int c = 0; c < kChunks; ++c) {
-    RowIo<float, V>::load(weight, c * 64 + lane, w[c]);
-    if (kRelu) RowIo<float, V>::load(bias, c * 64 + lane, b[c]);
+    Row<float, V>::load(weight, (c * 64 + lane) * V, w[c]);
+    if (kRelu) Row<float, V>::load(bias, (c * 64 + lane) * V, b[c]);
 #pragma unroll
     for (int j = 0; j < V; ++j) dw[c][j] = db[c][j] = 0.0f;
   }
@@ -155,8 +101,8 @@ __global__ __launch_bounds__(64 * kLnWaves) void layernorm_backward_kernel(const
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
     for (int c = 0; c < kChunks; ++c) {
-      RowIo<T, V>::load(x, row * (kD / V) + c * 64 + lane, xh[c]);
-      RowIo<T, V>::load(dy, row * (kD / V) + c * 64 + lane, g[c]);
+      Row<T, V>::load(x, row * kD + (c * 64 + lane) * V, xh[c]);
+      Row<T, V>::load(dy, row * kD + (c * 64 + lane) * V, g[c]);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         xh[c][j] = (xh[c][j] - st.x) * st.y;
@@ -174,15 +120,15 @@ __global__ __launch_bounds__(64 * kLnWaves) void layernorm_backward_kernel(const
       float o[V];
 #pragma unroll
       for (int j = 0; j < V; ++j) o[j] = st.y * (g[c][j] * w[c][j] - c1 - xh[c][j] * c2);
-      RowIo<T, V>::store(dx, row * (kD / V) + c * 64 + lane, o);
+      Row<T, V>::store(dx, row * kD + (c * 64 + lane) * V, o);
     }
   }
   // the block's column sums: wavefronts 1..3 hand theirs to wavefront 0 through LDS
   if (wave > 0) {
 #pragma unroll
     for (int c = 0; c < kChunks; ++c) {
-      RowIo<float, V>::store(fold[wave - 1][0], c * 64 + lane, dw[c]);
-      RowIo<float, V>::store(fold[wave - 1][1], c * 64 + lane, db[c]);
+      Row<float, V>::store(fold[wave - 1][0], (c * 64 + lane) * V, dw[c]);
+      Row<float, V>::store(fold[wave - 1][1], (c * 64 + lane) * V, db[c]);
     }
   }
   __syncthreads();
@@ -192,8 +138,8 @@ __global__ __launch_bounds__(64 * kLnWaves) void layernorm_backward_kernel(const
 #pragma unroll
       for (int k = 0; k < kLnWaves - 1; ++k) {
         float t[V], u[V];
-        RowIo<float, V>::load(fold[k][0], c * 64 + lane, t);
-        RowIo<float, V>::load(fold[k][1], c * 64 + lane, u);
+        Row<float, V>::load(fold[k][0], (c * 64 + lane) * V, t);
+        Row<float, V>::load(fold[k][1], (c * 64 + lane) * V, u);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
           dw[c][j] += t[j];
@@ -201,8 +147,8 @@ __global__ __launch_bounds__(64 * kLnWaves) void layernorm_backward_kernel(const
         }
       }
       float* out = partial + static_cast<long>(blockIdx.x) * 2 * kD;
-      RowIo<float, V>::store(out, c * 64 + lane, dw[c]);
-      RowIo<float, V>::store(out + kD, c * 64 + lane, db[c]);
+      Row<float, V>::store(out, (c * 64 + lane) * V, dw[c]);
+      Row<float, V>::store(out + kD, (c * 64 + lane) * V, db[c]);
     }
   }
 }

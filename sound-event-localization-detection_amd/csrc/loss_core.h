@@ -4,11 +4,10 @@
 // the cell write is each kernel's own.
 #pragma once
 
-#include <hip/hip_bf16.h>
-
 #include <string>
 #include <type_traits>
 
+#include "seld_bf16.h"
 #include "seld_common.h"
 
 namespace seld {
@@ -16,14 +15,6 @@ namespace seld {
 constexpr int kLossBlock = 256;            // threads per block = cells per tile
 constexpr int kLossClasses = 14;           // config.py:40
 constexpr int kLossMaxPartials = 4096;     // blocks of a main kernel = double partials per sum
-
-__device__ __forceinline__ unsigned short float_to_bf16_bits(float f) {
-  return __bfloat16_as_ushort(__float2bfloat16(f));   // v_cvt_pk_bf16_f32: RNE, NaN stays NaN
-}
-
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-  return float_to_bf16_bits(lo) | (static_cast<unsigned>(float_to_bf16_bits(hi)) << 16);
-}
 
 // ---- the tile extent ------------------------------------------------------------------------------------------------------
 // All index arithmetic is 32-bit on purpose (the host checks n_cells * 14 < 2^31).  With 64-bit extents hipcc

@@ -45,6 +45,7 @@ def _declare(lib):
     lib.seld_last_error.restype = ctypes.c_char_p
     lib.seld_last_error.argtypes = []
     lib.seld_version.restype = _int
+    lib.seld_version.argtypes = []
     lib.seld_init.argtypes = [_int]
     lib.seld_shutdown.argtypes = []
     lib.seld_set_mel_filterbank.argtypes = [_ptr]
@@ -67,6 +68,7 @@ def _declare(lib):
     for fn in (lib.seld_logmel_phasors_f32, lib.seld_logmel_phasors_i16):
         fn.argtypes = [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr]
     lib.seld_phasor_pitch.restype = ctypes.c_int64
+    lib.seld_phasor_pitch.argtypes = []
     lib.seld_gcc_phat_q15.argtypes = [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _ptr]
     lib.seld_gcc_table_host.argtypes = [_ptr]
     lib.seld_gcc_phat.argtypes = [_ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _i64, _ptr]

@@ -54,7 +54,7 @@ def test_python_binding_declares_the_same_entry_points(native_lib):
     import seld_native
     lib = seld_native.load_library()
     for name in declared_symbols():
-        assert getattr(lib, name) is not None
+        assert getattr(lib, name).argtypes is not None, f"seld_native._declare sets no argtypes for {name}"
 
 
 def test_product_path_has_no_cpu_fallback():
