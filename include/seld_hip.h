@@ -957,6 +957,30 @@ int seld_resample_f32(const float* pcm, int64_t N, int64_t C, int64_t L, const f
 int seld_resample_i16(const int16_t* pcm, int64_t N, int64_t C, int64_t L, const float* table_dev, int up, int down, int taps,
                       int half, float* out, int64_t L_out, void* stream);
 
+/* ---- per-window class statistics for class-balanced window sampling (csrc/balance.hip) ---------
+ * No reference counterpart (main.py:60-74 shuffles uniformly).  mask is the label timeline of seld_labels_rasterise laid
+ * end to end: uint16 [total_rows][cells], bit c of a word = class c active in that cell.  Integer work: both results are
+ * the same bits on every grid and device.  No allocation, no synchronisation, no atomics.
+ *
+ * seld_frame_class_mask:  frame_mask[t] = bitwise OR over the `cells` words of row t, t = 0 .. total_rows - 1.  The
+ * timeline is read once, in 16-byte chunks: mask 16-byte aligned and cells a multiple of 8 (at most 2048), else -4; a
+ * timeline too long for 32-bit row indices: -4.  A null pointer, total_rows < 1 or cells < 1: -1.
+ *
+ * seld_window_class_frames:  counts int32 [n_windows][SELD_BALANCE_COLUMNS]; window w covers the frames
+ * [w * hop, min(w * hop + window, total_rows)) and
+ *   counts[w][c], c < num_classes:          frames of the window whose frame_mask has bit c set;
+ *   counts[w][c], num_classes <= c < 14:    0;
+ *   counts[w][14]:                          frames with any of the bits 0 .. num_classes - 1 set;
+ *   counts[w][15]:                          frames of the window inside the timeline (tail windows are short).
+ * Bits at or above num_classes are ignored.  A null pointer, total_rows / window / hop / n_windows < 1, num_classes
+ * outside 1..SELD_BALANCE_MAX_CLASSES, or a last window that starts behind the end ((n_windows - 1) * hop >=
+ * total_rows): -1.  window above 2^31 - 65 or n_windows above 2^31 - 1: -4.  Every refusal comes before any launch. */
+#define SELD_BALANCE_COLUMNS 16
+#define SELD_BALANCE_MAX_CLASSES 14
+int seld_frame_class_mask(const uint16_t* mask, int64_t total_rows, int cells, uint16_t* frame_mask, void* stream);
+int seld_window_class_frames(const uint16_t* frame_mask, int64_t total_rows, int64_t window, int64_t hop, int64_t n_windows,
+                             int num_classes, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -211,6 +211,20 @@ class Config:
                                 # 'feature_statistics'; test_model / evaluate_seld / infer.py apply a checkpoint's statistics
                                 # whenever it holds them (with the switch on and none in the checkpoint: an error).  Needs
                                 # DEVICE_FEED like the augmentation switches (the host DataLoader path refuses to run)
+    # Class-balanced window sampling of the training feed (seld_balance.py, csrc/balance.hip).  Off by
+    # default: every entry point, epoch order, checkpoint and benchmark figure is then what it was
+    BALANCED_SAMPLING = False   # the training feed draws each epoch's len(dataset) windows WITH replacement, weighted by the
+                                # classes each window holds (reduced once from the device-resident label mask); epoch length,
+                                # steps per epoch and the LR schedule do not move.  Evaluation, test_model, infer.py and the
+                                # test loader are untouched.  Needs DEVICE_FEED like the augmentation switches (the host
+                                # DataLoader path refuses to run); every rank reproduces the same order from (SEED, epoch)
+    BALANCE_POWER = 1.0         # beta in [0, 1]: an active window weighs max over its classes of (windows holding the
+                                # class)^-beta.  0 = all active windows alike (only the silent share is controlled), 1 = a
+                                # window is weighted by its rarest class (classes that never share a window are then expected
+                                # in equally many drawn windows)
+    BALANCE_SILENT_SHARE = None # expected share of the draws that go to windows without any class, in [0, 1): None = their
+                                # natural share, 0 = never drawn
+    BALANCE_MIN_FRAMES = 5      # a class is present in a window from this many 20 ms frames on (5 = one 100 ms label frame)
     # Guarded optimiser update (csrc/guard.hip, csrc/adam.hip).  All off by default; device-side, inside
     # the one-launch update, so they need the master-weight path (bf16 autocast on a ROCm device): make_optimizer refuses
     # a switched-on guard anywhere else

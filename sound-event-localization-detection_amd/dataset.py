@@ -443,6 +443,7 @@ class SELDDataset(Dataset):
         self._feature_statistics = None          # statistics of THIS timeline (feature_statistics), computed once
         self.feature_stats = None                # the statistics device_batch applies (set_feature_statistics), or None
         self._feature_scale = self._feature_shift = None
+        self._window_class_counts = None         # window_class_counts, computed once
 
     # -- per-bin standardisation (Config.STANDARDISE_FEATURES; seld_standardise.py) ---------
     def feature_statistics(self):
@@ -475,6 +476,22 @@ class SELDDataset(Dataset):
         self.feature_stats = stats
         self._feature_scale = stats["scale"].to(self.spec_tm.device).contiguous()
         self._feature_shift = stats["shift"].to(self.spec_tm.device).contiguous()
+
+    # -- per-window class statistics (Config.BALANCED_SAMPLING; seld_balance.py) -------------
+    def window_class_counts(self):
+        """int32 [len(self), 16] on the host (numpy): for every window, column c < num_classes = its frames in which class c
+        is active somewhere on the grid, column 14 = its frames with any class active, column 15 = its frames inside the
+        timeline (tail windows are short).  Reduced from the device-resident label mask by the two kernels of
+        csrc/balance.hip -- one pass over ``mask_tm`` -- once, then cached."""
+        if getattr(self, "_window_class_counts", None) is None:
+            if self.mask_tm is None:
+                raise RuntimeError("window_class_counts needs the device timeline (keep_on_device=True): the label mask is "
+                                   "reduced on the GPU, there is no CPU fallback")
+            frame_mask = seld_native.frame_class_mask(self.mask_tm)
+            counts = seld_native.window_class_frames(frame_mask, self.window_length_frames, self.hop_length_frames,
+                                                     len(self.window_starts), self.num_classes)
+            self._window_class_counts = counts.cpu().numpy()
+        return self._window_class_counts
 
     # -- reference-shaped views ---------------------------------------------------------------
     @property

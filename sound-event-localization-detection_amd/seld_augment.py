@@ -471,8 +471,22 @@ def check_tta(patterns, feature_set: str, n_channels: int, array=None):
             f"array's geometry is unknown here, so no channel swap is defined")
 
 
+def _stream_keys(idx, keys) -> np.ndarray:
+    """The per-window generator keys of the three draws: the window indices themselves, or ``keys`` -- one integer per
+    window, what a feed that holds a window several times per epoch hands over (class-balanced sampling, DESIGN.md section
+    28: each draw's position in the epoch's global order)."""
+    if keys is None:
+        return idx
+    keys = np.asarray(keys, dtype=np.int64).reshape(-1)
+    if len(keys) != len(idx):
+        raise ValueError(f"keys must hold one integer per window: {len(keys)} for {len(idx)} windows")
+    if len(keys) and int(keys.min()) < 0:
+        raise ValueError("keys must not be negative")
+    return keys
+
+
 def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, bins: int = N_BINS,
-         steps: int | None = None, array=None) -> np.ndarray:
+         steps: int | None = None, array=None, keys=None) -> np.ndarray:
     """int32 [B, 12] parameter rows for the windows ``window_indices`` (dataset window indices) of ``epoch``.
 
     A window's row is a function of (seed, epoch, window index) and the switches ONLY -- not of the rank, the batch size
@@ -486,7 +500,10 @@ def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, 
 
     With Config.MIC_POSITIONS (a microphone array) AUGMENT_SPATIAL draws uniformly among the array's
     valid patterns, ``valid[rng.integers(0, len(valid))]``; with it None the generator is asked exactly what it was asked
-    before arrays existed.  ``array``: the positions to draw for in place of the Config's (a feed hands over its dataset's)."""
+    before arrays existed.  ``array``: the positions to draw for in place of the Config's (a feed hands over its dataset's).
+
+    ``keys``: None, or one integer per window that takes the window index's place in the generator's key (``_stream_keys``);
+    left out, the rows are what they were before the argument existed."""
     s = check_settings(cfg, array=array)
     array = _array_of(cfg, array)
     valid = mic_valid_patterns(array) if array is not None and s["spatial"] else None
@@ -498,7 +515,7 @@ def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, 
     rows = identity_rows(len(idx))
     if not (s["spatial"] or s["rotate"] or s["time_masks"] or s["freq_masks"]):
         return rows
-    for r, i in enumerate(idx):
+    for r, i in enumerate(_stream_keys(idx, keys)):
         rng = np.random.default_rng([int(seed), int(epoch), int(i)])
         if s["rotate"]:
             rows[r, 0] = (int(rng.integers(0, 2)) << 3) | int(rng.integers(0, 2))
@@ -516,7 +533,7 @@ def draw(seed: int, epoch: int, window_indices, cfg, window: int | None = None, 
     return rows
 
 
-def draw_mix(seed: int, epoch: int, window_indices, cfg, n_windows: int):
+def draw_mix(seed: int, epoch: int, window_indices, cfg, n_windows: int, keys=None):
     """The partners of the windows ``window_indices`` of ``epoch`` for the mixing gathers (csrc/mix.hip):
     (partner int64 [B]: a dataset window index, -1 = none; pattern_b int32 [B]: the partner's spatial pattern;
     gain float32 [B]: its linear power gain, 0 = none).
@@ -526,7 +543,8 @@ def draw_mix(seed: int, epoch: int, window_indices, cfg, n_windows: int):
     u < AUGMENT_MIX_PROB), the partner uniform over the ``n_windows`` windows of the dataset, its pattern uniform over the 16
     (used only with AUGMENT_SPATIAL, else 0), its level uniform in +-AUGMENT_MIX_GAIN_DB dB; the gain is 10^(dB / 10)
     evaluated in double precision and rounded once.  Like a parameter row the triple is a function of (seed, epoch, window
-    index) only: N ranks see the mixtures of one rank, a wrap-padded repeat gets the same partner."""
+    index) only: N ranks see the mixtures of one rank, a wrap-padded repeat gets the same partner.  ``keys``: as in ``draw``
+    (the key replaces the index in the generator's key; the partner stays uniform over all ``n_windows`` windows)."""
     s = check_settings(cfg)
     idx = np.asarray(window_indices, dtype=np.int64).reshape(-1)
     partner = np.full(len(idx), -1, dtype=np.int64)
@@ -536,7 +554,7 @@ def draw_mix(seed: int, epoch: int, window_indices, cfg, n_windows: int):
         return partner, pattern, gain
     if int(n_windows) <= 0:
         raise ValueError("draw_mix: the dataset has no windows to draw a partner from")
-    for r, i in enumerate(idx):
+    for r, i in enumerate(_stream_keys(idx, keys)):
         rng = np.random.default_rng([int(seed), int(epoch), int(i), 1])
         u = rng.random()
         other = int(rng.integers(0, int(n_windows)))
@@ -577,7 +595,7 @@ def filter_curve(rng, s, bins: int = N_BINS) -> np.ndarray:
     return gains[k] + (gains[k + 1] - gains[k]) * (f - edges[k]) / (edges[k + 1] - edges[k]).astype(np.float64)
 
 
-def draw_spectral(seed: int, epoch: int, window_indices, cfg, window: int | None = None, bins: int = N_BINS):
+def draw_spectral(seed: int, epoch: int, window_indices, cfg, window: int | None = None, bins: int = N_BINS, keys=None):
     """(rows int32 [B, 12], curves float32 [B, 64] or None) of the in-place spectral stage (csrc/spectral.hip, DESIGN.md
     section 26) for the windows ``window_indices`` of ``epoch``: row = [0] frequency shift, [1] flags (bit 0: the window has a
     curve), [2..5] / [6..9] two cutouts (first frame, frames, first bin, bins).  ``curves`` is None when no window has one.
@@ -589,7 +607,8 @@ def draw_spectral(seed: int, epoch: int, window_indices, cfg, window: int | None
     frames (uniform integer in [0, min(AUGMENT_CUTOUT_TIME_MAX, window)]), first frame (uniform over the positions that
     fit), bins and first bin likewise, then u (a filter iff u < AUGMENT_FILTER_PROB) and, only with a filter, its
     variable-length part (``filter_curve``).  So switching one component on never changes another's draw.  The curve of a
-    window is level + filter, evaluated in double precision and rounded once; the flag is clear when both are off for it."""
+    window is level + filter, evaluated in double precision and rounded once; the flag is clear when both are off for it.
+    ``keys``: as in ``draw``."""
     s = check_settings(cfg)
     if window is None:
         window = int(int(cfg.WINDOW_LENGTH) / int(cfg.SPECTROGRAM_HOP_LENGTH))
@@ -599,7 +618,7 @@ def draw_spectral(seed: int, epoch: int, window_indices, cfg, window: int | None
     curves = np.zeros((len(idx), bins), dtype=np.float32)
     if not spectral_enabled(cfg):
         return rows, None
-    for r, i in enumerate(idx):
+    for r, i in enumerate(_stream_keys(idx, keys)):
         rng = np.random.default_rng([int(seed), int(epoch), int(i), 2])
         rows[r, 0] = _uniform_int(rng.random(), 2 * s["freq_shift_max"] + 1) - s["freq_shift_max"]
         level = (2.0 * rng.random() - 1.0) * s["level_db"]

@@ -209,6 +209,8 @@ def _declare(lib):
     lib.seld_resample_table_host.argtypes = [_i64, _i64, _ptr, _ptr]
     for fn in (lib.seld_resample_f32, lib.seld_resample_i16):
         fn.argtypes = [_ptr, _i64, _i64, _i64, _ptr, _int, _int, _int, _int, _ptr, _i64, _ptr]
+    lib.seld_frame_class_mask.argtypes = [_ptr, _i64, _int, _ptr, _ptr]
+    lib.seld_window_class_frames.argtypes = [_ptr, _i64, _i64, _i64, _i64, _int, _ptr, _ptr]
     return lib
 
 
@@ -615,6 +617,49 @@ def feature_moments(spec_tm: torch.Tensor) -> torch.Tensor:
         check(lib.seld_feature_moments(_p(spec_tm), frames, channels, _p(moments), _p(workspace), nbytes,
                                        _stream_ptr(spec_tm.device)), "seld_feature_moments")
     return moments
+
+
+BALANCE_COLUMNS = 16              # SELD_BALANCE_COLUMNS: classes 0..13, frames with any class, frames inside the timeline
+BALANCE_MAX_CLASSES = 14          # SELD_BALANCE_MAX_CLASSES
+
+
+def frame_class_mask(mask_tm: torch.Tensor) -> torch.Tensor:
+    """The classes active anywhere on the grid, per frame: uint16 [T] on the device, the bitwise OR over the cells of every
+    row of the label timeline mask_tm [T, cells] (uint16, on the GPU, cells a multiple of 8).  The timeline is read once
+    (csrc/balance.hip)."""
+    if not (isinstance(mask_tm, torch.Tensor) and mask_tm.is_cuda and mask_tm.dtype == torch.uint16 and mask_tm.dim() == 2):
+        raise SeldNativeError("frame_class_mask: mask_tm must be a uint16 GPU tensor [T, cells]")
+    if mask_tm.shape[0] == 0 or mask_tm.shape[1] == 0:
+        raise ValueError("frame_class_mask: empty timeline")
+    mask_tm = mask_tm.contiguous()
+    if mask_tm.shape[1] % 8 != 0 or mask_tm.shape[1] > 2048:
+        raise SeldNativeError(f"frame_class_mask: cells must be a multiple of 8, at most 2048 (rows are read in 16-byte chunks), "
+                              f"got {mask_tm.shape[1]}")
+    if mask_tm.data_ptr() % 16 != 0:                 # the entry point wants 16-byte alignment (-4 otherwise): a view that
+        mask_tm = mask_tm.clone()                    # starts off it inside its allocation is copied to a fresh one
+    index = ensure_init(mask_tm.device)
+    with _device_guard(index):
+        out = torch.empty((mask_tm.shape[0],), dtype=torch.uint16, device=mask_tm.device)
+        check(load_library().seld_frame_class_mask(_p(mask_tm), int(mask_tm.shape[0]), int(mask_tm.shape[1]), _p(out),
+                                                   _stream_ptr(mask_tm.device)), "seld_frame_class_mask")
+    return out
+
+
+def window_class_frames(frame_mask: torch.Tensor, window: int, hop: int, n_windows: int, num_classes: int) -> torch.Tensor:
+    """int32 [n_windows, 16] on the device from the per-frame class words of ``frame_class_mask``: for window w, covering
+    the frames [w hop, min(w hop + window, T)), column c < num_classes = frames with class c active, column 14 = frames
+    with any of them active, column 15 = frames inside the timeline (csrc/balance.hip)."""
+    if not (isinstance(frame_mask, torch.Tensor) and frame_mask.is_cuda and frame_mask.dtype == torch.uint16
+            and frame_mask.dim() == 1):
+        raise SeldNativeError("window_class_frames: frame_mask must be a uint16 GPU tensor [T]")
+    frame_mask = frame_mask.contiguous()
+    index = ensure_init(frame_mask.device)
+    with _device_guard(index):
+        out = torch.empty((max(int(n_windows), 0), BALANCE_COLUMNS), dtype=torch.int32, device=frame_mask.device)
+        check(load_library().seld_window_class_frames(_p(frame_mask), int(frame_mask.shape[0]), int(window), int(hop),
+                                                      int(n_windows), int(num_classes), _p(out),
+                                                      _stream_ptr(frame_mask.device)), "seld_window_class_frames")
+    return out
 
 
 def augment_params(params, batch: int, window: int, device, steps: int | None = None) -> torch.Tensor:

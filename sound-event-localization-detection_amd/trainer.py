@@ -37,6 +37,7 @@ from torch.utils.data import DataLoader, RandomSampler, SequentialSampler  # noq
 from tqdm import tqdm
 
 import seld_augment
+import seld_balance
 import seld_standardise
 from config import Config
 from dataset import SELDDataset
@@ -261,6 +262,11 @@ class LoaderFeed:
             raise RuntimeError("STANDARDISE_FEATURES: the per-bin standardisation is applied by the device window gather and "
                                "needs the device feed (DEVICE_FEED = True, a ROCm GPU, a SELDDataset kept on the device); the "
                                "host DataLoader path has no CPU implementation of it.  Switch it off to use this path")
+        if getattr(config, "BALANCED_SAMPLING", False):
+            # likewise: the per-window class statistics are reduced from the device-resident label mask (csrc/balance.hip)
+            raise RuntimeError("BALANCED_SAMPLING: the windows' class statistics are reduced from the device-resident label mask "
+                               "and need the device feed (DEVICE_FEED = True, a ROCm GPU, a SELDDataset kept on the device); "
+                               "the host DataLoader path has no CPU implementation of it.  Switch it off to use this path")
         self.loader, self.device = loader, device
         self.rank, self.world, self.seed = rank, world, seed
         sampler = getattr(loader, "sampler", None)
@@ -304,7 +310,9 @@ class LoaderFeed:
 class DeviceFeed:
     """Batches gathered on the GPU from the dataset's device timeline.  Honours the DataLoader's
     batch size, drop_last and sampler kind (RandomSampler -> a fresh permutation every epoch,
-    otherwise sequential); shards the index order over the ranks."""
+    otherwise sequential); shards the index order over the ranks.  With Config.BALANCED_SAMPLING a shuffling loader's
+    epochs are class-balanced draws with replacement instead (seld_balance.py) -- for the caller
+    that asks for them, which is the training loop."""
 
     def __init__(self, loader, device, rank, world, seed=0):
         self.dataset = loader.dataset
@@ -329,36 +337,86 @@ class DeviceFeed:
             if seld_augment.settings(config)["mix_prob"] > 0 and getattr(self.dataset, "rot_tm", None) is not None:
                 raise ValueError("AUGMENT_MIX_PROB cannot be used with a dataset constructed with AUGMENT_ROTATE: its batches "
                                  "come from the rotating gathers, which do not mix (construct the dataset with the switch off)")
+        # Config.BALANCED_SAMPLING: out-of-range settings are refused here; the weight table is built on first use
+        self.balanced = bool(getattr(config, "BALANCED_SAMPLING", False)) and self.shuffle
+        self._balance_settings = seld_balance.check_settings(config) if getattr(config, "BALANCED_SAMPLING", False) else None
+        self._balance_k = None
 
-    def _order(self, epoch):
+    def balance_table(self):
+        """The int64 weight table ``k`` of class-balanced sampling (seld_balance.window_weights of the dataset's
+        window_class_counts), built once.  Every rank reduces its own copy of the label timeline; under data parallelism
+        rank 0's CRC32 of the table travels the way make_feed's seed does, and a rank whose table differs raises here --
+        before the first batch -- instead of training on overlapping shards."""
+        if self._balance_k is None:
+            if self._balance_settings is None:
+                raise RuntimeError("balance_table: Config.BALANCED_SAMPLING was off when this feed was built")
+            k, failure = None, None
+            try:
+                k = seld_balance.window_weights(self.dataset.window_class_counts(), self._balance_settings)
+            except ValueError as exc:                    # (no active window): raised BEHIND the collectives below, so that
+                if self.world <= 1:                      # a rank that fails alone leaves no other rank waiting in them
+                    raise
+                failure = exc
+            if self.world > 1:
+                mine = seld_balance.table_crc(k) if failure is None else 1 << 32          # no CRC32: agrees with no table
+                first = int(all_reduce_sums([float(mine) if self.rank == 0 else 0.0], self.device)[0])
+                agree = all_reduce_sums([1.0 if mine == first and failure is None else 0.0], self.device)[0]
+                if failure is not None:
+                    raise failure
+                if int(agree) != self.world:             # every rank raises, none is left waiting in a collective
+                    raise RuntimeError(f"BALANCED_SAMPLING: rank {self.rank}'s weight table (CRC32 {mine:08x}) "
+                                       f"{'differs from' if mine != first else 'is'} rank 0's ({first:08x}), and "
+                                       f"{self.world - int(agree)} rank(s) disagree: the ranks' datasets differ, their "
+                                       f"epoch orders would overlap")
+            self._balance_k = k
+        return self._balance_k
+
+    def _order(self, epoch, balanced=True):
+        """This rank's window indices of ``epoch``.  ``balanced``: the caller takes the class-balanced draw when the feed
+        has one (Config.BALANCED_SAMPLING on a shuffling loader); with the switch off it is ``epoch_order``'s, as ever.
+        The defaults differ ON PURPOSE: ``_order(epoch)`` answers "what does the training loop see in this epoch" (the
+        balanced order with the switch on), while ``batches`` hands the balanced order only to the caller that asks for it
+        and passes its own flag down -- an evaluation loop over a shuffling loader gets the permutation.  A caller of
+        ``_order`` that is not the training loop passes ``balanced=False``."""
+        if balanced and self.balanced:
+            order = seld_balance.order(self.balance_table(), self.seed, epoch).tolist()
+            return shard_indices(order, self.rank, self.world)
         return shard_indices(epoch_order(len(self.dataset), self.shuffle, self.seed, epoch), self.rank, self.world)
 
     def __len__(self):
         n = len(shard_indices(range(len(self.dataset)), self.rank, self.world))
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
-    def batches(self, epoch, out=None, augment=False):
+    def batches(self, epoch, out=None, augment=False, balanced=False):
         """``out``: see SELDDataset.device_batch (gather straight into a captured step's input buffers).
         ``augment``: apply the Config.AUGMENT_* switches (seld_augment.draw: a window's transform depends on the seed, the
         epoch and the window's dataset index only).  Only the training loop passes True; with every switch off it is the
-        plain gather."""
+        plain gather.
+        ``balanced``: take the class-balanced order (Config.BALANCED_SAMPLING).  Only the training loop passes True; with
+        the switch off it is the permutation.  A balanced epoch holds windows several times, so the augmentation streams
+        are keyed on each draw's position in the epoch's GLOBAL order (rank + world * local position) instead of the
+        window index: every copy of an oversampled window gets a transform of its own."""
         augment = bool(augment) and seld_augment.enabled(config)
+        balanced = bool(balanced) and self.balanced
         # AUGMENT_MIX_PROB: a partner per window from a stream of its own (seld_augment.draw_mix; csrc/mix.hip)
         mixing = augment and seld_augment.settings(config)["mix_prob"] > 0
         # frequency shift, level / filter curve, cutouts: a third stream per window (seld_augment.draw_spectral), applied by
         # one in-place stage behind whichever gather produced the batch (csrc/spectral.hip)
         shaping = augment and seld_augment.spectral_enabled(config)
-        for idx in batched(self._order(epoch), self.batch_size, self.drop_last):
+        done = 0                                             # windows of this rank's order already handed out
+        for idx in batched(self._order(epoch, balanced), self.batch_size, self.drop_last):
+            keys = [self.rank + self.world * (done + j) for j in range(len(idx))] if balanced else None
+            done += len(idx)
             params = seld_augment.draw(self.seed, epoch, idx, config, window=self.dataset.window_length_frames,
-                                       array=self.array) if augment else None
+                                       array=self.array, keys=keys) if augment else None
             more = {}
             if shaping:
                 more["spectral"] = seld_augment.draw_spectral(self.seed, epoch, idx, config,
-                                                              window=self.dataset.window_length_frames)
+                                                              window=self.dataset.window_length_frames, keys=keys)
             if not mixing:
                 yield self.dataset.device_batch(idx, out=out, augment=params, **more)
                 continue
-            mix = seld_augment.draw_mix(self.seed, epoch, idx, config, len(self.dataset))
+            mix = seld_augment.draw_mix(self.seed, epoch, idx, config, len(self.dataset), keys=keys)
             yield self.dataset.device_batch(idx, out=out, augment=params, mix=mix, **more)
 
 
@@ -791,6 +849,24 @@ def standardise_datasets(train_dataset, test_dataset):
     return seld_standardise.to_payload(stats, getattr(config, "FEATURE_SET", "logmel"), train_dataset.n_channels)
 
 
+def log_balanced_sampling(train_feed):
+    """Config.BALANCED_SAMPLING: build the training feed's weight table now -- the ranks compare
+    theirs here, before the first batch -- and log once what it does to the classes' and the silent windows' exposure.
+    Nothing is computed or launched with the switch off.  Returns the exposure report, or None."""
+    if not getattr(config, "BALANCED_SAMPLING", False):
+        return None
+    if not isinstance(train_feed, DeviceFeed):
+        raise RuntimeError("BALANCED_SAMPLING needs the device feed (DEVICE_FEED = True, a ROCm GPU, a SELDDataset kept on "
+                           "the device): there is no CPU fallback")
+    if not train_feed.balanced:
+        logger.info("Balanced sampling: the training loader does not shuffle; its sequential order is kept")
+        return None
+    report = seld_balance.exposure(train_feed.dataset.window_class_counts(), train_feed.balance_table(),
+                                   train_feed._balance_settings)
+    logger.info("Balanced sampling: " + seld_balance.describe(report, train_feed.dataset.num_classes))
+    return report
+
+
 def apply_checkpoint_statistics(checkpoint, dataset):
     """Evaluation: the checkpoint decides.  Its ``feature_statistics`` are set on ``dataset`` when it holds them; without
     them the dataset gathers raw features -- unless Config.STANDARDISE_FEATURES is on, which is an error (the shape of the
@@ -904,6 +980,7 @@ def train_model(train_loader, test_loader, num_epochs=None, batch_size=None, lea
     # Config.STANDARDISE_FEATURES: the training timeline's statistics on both datasets (every rank reduces its own copy of
     # the timeline in the same fixed order: the same bits without a collective); None with the switch off
     feature_statistics = standardise_datasets(train_dataset, test_dataset)
+    log_balanced_sampling(train_feed)
 
     train_losses, test_losses = [], []
     best_train_loss = best_test_loss = float("inf")
@@ -922,8 +999,8 @@ def train_model(train_loader, test_loader, num_epochs=None, batch_size=None, lea
         term_sum = torch.zeros((), dtype=torch.float64, device=device)
         steps = 0
         static = getattr(stepper, "static_inputs", None) if isinstance(train_feed, DeviceFeed) else None
-        if isinstance(train_feed, DeviceFeed):               # the training feed is the only one that augments
-            source = train_feed.batches(epoch, out=static, augment=True)
+        if isinstance(train_feed, DeviceFeed):               # the training feed is the only one that augments / balances
+            source = train_feed.batches(epoch, out=static, augment=True, balanced=True)
         else:
             source = train_feed.batches(epoch)
         bar = tqdm(source, total=len(train_feed), desc=f"Epoch {epoch}/{num_epochs} [Train]",
