@@ -847,13 +847,9 @@ int seld_gru_forward(const void* gi, int is_bf16, const void* w_hh_bf16, const f
   const dim3 grid(static_cast<unsigned>(tiles), 2);
   const size_t lds = kWnBytes + 2 * kSeqs * kHPitch * sizeof(__hip_bfloat16);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (need_lds(st, kAttrGruForward)) {     // once per device (seld_common.h)
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gru_forward_kernel<__hip_bfloat16>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gru_forward_kernel<float>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    lds_attr_set(st, kAttrGruForward);
-  }
+  // once per device (seld_common.h)
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(gru_forward_kernel<__hip_bfloat16>), static_cast<int>(lds))) return rc;
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(gru_forward_kernel<float>), static_cast<int>(lds))) return rc;
   // (Round 2 measured two variants against this kernel and dropped them: all of W_hh in registers with four wavefronts,
   // 36 % slower -- one wavefront per SIMD has nothing to run in the shadow of its own MFMAs; gate-major MFMA order, no
   // change.  DESIGN.md 5.4.)
@@ -878,13 +874,8 @@ int seld_gru_backward(const void* dy_tile, const void* saved_tile, const void* y
   const dim3 grid(static_cast<unsigned>(tiles), 2);
   const size_t lds = kWnBytes + 2 * kSeqs * kDghPitch * sizeof(__hip_bfloat16);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (need_lds(st, kAttrGruBackward)) {
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gru_backward_kernel<__hip_bfloat16, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gru_backward_kernel<float, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    lds_attr_set(st, kAttrGruBackward);
-  }
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(gru_backward_kernel<__hip_bfloat16, false>), static_cast<int>(lds))) return rc;
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(gru_backward_kernel<float, false>), static_cast<int>(lds))) return rc;
   if (is_bf16) hipLaunchKernelGGL((gru_backward_kernel<__hip_bfloat16, false>), grid, dim3(kGruThreads), lds, stream, a);
   else hipLaunchKernelGGL((gru_backward_kernel<float, false>), grid, dim3(kGruThreads), lds, stream, a);
   SELD_HIP_TRY(hipGetLastError());
@@ -910,11 +901,7 @@ int seld_gru_backward_direct(const void* dy, const void* saved_tile, const void*
   const dim3 grid(static_cast<unsigned>(tiles), 2);
   const size_t lds = kWnBytes + 2 * kSeqs * kDghDirectPitch * sizeof(__hip_bfloat16);   // 144.3 KB of the CU's 160
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (need_lds(st, kAttrGruBackwardDirect)) {
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gru_backward_kernel<__hip_bfloat16, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    lds_attr_set(st, kAttrGruBackwardDirect);
-  }
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(gru_backward_kernel<__hip_bfloat16, true>), static_cast<int>(lds))) return rc;
   hipLaunchKernelGGL((gru_backward_kernel<__hip_bfloat16, true>), grid, dim3(kGruThreads), lds, stream, a);
   SELD_HIP_TRY(hipGetLastError());
   return kOk;

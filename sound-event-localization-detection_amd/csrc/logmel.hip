@@ -56,6 +56,44 @@ __device__ __forceinline__ bool pair_live(unsigned bits, int lane, bool& live_a,
     __builtin_amdgcn_wave_barrier();                       \
   } while (0)
 
+// Stages A and B of one iteration on the samples in s: the verdict of the all-zero rule (pair_live), then the lane's
+// spectrum values in z.  Ends after the third wavefront sync: s is free again and phase_c_load may follow.
+__device__ __forceinline__ bool stages_ab(int lane, const float (&s)[48], const LaneConsts& consts, float* lds, cf (&z)[kN2],
+                                          bool& live_a, bool& live_b) {
+  const bool any_dead = pair_live(lane_live_bits(s), lane, live_a, live_b);
+  phase_a(lane, s, consts, lds);
+  SELD_WAVE_SYNC();
+  phase_b(lane, lds, z);
+  SELD_WAVE_SYNC();
+  phase_b_store(lane, lds, z);
+  SELD_WAVE_SYNC();
+  return any_dead;
+}
+
+// The sparse mel pass over the power rows: the dB values of this lane's band for the four frames.
+__device__ __forceinline__ void mel_db(int lane, float* lds, const float* tab, int seg, float (&db)[kFramesPerIter]) {
+  LaneAcc acc;
+  phase_d_accumulate(lane, lds, tab, seg, acc);
+  float below[kFramesPerIter];
+#pragma unroll
+  for (int f = 0; f < kFramesPerIter; ++f) below[f] = lane_below(acc.ab[f].y);
+  phase_d_finish(acc, below, db);
+}
+
+// The start of every workgroup: the tables into LDS, the wavefront's tile zeroed once -- pad cells are otherwise never
+// written and the mel phase multiplies over-read cells by a zero weight (0 * NaN would poison the sum) -- the lane's
+// segment and power-row pointers, the barrier, the lane's constants from the tables.
+__device__ __forceinline__ void workgroup_prologue(const LogmelArgs& a, int tid, int nthreads, float* tab, float* lds, int& seg,
+                                                   float* (&pp)[16], LaneConsts& consts) {
+  const int lane = tid & 63;
+  fill_tables(a, tab, tid, nthreads);
+  for (int i = lane; i < kLdsFloatsPerWave; i += 64) lds[i] = 0.0f;
+  seg = a.tab.mel_pos[lane];
+  power_row_pointers(lane, lds, a.tab.mel_pos, pp);
+  __syncthreads();
+  load_lane_consts(lane, tab, consts);
+}
+
 // One edge iteration (index e of rows * edge_per_row) by one wavefront: generic load path (reflection, frames past the end
 // masked), no pipelining.
 template <typename T, int kSpec>
@@ -71,14 +109,8 @@ __device__ __forceinline__ void edge_iteration(const LogmelArgs& a, long e, int 
   float s[48];
   load_samples<T, false>(lane, pcm + row * a.L, a.L, tf + 2 * h, s);
   bool live_a, live_b;
-  const bool any_dead = pair_live(lane_live_bits(s), lane, live_a, live_b);
-  phase_a(lane, s, consts, lds);
-  SELD_WAVE_SYNC();
   cf z[kN2];
-  phase_b(lane, lds, z);
-  SELD_WAVE_SYNC();
-  phase_b_store(lane, lds, z);
-  SELD_WAVE_SYNC();
+  const bool any_dead = stages_ab(lane, s, consts, lds, z, live_a, live_b);
   cf m[16];
   phase_c_load(lane, lds, m);
   if (kSpec == 1) {
@@ -98,12 +130,8 @@ __device__ __forceinline__ void edge_iteration(const LogmelArgs& a, long e, int 
   }
   if (any_dead) phase_c_zero_rows(lane, pp, live_a, live_b);
   SELD_WAVE_SYNC();
-  LaneAcc acc;
-  phase_d_accumulate(lane, lds, tab, seg, acc);
-  float below[kFramesPerIter], db[kFramesPerIter];
-#pragma unroll
-  for (int f = 0; f < kFramesPerIter; ++f) below[f] = lane_below(acc.ab[f].y);
-  phase_d_finish(acc, below, db);
+  float db[kFramesPerIter];
+  mel_db(lane, lds, tab, seg, db);
   float* outp = out_pointer(a, row, itr, lane);
 #pragma unroll
   for (int f = 0; f < kFramesPerIter; ++f)
@@ -127,16 +155,10 @@ __global__ __launch_bounds__(kMainWaves * 64, 2) void logmel_main_kernel(LogmelA
   const int h = lane >> 5;
   float* tab = smem;
   float* lds = smem + kTabFloats + wave * kLdsFloatsPerWave;
-  fill_tables(a, tab, tid, kMainWaves * 64);
-  // Zero the wavefront's tile once: pad cells are otherwise never written and the mel phase multiplies
-  // over-read cells by a zero weight (0 * NaN would poison the sum).
-  for (int i = lane; i < kLdsFloatsPerWave; i += 64) lds[i] = 0.0f;
-  const int seg = a.tab.mel_pos[lane];
+  int seg;
   float* pp[16];
-  power_row_pointers(lane, lds, a.tab.mel_pos, pp);
-  __syncthreads();
   LaneConsts consts;
-  load_lane_consts(lane, tab, consts);
+  workgroup_prologue(a, tid, kMainWaves * 64, tab, lds, seg, pp, consts);
 
   // Workgroups past main_blocks run the edge iterations (the first and the last one or two of every row), 8 per
   // workgroup: they land on the CUs the interior pipelines leave free and are done long before those are (round 1 ran
@@ -179,14 +201,8 @@ __global__ __launch_bounds__(kMainWaves * 64, 2) void logmel_main_kernel(LogmelA
     }
     float* outp = out_lane + (clip * a.sN + chan * a.sC + itr * kFramesPerIter * a.sT);
     bool live_a, live_b;
-    const bool any_dead = pair_live(lane_live_bits(s), lane, live_a, live_b);
-    phase_a(lane, s, consts, lds);
-    SELD_WAVE_SYNC();
     cf z[kN2];
-    phase_b(lane, lds, z);
-    SELD_WAVE_SYNC();
-    phase_b_store(lane, lds, z);
-    SELD_WAVE_SYNC();
+    const bool any_dead = stages_ab(lane, s, consts, lds, z, live_a, live_b);
     // the next iteration's samples: requested here, a whole un-pack + mel + store phase ahead -- except in the fp32
     // phasor instantiation, whose un-packing needs the 48 registers (requested after it: no scratch, 64 B per lane before)
     constexpr bool kLatePrefetch = kSpec != 0 && sizeof(T) == 4;
@@ -209,12 +225,8 @@ __global__ __launch_bounds__(kMainWaves * 64, 2) void logmel_main_kernel(LogmelA
     if (any_dead) phase_c_zero_rows(lane, pp, live_a, live_b);
     if (kLatePrefetch) load_samples<T, true>(lane, pcm + nrow * a.L, a.L, nitr * kFramesPerIter + 2 * h, s);
     SELD_WAVE_SYNC();
-    LaneAcc acc;
-    phase_d_accumulate(lane, lds, tab, seg, acc);
-    float below[kFramesPerIter], db[kFramesPerIter];
-#pragma unroll
-    for (int f = 0; f < kFramesPerIter; ++f) below[f] = lane_below(acc.ab[f].y);
-    phase_d_finish(acc, below, db);
+    float db[kFramesPerIter];
+    mel_db(lane, lds, tab, seg, db);
 #pragma unroll
     for (int f = 0; f < kFramesPerIter; ++f) outp[f * a.sT] = db[f];
     SELD_WAVE_SYNC();
@@ -235,14 +247,10 @@ __global__ __launch_bounds__(kEdgeWaves * 64, 1) void logmel_edge_kernel(LogmelA
   const int wave = tid >> 6, lane = tid & 63;
   float* tab = smem;
   float* lds = smem + kTabFloats + wave * kLdsFloatsPerWave;
-  fill_tables(a, tab, tid, kEdgeWaves * 64);
-  for (int i = lane; i < kLdsFloatsPerWave; i += 64) lds[i] = 0.0f;
-  const int seg = a.tab.mel_pos[lane];
+  int seg;
   float* pp[16];
-  power_row_pointers(lane, lds, a.tab.mel_pos, pp);
-  __syncthreads();
   LaneConsts consts;
-  load_lane_consts(lane, tab, consts);
+  workgroup_prologue(a, tid, kEdgeWaves * 64, tab, lds, seg, pp, consts);
 
   const long e = static_cast<long>(blockIdx.x) * kEdgeWaves + wave;
   if (e >= a.rows * a.edge_per_row) return;
@@ -262,11 +270,10 @@ __global__ __launch_bounds__(kEdgeWaves * 64, 2) void stft_kernel(LogmelArgs a) 
   const int h = lane >> 5;
   float* tab = smem;
   float* lds = smem + kTabFloats + wave * kLdsFloatsPerWave;
-  fill_tables(a, tab, tid, kEdgeWaves * 64);
-  for (int i = lane; i < kLdsFloatsPerWave; i += 64) lds[i] = 0.0f;
-  __syncthreads();
+  int seg;              // (neither the segment nor the power rows are used here: no mel pass)
+  float* pp[16];
   LaneConsts consts;
-  load_lane_consts(lane, tab, consts);
+  workgroup_prologue(a, tid, kEdgeWaves * 64, tab, lds, seg, pp, consts);
 
   const long total = a.rows * a.iters_per_row;
   const long gw = static_cast<long>(blockIdx.x) * kEdgeWaves + wave;
@@ -283,14 +290,8 @@ __global__ __launch_bounds__(kEdgeWaves * 64, 2) void stft_kernel(LogmelArgs a) 
     if (interior) load_samples<T, true>(lane, pcm + row * a.L, a.L, tf + 2 * h, s);
     else load_samples<T, false>(lane, pcm + row * a.L, a.L, tf + 2 * h, s);
     bool live_a, live_b;
-    const bool any_dead = pair_live(lane_live_bits(s), lane, live_a, live_b);
-    phase_a(lane, s, consts, lds);
-    SELD_WAVE_SYNC();
     cf z[kN2];
-    phase_b(lane, lds, z);
-    SELD_WAVE_SYNC();
-    phase_b_store(lane, lds, z);
-    SELD_WAVE_SYNC();
+    const bool any_dead = stages_ab(lane, s, consts, lds, z, live_a, live_b);
     cf m[16];
     phase_c_load(lane, lds, m);
     const long fa = tf + 2 * h;
@@ -328,14 +329,10 @@ __global__ __launch_bounds__(kIvChannels * 64, 1) void logmel_iv_kernel(LogmelAr
   float* tab = smem;
   float* lds = smem + kTabFloats + wave * kLdsFloatsPerWave;
   float* wspec = smem + kTabFloats + kIvChannels * kLdsFloatsPerWave;
-  fill_tables(a, tab, tid, kIvChannels * 64);
-  for (int i = lane; i < kLdsFloatsPerWave; i += 64) lds[i] = 0.0f;
-  const int seg = a.tab.mel_pos[lane];
+  int seg;
   float* pp[16];
-  power_row_pointers(lane, lds, a.tab.mel_pos, pp);
-  __syncthreads();
   LaneConsts consts;
-  load_lane_consts(lane, tab, consts);
+  workgroup_prologue(a, tid, kIvChannels * 64, tab, lds, seg, pp, consts);
 
   const long total = (a.rows / kIvChannels) * a.iters_per_row;       // (clip, iteration) pairs
   const long begin = static_cast<long>(blockIdx.x) * a.chunk;
@@ -354,14 +351,8 @@ __global__ __launch_bounds__(kIvChannels * 64, 1) void logmel_iv_kernel(LogmelAr
     }
     const long tf = itr * kFramesPerIter;
     bool live_a, live_b;
-    const bool any_dead = pair_live(lane_live_bits(s), lane, live_a, live_b);
-    phase_a(lane, s, consts, lds);
-    SELD_WAVE_SYNC();
     cf z[kN2];
-    phase_b(lane, lds, z);
-    SELD_WAVE_SYNC();
-    phase_b_store(lane, lds, z);
-    SELD_WAVE_SYNC();
+    const bool any_dead = stages_ab(lane, s, consts, lds, z, live_a, live_b);
     iv_fetch<T>(a, nclip, nitr, wave, lane, s);                       // the next iteration's samples (this one's again at the end)
     cf m[16];
     phase_c_load(lane, lds, m);
@@ -374,12 +365,8 @@ __global__ __launch_bounds__(kIvChannels * 64, 1) void logmel_iv_kernel(LogmelAr
     if (wave != 0) iv_compute(lane, wave, wspec, pp, xa, xb, kIvEps, ia, ib);
     float* outp = a.out + clip * a.sN + lane * a.sM + tf * a.sT;
     {
-      LaneAcc acc;
-      phase_d_accumulate(lane, lds, tab, seg, acc);
-      float below[kFramesPerIter], db[kFramesPerIter];
-#pragma unroll
-      for (int f = 0; f < kFramesPerIter; ++f) below[f] = lane_below(acc.ab[f].y);
-      phase_d_finish(acc, below, db);
+      float db[kFramesPerIter];
+      mel_db(lane, lds, tab, seg, db);
 #pragma unroll
       for (int f = 0; f < kFramesPerIter; ++f)
         if (tf + f < a.F) outp[wave * a.sC + f * a.sT] = db[f];
@@ -402,43 +389,56 @@ __global__ __launch_bounds__(kIvChannels * 64, 1) void logmel_iv_kernel(LogmelAr
   }
 }
 
-template <typename T>
-static int launch_logmel_iv(const T* pcm, int64_t N, int64_t L, float* out, const int64_t* strides, hipStream_t stream) {
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (!pcm || !out) return fail(kErrInvalidArgument, "seld_logmel_iv: null pointer");
-  if (N <= 0) return fail(kErrInvalidArgument, "seld_logmel_iv: N must be positive");
-  if (L <= kNfft / 2) return fail(kErrInvalidArgument, "seld_logmel_iv: reflect padding needs L > n_fft/2 = 480 samples");
-  if (L >= (1L << 30)) return fail(kErrUnsupported, "seld_logmel_iv: at most 2^30 samples per channel");
-  LogmelArgs a;
+// ---- the host prologue of the three launchers ---------------------------------------------------------------------------
+// In this order: the library's state, the pointers, the extents (`extents_ok`, refused as "<who>: <extents>"), L against the
+// reflection and the 32-bit sample index, the layout.  Returns kOk with *state set.
+static int check_logmel_args(const char* who, std::initializer_list<const void*> pointers, bool extents_ok, const char* extents,
+                             int64_t L, int layout, DeviceState** state) {
+  const std::string name(who);
+  *state = current_state();
+  if (!*state) return kErrNotInitialised;
+  for (const void* ptr : pointers)
+    if (!ptr) return fail(kErrInvalidArgument, name + ": null pointer");
+  if (!extents_ok) return fail(kErrInvalidArgument, name + ": " + extents);
+  if (L <= kNfft / 2) return fail(kErrInvalidArgument, name + ": reflect padding needs L > n_fft/2 = 480 samples");
+  if (L >= (1L << 30)) return fail(kErrUnsupported, name + ": at most 2^30 samples per channel");
+  if (layout != 0 && layout != 1) return fail(kErrInvalidArgument, name + ": layout must be 0 or 1");
+  return kOk;
+}
+
+// The arguments every launcher starts from: the rows, their iteration geometry (logmel_core.h) and the tables.
+static LogmelArgs logmel_args(const DeviceState* st, const void* pcm, float* out, int64_t N, int64_t C, int64_t L) {
+  const IterGeometry g = iter_geometry(L);
+  LogmelArgs a{};
   a.pcm = pcm;
   a.out = out;
-  a.rows = N * kIvChannels;
-  a.C = kIvChannels;
+  a.rows = N * C;
+  a.C = C;
   a.L = L;
-  a.F = 1 + L / kHop;
-  a.iters_per_row = (a.F + kFramesPerIter - 1) / kFramesPerIter;
-  a.interior = (L / kHop - kFramesPerIter) / kFramesPerIter;          // as launch_logmel
-  if (a.interior < 0) a.interior = 0;
-  if (a.interior > a.iters_per_row - 1) a.interior = a.iters_per_row - 1;
-  a.edge_per_row = a.iters_per_row - a.interior;
+  a.F = g.F;
+  a.iters_per_row = g.iters_per_row;
+  a.interior = g.interior;
+  a.edge_per_row = g.edge_per_row;
+  a.chunk = 1;
+  a.tab = st->tables();
+  return a;
+}
+
+template <typename T>
+static int launch_logmel_iv(const T* pcm, int64_t N, int64_t L, float* out, const int64_t* strides, hipStream_t stream) {
+  DeviceState* st;
+  if (int rc = check_logmel_args("seld_logmel_iv", {pcm, out}, N > 0, "N must be positive", L, 0, &st)) return rc;
+  LogmelArgs a = logmel_args(st, pcm, out, N, kIvChannels, L);
   a.sN = strides[0];
   a.sC = strides[1];
   a.sM = strides[2];
   a.sT = strides[3];
-  a.tab = st->tables();
-  a.spec = nullptr;
-  a.main_blocks = 0;
   const long total = N * a.iters_per_row;
   long groups = total < st->num_cus ? total : static_cast<long>(st->num_cus);
   a.chunk = (total + groups - 1) / groups;
   groups = (total + a.chunk - 1) / a.chunk;
-  const unsigned bit = sizeof(T) == 4 ? kAttrLogmelIvF32 : kAttrLogmelIvI16;
-  if (need_lds(st, bit)) {                 // once per device (seld_common.h)
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_iv_kernel<T>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kIvLdsBytes));
-    lds_attr_set(st, bit);
-  }
+  // once per device (seld_common.h)
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(logmel_iv_kernel<T>), kIvLdsBytes)) return rc;
   hipLaunchKernelGGL(logmel_iv_kernel<T>, dim3(static_cast<unsigned>(groups)), dim3(kIvChannels * 64), kIvLdsBytes, stream, a);
   SELD_HIP_TRY(hipGetLastError());
   return kOk;
@@ -446,38 +446,17 @@ static int launch_logmel_iv(const T* pcm, int64_t N, int64_t L, float* out, cons
 
 template <typename T>
 static int launch_stft(const T* pcm, int64_t N, int64_t C, int64_t L, float* out, hipStream_t stream) {
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (!pcm || !out) return fail(kErrInvalidArgument, "seld_stft: null pointer");
-  if (N <= 0 || C <= 0) return fail(kErrInvalidArgument, "seld_stft: N and C must be positive");
-  if (L <= kNfft / 2) return fail(kErrInvalidArgument, "seld_stft: reflect padding needs L > n_fft/2 = 480 samples");
-  if (L >= (1L << 30)) return fail(kErrUnsupported, "seld_stft: at most 2^30 samples per channel");
-  LogmelArgs a;
-  a.pcm = pcm;
-  a.out = out;
-  a.rows = N * C;
-  a.C = C;
-  a.L = L;
-  a.F = 1 + L / kHop;
-  a.iters_per_row = (a.F + kFramesPerIter - 1) / kFramesPerIter;
-  a.interior = (L / kHop - kFramesPerIter) / kFramesPerIter;
-  if (a.interior < 0) a.interior = 0;
-  if (a.interior > a.iters_per_row - 1) a.interior = a.iters_per_row - 1;
-  a.edge_per_row = a.iters_per_row - a.interior;
-  a.sN = a.sC = a.sM = a.sT = 0;
-  a.tab = st->tables();
+  DeviceState* st;
+  if (int rc = check_logmel_args("seld_stft", {pcm, out}, N > 0 && C > 0, "N and C must be positive", L, 0, &st)) return rc;
+  LogmelArgs a = logmel_args(st, pcm, out, N, C, L);
   const long total = a.rows * a.iters_per_row;
   const long max_waves = static_cast<long>(st->num_cus) * 8;
   long waves = (total + 3) / 4;
   if (waves > max_waves) waves = max_waves;
   a.chunk = (total + waves - 1) / waves;
   const long used = (total + a.chunk - 1) / a.chunk;
-  const unsigned bit = sizeof(T) == 4 ? kAttrStftF32 : kAttrStftI16;
-  if (need_lds(st, bit)) {                 // once per device (seld_common.h)
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(stft_kernel<T>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kEdgeLdsBytes));
-    lds_attr_set(st, bit);
-  }
+  // once per device (seld_common.h)
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(stft_kernel<T>), kEdgeLdsBytes)) return rc;
   hipLaunchKernelGGL(stft_kernel<T>, dim3(static_cast<unsigned>((used + kEdgeWaves - 1) / kEdgeWaves)),
                      dim3(kEdgeWaves * 64), kEdgeLdsBytes, stream, a);
   SELD_HIP_TRY(hipGetLastError());
@@ -487,28 +466,11 @@ static int launch_stft(const T* pcm, int64_t N, int64_t C, int64_t L, float* out
 template <typename T, int kSpec = 0>
 static int launch_logmel(const T* pcm, int64_t N, int64_t C, int64_t L, float* out, int layout,
                          hipStream_t stream, const int64_t* strides = nullptr, float* spec = nullptr) {
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (!pcm || !out || (kSpec && !spec)) return fail(kErrInvalidArgument, "seld_logmel: null pointer");
-  if (N <= 0 || C <= 0) return fail(kErrInvalidArgument, "seld_logmel: N and C must be positive");
-  if (L <= kNfft / 2)
-    return fail(kErrInvalidArgument, "seld_logmel: reflect padding needs L > n_fft/2 = 480 samples");
-  if (L >= (1L << 30)) return fail(kErrUnsupported, "seld_logmel: at most 2^30 samples per channel");
-  if (!strides && layout != 0 && layout != 1) return fail(kErrInvalidArgument, "seld_logmel: layout must be 0 or 1");
-
-  LogmelArgs a;
-  a.pcm = pcm;
-  a.out = out;
-  a.rows = N * C;
-  a.C = C;
-  a.L = L;
-  a.F = 1 + L / kHop;
-  a.iters_per_row = (a.F + kFramesPerIter - 1) / kFramesPerIter;
-  // iteration i (frames 4i..4i+3) is interior iff i >= 1 and 480*(4i+4) <= L
-  a.interior = (L / kHop - kFramesPerIter) / kFramesPerIter;
-  if (a.interior < 0) a.interior = 0;
-  if (a.interior > a.iters_per_row - 1) a.interior = a.iters_per_row - 1;
-  a.edge_per_row = a.iters_per_row - a.interior;
+  DeviceState* st;
+  if (int rc = check_logmel_args("seld_logmel", {pcm, out, kSpec ? spec : out}, N > 0 && C > 0, "N and C must be positive", L,
+                                 strides ? 0 : layout, &st))
+    return rc;
+  LogmelArgs a = logmel_args(st, pcm, out, N, C, L);
   if (strides) {                // caller-defined placement (e.g. channels 0..C-1 of a wider feature tensor)
     a.sN = strides[0];
     a.sC = strides[1];
@@ -525,23 +487,13 @@ static int launch_logmel(const T* pcm, int64_t N, int64_t C, int64_t L, float* o
     a.sT = C * kMels;
     a.sN = a.F * C * kMels;
   }
-  a.tab = st->tables();
-  a.chunk = 1;
   a.spec = spec;
 
-  const unsigned bit = kSpec == 2 ? (sizeof(T) == 4 ? kAttrLogmelPhasorF32 : kAttrLogmelPhasorI16)
-                       : kSpec == 1 ? (sizeof(T) == 4 ? kAttrLogmelSpecF32 : kAttrLogmelSpecI16)
-                                    : (sizeof(T) == 4 ? kAttrLogmelF32 : kAttrLogmelI16);
-  if (need_lds(st, bit)) {                 // once per device (seld_common.h)
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_main_kernel<T, kSpec>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kMainLdsBytes));
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_edge_kernel<T, kSpec>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kEdgeLdsBytes));
-    lds_attr_set(st, bit);
-  }
+  // once per device (seld_common.h)
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(logmel_main_kernel<T, kSpec>), kMainLdsBytes)) return rc;
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(logmel_edge_kernel<T, kSpec>), kEdgeLdsBytes)) return rc;
   const long n_edge = a.rows * a.edge_per_row;
   const long total = a.rows * a.interior;
-  a.main_blocks = 0;
   if (total == 0) {             // clips shorter than ~8 frames: edge iterations only
     hipLaunchKernelGGL((logmel_edge_kernel<T, kSpec>), dim3(static_cast<unsigned>((n_edge + kEdgeWaves - 1) / kEdgeWaves)),
                        dim3(kEdgeWaves * 64), kEdgeLdsBytes, stream, a);

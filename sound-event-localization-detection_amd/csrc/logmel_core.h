@@ -56,6 +56,27 @@ constexpr int kMelMaxCnt = 24;          // max bins owned by one lane (checked w
 constexpr int kFramesPerIter = 4;
 constexpr float kAmin = 1e-10f;
 
+// The iterations of one row of L samples (host side: the launchers and the lane emulator).  An iteration is 4 consecutive
+// frames; iteration i is interior -- it touches only samples inside [0, L) and all its frames exist -- iff
+// 1 <= i <= interior, i.e. i >= 1 and 480 * (4 i + 4) <= L.  The others (the first, the last one or two) are the edge ones.
+struct IterGeometry {
+  long F;               // 1 + L / 480 frames
+  long iters_per_row;   // ceil(F / 4)
+  long interior, edge_per_row;
+  bool is_interior(long itr) const { return itr >= 1 && itr <= interior; }
+};
+
+inline IterGeometry iter_geometry(long L) {
+  IterGeometry g;
+  g.F = 1 + L / kHop;
+  g.iters_per_row = (g.F + kFramesPerIter - 1) / kFramesPerIter;
+  g.interior = (L / kHop - kFramesPerIter) / kFramesPerIter;
+  if (g.interior < 0) g.interior = 0;
+  if (g.interior > g.iters_per_row - 1) g.interior = g.iters_per_row - 1;
+  g.edge_per_row = g.iters_per_row - g.interior;
+  return g;
+}
+
 static_assert(kPOff + 4 * kPPitch <= kEFloats, "power rows must fit in the E tile");
 constexpr int kMelPosInts = 64 + 16 * 32;   // seg[64] followed by the power-row offset of bin l + 32 r at [64 + 32 r + l]
 

@@ -208,15 +208,11 @@ int seld_nipd_table_host(double min_hz, double max_hz, double sound_speed, int32
 int seld_nipd_q15(const uint32_t* phasors, int64_t N, int64_t C, int64_t F, const void* table_dev, float* out, int64_t sN,
                   int64_t sC, int64_t sM, int64_t sT, void* stream_) {
   using namespace seld;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (!phasors || !table_dev || !out) return fail(kErrInvalidArgument, "seld_nipd_q15: null pointer");
-  if (N <= 0 || F <= 0) return fail(kErrInvalidArgument, "seld_nipd_q15: N and F must be positive");
-  if (C < 2 || C > 8) return fail(kErrUnsupported, "seld_nipd_q15: 2..8 channels");
-  if (C * F * kPhasorPitch >= (1L << 31)) return fail(kErrUnsupported, "seld_nipd_q15: a clip's phasors exceed 2^31 words");
-  if (N * F + 4L * 1024 >= (1L << 31)) return fail(kErrUnsupported, "seld_nipd_q15: more than 2^31 frames");
-  const bool rows_ok = sM == 1 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && sN % 4 == 0 && sC % 4 == 0 && sT % 4 == 0;
-  if (!rows_ok) return fail(kErrUnsupported, "seld_nipd_q15: needs unit band stride and 16-byte aligned rows");
+  DeviceState* st;
+  if (int rc = check_pair_args("seld_nipd_q15", {phasors, table_dev, out}, N, C, F, kPhasorPitch, "phasors exceed 2^31 words", true, &st))
+    return rc;
+  if (!vector_rows(out, sN, sC, sM, sT))
+    return fail(kErrUnsupported, "seld_nipd_q15: needs unit band stride and 16-byte aligned rows");
   if ((reinterpret_cast<uintptr_t>(phasors) & 15) != 0 || (reinterpret_cast<uintptr_t>(table_dev) & 3) != 0)
     return fail(kErrUnsupported, "seld_nipd_q15: phasor rows must be 16-byte aligned, the table 4-byte aligned");
   hipStream_t stream = static_cast<hipStream_t>(stream_);

@@ -39,6 +39,16 @@ DeviceState* current_state() {
   return &it->second;
 }
 
+int allow_dynamic_lds(DeviceState* st, const void* kernel, int bytes) {
+  std::lock_guard<std::mutex> lock(g_mutex);
+  for (int i = 0; i < st->lds_allowed_n; ++i)
+    if (st->lds_allowed[i] == kernel) return kOk;
+  SELD_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  constexpr int kSlots = sizeof(st->lds_allowed) / sizeof(st->lds_allowed[0]);
+  if (st->lds_allowed_n < kSlots) st->lds_allowed[st->lds_allowed_n++] = kernel;
+  return kOk;
+}
+
 static int upload_mel(DeviceState& st, const std::vector<float>& fb) {
   std::vector<int> b0;
   std::vector<float> wd, wu;
@@ -51,7 +61,6 @@ static int upload_mel(DeviceState& st, const std::vector<float>& fb) {
   SELD_HIP_TRY(hipMemcpy(st.mel_b0, b0.data(), b0.size() * sizeof(int), hipMemcpyHostToDevice));
   SELD_HIP_TRY(hipMemcpy(st.mel_wd, wd.data(), wd.size() * sizeof(float), hipMemcpyHostToDevice));
   SELD_HIP_TRY(hipMemcpy(st.mel_wu, wu.data(), wu.size() * sizeof(float), hipMemcpyHostToDevice));
-  SELD_HIP_TRY(hipMemcpy(st.mel_fb, fb.data(), fb.size() * sizeof(float), hipMemcpyHostToDevice));
   return kOk;
 }
 
@@ -83,7 +92,6 @@ int seld_init(int device) {
   SELD_HIP_TRY(hipMalloc(&st.mel_pos, kMelPosInts * sizeof(int)));
   SELD_HIP_TRY(hipMalloc(&st.mel_wd, kMels * kMelMaxCnt * sizeof(float)));
   SELD_HIP_TRY(hipMalloc(&st.mel_wu, kMels * kMelMaxCnt * sizeof(float)));
-  SELD_HIP_TRY(hipMalloc(&st.mel_fb, static_cast<size_t>(kBins) * kMels * sizeof(float)));
   SELD_HIP_TRY(hipMemcpy(st.window, window.data(), window.size() * sizeof(float), hipMemcpyHostToDevice));
   SELD_HIP_TRY(hipMemcpy(st.twiddle, twiddle.data(), twiddle.size() * sizeof(float), hipMemcpyHostToDevice));
   std::vector<float> fb;
@@ -92,9 +100,6 @@ int seld_init(int device) {
   if (rc != kOk) return rc;
   const int rc_gcc = build_gcc_table(&st);
   if (rc_gcc != kOk) return rc_gcc;
-  SELD_HIP_TRY(hipStreamCreateWithFlags(&st.side_stream, hipStreamNonBlocking));
-  SELD_HIP_TRY(hipEventCreateWithFlags(&st.fork_event, hipEventDisableTiming));
-  SELD_HIP_TRY(hipEventCreateWithFlags(&st.join_event, hipEventDisableTiming));
   st.ready = true;
   return kOk;
 }
@@ -112,11 +117,7 @@ int seld_shutdown(void) {
     (void)hipFree(st.mel_pos);
     (void)hipFree(st.mel_wd);
     (void)hipFree(st.mel_wu);
-    (void)hipFree(st.mel_fb);
     if (st.gcc_table) (void)hipFree(st.gcc_table);
-    (void)hipEventDestroy(st.fork_event);
-    (void)hipEventDestroy(st.join_event);
-    (void)hipStreamDestroy(st.side_stream);
     st = DeviceState();
   }
   g_states.clear();

@@ -14,13 +14,10 @@
 // HBM-bound: 4 x 481 x 8 B = 15.4 KB of spectra read and 768 B written per frame (intensity vectors);
 // C x 3.8 KB read and C(C-1)/2 x 256 B written per frame (GCC).
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <vector>
-
-#include <type_traits>
 
 #include "seld_common.h"
 
@@ -980,10 +977,8 @@ extern "C" {
 int seld_foa_intensity(const float* spec_complex, int64_t N, int64_t F, float* out, int64_t sN, int64_t sC,
                        int64_t sM, int64_t sT, void* stream_) {
   using namespace seld;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (!spec_complex || !out) return fail(kErrInvalidArgument, "seld_foa_intensity: null pointer");
-  if (N <= 0 || F <= 0) return fail(kErrInvalidArgument, "seld_foa_intensity: N and F must be positive");
+  DeviceState* st;
+  if (int rc = check_frame_args("seld_foa_intensity", {spec_complex, out}, N, F, &st)) return rc;
   IvArgs a{spec_complex, out, N, F, sN, sC, sM, sT, 1e-8f, st->tables()};
   long blocks = (N * F + kIvWaves - 1) / kIvWaves;
   const long cap = static_cast<long>(st->num_cus) * 8;
@@ -1011,15 +1006,9 @@ static int launch_gcc_q15(seld::DeviceState* st, const uint32_t* phasors, int64_
                           int64_t sN, int64_t sC, int64_t sM, int64_t sT, void* stream_) {
   using namespace seld;
   GccMfmaArgs a{reinterpret_cast<const float*>(phasors), out, N, C, F, sN, sC, sM, sT, st->gcc_table};
-  if (need_lds(st, kAttrGccMfmaQ15)) {
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gcc_mfma_kernel<true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kGmLdsBytes));
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gcc_q15_kernel<1>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kGqLdsBytes));
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gcc_q15_kernel<2>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kGqLdsBytes));
-    lds_attr_set(st, kAttrGccMfmaQ15);
-  }
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(gcc_mfma_kernel<true>), kGmLdsBytes)) return rc;
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(gcc_q15_kernel<1>), kGqLdsBytes)) return rc;
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(gcc_q15_kernel<2>), kGqLdsBytes)) return rc;
   // SELD_GCC=planar selects the kernel that unpacks the words to fp32 in LDS (the round-3a path): developer A/B, read per
   // call because the tests run both kernels in one process
   const char* which = getenv("SELD_GCC");
@@ -1047,42 +1036,28 @@ static int launch_gcc_q15(seld::DeviceState* st, const uint32_t* phasors, int64_
 int seld_gcc_phat_q15(const uint32_t* phasors, int64_t N, int64_t C, int64_t F, float* out, int64_t sN, int64_t sC,
                       int64_t sM, int64_t sT, void* stream_) {
   using namespace seld;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (!phasors || !out) return fail(kErrInvalidArgument, "seld_gcc_phat_q15: null pointer");
-  if (N <= 0 || F <= 0) return fail(kErrInvalidArgument, "seld_gcc_phat_q15: N and F must be positive");
-  if (C < 2 || C > 8) return fail(kErrUnsupported, "seld_gcc_phat_q15: 2..8 channels");
-  if (C * F * kPhasorPitch >= (1L << 31)) return fail(kErrUnsupported, "seld_gcc_phat_q15: a clip's phasors exceed 2^31 words");
-  if (N * F + 4L * 1024 >= (1L << 31)) return fail(kErrUnsupported, "seld_gcc_phat_q15: more than 2^31 frames");
-  // the kernel stores four consecutive lags as one vector: unit lag stride, 16-byte aligned rows
-  const bool vector_rows = sM == 1 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && sN % 4 == 0 && sC % 4 == 0 && sT % 4 == 0;
-  if (!vector_rows) return fail(kErrUnsupported, "seld_gcc_phat_q15: needs unit lag stride and 16-byte aligned rows");
+  DeviceState* st;
+  if (int rc = check_pair_args("seld_gcc_phat_q15", {phasors, out}, N, C, F, kPhasorPitch, "phasors exceed 2^31 words", true, &st))
+    return rc;
+  if (!vector_rows(out, sN, sC, sM, sT))
+    return fail(kErrUnsupported, "seld_gcc_phat_q15: needs unit lag stride and 16-byte aligned rows");
   return launch_gcc_q15(st, phasors, N, C, F, out, sN, sC, sM, sT, stream_);
 }
 
 int seld_gcc_phat(const float* spec_complex, int64_t N, int64_t C, int64_t F, float* out, int64_t sN, int64_t sC,
                   int64_t sM, int64_t sT, void* stream_) {
   using namespace seld;
-  DeviceState* st = current_state();
-  if (!st) return kErrNotInitialised;
-  if (!spec_complex || !out) return fail(kErrInvalidArgument, "seld_gcc_phat: null pointer");
-  if (N <= 0 || F <= 0) return fail(kErrInvalidArgument, "seld_gcc_phat: N and F must be positive");
-  if (C < 2 || C > 8) return fail(kErrUnsupported, "seld_gcc_phat: 2..8 channels");
-  if (C * F * kBins >= (1L << 31)) return fail(kErrUnsupported, "seld_gcc_phat: a clip's spectra exceed 2^31 complex values");
+  DeviceState* st;
+  if (int rc = check_pair_args("seld_gcc_phat", {spec_complex, out}, N, C, F, kBins, "spectra exceed 2^31 complex values", false, &st))
+    return rc;
   // SELD_GCC=fft selects the round-2a kernel (14 packed pruned inverse FFTs per frame on the vector units): developer A/B
   const char* which = getenv("SELD_GCC");                          // read per call: the tests run both kernels in one process
   const bool use_fft = which && which[0] == 'f';
-  // the matrix-core kernel stores four consecutive lags as one vector: unit lag stride, 16-byte aligned rows
-  const bool vector_rows = sM == 1 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && sN % 4 == 0 && sC % 4 == 0 && sT % 4 == 0;
-  if (!use_fft && vector_rows) {
+  if (!use_fft && vector_rows(out, sN, sC, sM, sT)) {        // else the FFT kernel, which stores lag by lag
     GccMfmaArgs a{spec_complex, out, N, C, F, sN, sC, sM, sT, st->gcc_table};
     long blocks = (N * F + 1) / 2;
     if (blocks > st->num_cus) blocks = st->num_cus;         // persistent: the 96 KB table is staged once per workgroup
-    if (need_lds(st, kAttrGccMfma)) {
-      SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gcc_mfma_kernel<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kGmLdsBytes));
-      lds_attr_set(st, kAttrGccMfma);
-    }
+    if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(gcc_mfma_kernel<false>), kGmLdsBytes)) return rc;
     hipLaunchKernelGGL(gcc_mfma_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kGmThreads), kGmLdsBytes,
                        static_cast<hipStream_t>(stream_), a);
     SELD_HIP_TRY(hipGetLastError());
@@ -1093,11 +1068,8 @@ int seld_gcc_phat(const float* spec_complex, int64_t N, int64_t C, int64_t F, fl
   const long cap = static_cast<long>(st->num_cus) * 4;
   if (blocks > cap) blocks = cap;
   const size_t lds = kGccLdsFloats * sizeof(float);
-  if (need_lds(st, kAttrSpatial)) {        // once per device (seld_common.h)
-    SELD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gcc_phat_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    lds_attr_set(st, kAttrSpatial);
-  }
+  // once per device (seld_common.h)
+  if (int rc = allow_dynamic_lds(st, reinterpret_cast<const void*>(gcc_phat_kernel), static_cast<int>(lds))) return rc;
   hipLaunchKernelGGL(gcc_phat_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kGccWaves * 64), lds,
                      static_cast<hipStream_t>(stream_), a);
   SELD_HIP_TRY(hipGetLastError());

@@ -55,7 +55,8 @@ int run(const T* pcm, int64_t N, int64_t C, int64_t L, float* out, long sN, long
   if (place_power_rows(t.fb, t.b0, t.pos)) return -5;
   const LogmelTables tab = t.view();
 
-  const long F = 1 + L / kHop;
+  const IterGeometry g = iter_geometry(L);
+  const long F = g.F;
   std::vector<float> block(kGuard + kLdsFloatsPerWave + kGuard, 0.0f);
   for (int i = 0; i < kGuard; ++i) block[i] = block[block.size() - 1 - i] = kGuardValue;
   float* lds = block.data() + kGuard;
@@ -65,14 +66,13 @@ int run(const T* pcm, int64_t N, int64_t C, int64_t L, float* out, long sN, long
   std::vector<float> smp(64 * 48);
   std::vector<unsigned> bits(64);
   std::vector<LaneAcc> acc(64);
-  const long iters_per_row = (F + kFramesPerIter - 1) / kFramesPerIter;
 
   for (long row = 0; row < N * C; ++row) {
     const T* rowp = pcm + row * L;
     const long n = row / C, c = row % C;
-    for (long itr = 0; itr < iters_per_row; ++itr) {
+    for (long itr = 0; itr < g.iters_per_row; ++itr) {
       const long tf = itr * kFramesPerIter;
-      const bool interior = (tf >= 1) && (static_cast<long>(kHop) * (tf + kFramesPerIter) <= L);
+      const bool interior = g.is_interior(itr);
       for (int lane = 0; lane < 64; ++lane) {
         const long fa = tf + 2 * (lane >> 5);
         float(&s)[48] = *reinterpret_cast<float(*)[48]>(&smp[lane * 48]);
@@ -156,7 +156,8 @@ int run_iv(const T* pcm, int64_t N, int64_t L, float* out, const float* fb_opt, 
   if (build_sparse_mel(t.fb, t.b0, t.wd, t.wu)) return -4;
   if (place_power_rows(t.fb, t.b0, t.pos)) return -5;
   const LogmelTables tab = t.view();
-  const long F = 1 + L / kHop;
+  const IterGeometry g = iter_geometry(L);
+  const long F = g.F;
   const long total_ch = 2 * kIvChannels - 1;
   const long sM = 1, sC = kMels, sT = total_ch * kMels, sN = F * total_ch * kMels;
   std::vector<float> block(kGuard + kIvChannels * kLdsFloatsPerWave + kIvSpecFloats + kGuard, 0.0f);
@@ -169,12 +170,11 @@ int run_iv(const T* pcm, int64_t N, int64_t L, float* out, const float* fb_opt, 
   std::vector<float> smp(64 * 48), ia(kIvChannels * 64 * 16), ib(kIvChannels * 64 * 16);
   std::vector<LaneAcc> acc(64);
   std::vector<unsigned> bits(64);
-  const long iters_per_row = (F + kFramesPerIter - 1) / kFramesPerIter;
 #define AT(vec, w, lane, n) (*reinterpret_cast<decltype(vec)::value_type(*)[n]>(&vec[((w) * 64 + (lane)) * (n)]))
   for (long clip = 0; clip < N; ++clip) {
-    for (long itr = 0; itr < iters_per_row; ++itr) {
+    for (long itr = 0; itr < g.iters_per_row; ++itr) {
       const long tf = itr * kFramesPerIter;
-      const bool interior = (tf >= 1) && (static_cast<long>(kHop) * (tf + kFramesPerIter) <= L);
+      const bool interior = g.is_interior(itr);
       for (int w = 0; w < kIvChannels; ++w) {
         float* lds = tiles + w * kLdsFloatsPerWave;
         const T* rowp = pcm + (clip * kIvChannels + w) * L;
