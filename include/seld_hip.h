@@ -380,6 +380,40 @@ int seld_window_spectral_standardised(float* batch, int64_t total_rows, int chan
                                       const float* curves, int64_t B, int64_t window, float mask_value, const float* scale,
                                       const float* shift, void* stream);
 
+/* ---- per-channel energy normalisation of the log-mel channels (csrc/pcen.hip) ------------------- */
+/* x float32 [N][T][C_total][64], time-major: n the clip, t the frame, c the channel, f the mel bin.  The first C_log channels
+ * are log-mel in dB as the feature kernels above write them.  For every clip, every c < C_log and every f:
+ *   E[t] = 2^(x[t] log2(10) / 10)                    the stored value back as mel power: the -100 dB floor is 1e-10
+ *   M[t] = a M[t-1] + s E[t],  a = 1 - s,  M[-1] = E[0]     (the steady-state start; the smoother starts afresh in every clip)
+ *   y[t] = (E[t] (eps + M[t])^-alpha + delta)^r - delta^r
+ * and out[n][t][c][f] = y[t].  s comes from a time constant tau in seconds at 50 frames per second: T_f = 50 tau,
+ * s = (sqrt(1 + 4 T_f^2) - 1) / (2 T_f^2), computed in float64 by the caller and passed as one float.  Channels c >= C_log
+ * (intensity vectors, GCC lags, NIPD) are neither read nor written.  out has x's layout; out == x (in place) is allowed,
+ * any other overlap is refused; with out != x, out's channels c >= C_log are left untouched.
+ *
+ * The arithmetic is FIXED, so the result is the same bits on every grid, CU count and device, a clip's result does not depend
+ * on the other clips of the call, and frame t does not depend on frames after it or on T:
+ *   - fp32 throughout; u^v is exp2(fl(v log2(u))) with the hardware's exp2 / log2 (v_exp_f32, v_log_f32);
+ *     E = exp2(fl(x c)), c = fl32(log2(10) / 10); a = fl(1 - s);
+ *   - the time axis is cut into chunks of SELD_PCEN_CHUNK_FRAMES frames anchored at a clip's frame 0 (the last one ragged);
+ *   - the aggregate of a chunk k that has a successor is A_k = the state after its 256 frames from state 0,
+ *     M <- fmaf(a, M, fl(s E)) in ascending frame order;
+ *   - the state entering chunk k is Horner over the earlier chunks in ascending order from E[0]:
+ *     M <- fmaf(a256, M, A_j), j = 0 .. k - 1, a256 = fl32(a^256 evaluated in double);
+ *   - inside the chunk M <- fmaf(a, M, fl(s E)), then y = fl(exp2(fl(r log2(fl(fl(E g) + delta)))) - dr) with
+ *     g = exp2(fl(-alpha log2(fl(eps + M)))) and dr = fl32(delta^r evaluated in double); nothing else is fused.
+ * Two launches on `stream`: the first writes E[0] and the aggregates to `workspace` (seld_pcen_workspace bytes: float
+ * [N][chunks][C_log][64], row 0 of a clip E[0], row 1 + k the aggregate A_k), the second reads its own chunk's frames of x
+ * and the workspace, nothing else -- so in place no workgroup reads what another may have overwritten.  No spin, no
+ * look-back, no atomics, no device-scope fence, no allocation, no synchronisation.
+ * -1: a null pointer; N < 1 or T < 1; C_log < 1 or C_log > C_total; a non-finite parameter; s outside (0, 1]; alpha outside
+ * [0, 1]; r outside (0, 1]; delta <= 0 or eps <= 0; a workspace smaller than reported; out overlapping x without being x.
+ * -4: extents beyond the kernels' 32-bit chunk indices; a pointer that is not 16-byte aligned. */
+#define SELD_PCEN_CHUNK_FRAMES 256
+int64_t seld_pcen_workspace(int64_t N, int64_t T, int C_total, int C_log);   /* bytes; 0 for extents that are refused */
+int seld_pcen(const float* x, float* out, int64_t N, int64_t T, int C_total, int C_log, float s, float alpha, float delta,
+              float r, float eps, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- loss: loss.py:43-54 class_mse_loss (+ its backward) ---------------------------------- */
 /* logits [n_cells][14] (fp32, or bf16 when logits_is_bf16), labels as EITHER the compact mask
  * (uint16 [n_cells]) OR dense float32 [n_cells][14] (exactly one non-NULL).  Writes

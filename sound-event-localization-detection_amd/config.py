@@ -211,6 +211,21 @@ class Config:
                                 # 'feature_statistics'; test_model / evaluate_seld / infer.py apply a checkpoint's statistics
                                 # whenever it holds them (with the switch on and none in the checkpoint: an error).  Needs
                                 # DEVICE_FEED like the augmentation switches (the host DataLoader path refuses to run)
+    # Per-channel energy normalisation of the log-mel channels (csrc/pcen.hip).  Off by default: every
+    # entry point, cache file name, checkpoint and benchmark figure is then what it was
+    PCEN = False                # SELDDataset replaces each recording's log-mel channels (dB) by
+                                # y = (E (eps + M)^-gain + bias)^power - bias^power, E the mel power and M its first-order
+                                # average along time, restarted per recording: nearly independent of the recording level,
+                                # stationary background suppressed.  The other channels (intensity vectors, GCC-PHAT, NIPD)
+                                # stay.  Not with the switches defined on dB or power values (AUGMENT_MIX_PROB,
+                                # AUGMENT_ROTATE, AUGMENT_LEVEL_DB, AUGMENT_FILTER_PROB); needs the device path (the host
+                                # DataLoader path refuses to run); the five settings travel in the checkpoint
+    PCEN_TIME_CONSTANT = 0.4    # seconds: the smoother's time constant (seld_native.pcen_coefficient turns it into s)
+    PCEN_GAIN = 0.98            # alpha in [0, 1]: how much of the smoothed level is divided out
+    PCEN_BIAS = 2.0             # delta > 0: added before the root
+    PCEN_POWER = 0.5            # r in (0, 1]: the root
+    PCEN_EPS = 1e-10            # the log-mel's own power floor (-100 dB).  librosa's default of 1e-6 presumes magnitudes of
+                                # integer-scaled samples (x 2^31); the mel powers here come from samples in [-1, 1)
     # Class-balanced window sampling of the training feed (seld_balance.py, csrc/balance.hip).  Off by
     # default: every entry point, epoch order, checkpoint and benchmark figure is then what it was
     BALANCED_SAMPLING = False   # the training feed draws each epoch's len(dataset) windows WITH replacement, weighted by the

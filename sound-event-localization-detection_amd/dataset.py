@@ -290,6 +290,8 @@ class SELDDataset(Dataset):
             fields += ("resample-kaiser10.06-zc64-v1",)    # with the switch off the names are the ones they always were
         if getattr(config, "FEATURE_SET", "logmel") == "logmel_nipd":      # what the NIPD channels depend on
             fields += tuple(float(v) for v in _nipd_settings())
+        if getattr(self, "pcen_settings", None) is not None:               # Config.PCEN: the log-mel channels hold PCEN values
+            fields += ("pcen-v1",) + tuple(self.pcen_settings[k] for k in seld_augment.PCEN_SETTINGS[1:])
         key = "|".join(str(v) for v in fields)
         return Path(root) / f"{a.stem}.{hashlib.sha1(key.encode()).hexdigest()[:16]}.npz"
 
@@ -336,6 +338,14 @@ class SELDDataset(Dataset):
             spec = seld_native.spatial_features(signal, feature_set, nipd_min_hz=lo, nipd_max_hz=hi, sound_speed=speed)
         else:
             spec = seld_native.spatial_features(signal, feature_set)
+        if self.pcen_settings is not None:
+            # Config.PCEN (csrc/pcen.hip): the log-mel channels of THIS recording, in place and before
+            # the crop -- the smoother restarts per recording, the timeline holds PCEN values; the other channels and the
+            # rotation terms are not touched (the switches defined on dB or power values were refused by _init_fields)
+            p = self.pcen_settings
+            seld_native.pcen(spec, seld_augment.logmel_channels(feature_set, int(spec.shape[1])),
+                             seld_native.pcen_coefficient(p["PCEN_TIME_CONSTANT"]), p["PCEN_GAIN"], p["PCEN_BIAS"],
+                             p["PCEN_POWER"], p["PCEN_EPS"], out=spec)
         audio_duration = pcm.shape[1] / rate                                   # dataset.py:232 (float64)
         if self.use_gaussian_augmentation:                                      # smrl_seld_gaussian.py:608-618
             mask, _, _ = augment_with_gaussian_mask(rows, audio_duration, self.I, self.J,
@@ -438,6 +448,11 @@ class SELDDataset(Dataset):
         self.use_gaussian_augmentation = bool(config.GAUSSIAN_AUGMENT)
         self.with_rotation = bool(getattr(config, "AUGMENT_ROTATE", False))   # as of construction: decides whether rot_tm exists
         self.rot_tm = None
+        # Config.PCEN and its five settings as of construction (seld_augment.pcen_settings), or None: what the log-mel
+        # channels of the timeline hold; evaluation compares it with what the checkpoint records
+        self.pcen_settings = seld_augment.pcen_settings(config)
+        if self.pcen_settings is not None:       # the switches defined on dB or power values: refused before any launch
+            seld_augment.check_settings(config, pcen=True)
         # Config.MIC_POSITIONS as of construction: float64 [C, 3], or None (no array: the FOA rules of the augmenting gathers)
         self.mic_array = seld_augment.mic_positions(getattr(config, "MIC_POSITIONS", None))
         self._feature_statistics = None          # statistics of THIS timeline (feature_statistics), computed once

@@ -14,6 +14,8 @@ With ``--thresholds`` the per-class detection thresholds of a sweep's thresholds
 (DESIGN.md section 17).
 A checkpoint trained with FEATURE_SET 'logmel_nipd' carries NIPD_MIN_HZ, NIPD_MAX_HZ and SOUND_SPEED in its ``config``: the
 recordings' features are computed with those values, which are logged.
+A checkpoint trained with Config.PCEN carries the switch and its five settings the same way: the recordings' log-mel
+channels are normalised with them, and Config is put back afterwards.
 """
 import argparse
 import logging
@@ -90,6 +92,12 @@ def main(argv=None):
     nipd = {k: float(own[k]) for k in trainer.NIPD_SETTINGS if k in own}
     if nipd:
         logging.getLogger(__name__).info("NIPD settings of the checkpoint: " + ", ".join(f"{k} = {v:g}" for k, v in nipd.items()))
+    # Config.PCEN and its five settings travel the same way: the recordings' log-mel channels are
+    # normalised with what the weights were trained on
+    pcen = {k: own[k] for k in trainer.PCEN_SETTINGS if k in own}
+    if pcen.get("PCEN"):
+        logging.getLogger(__name__).info("PCEN settings of the checkpoint: "
+                                         + ", ".join(f"{k} = {v:g}" for k, v in pcen.items() if k != "PCEN"))
     # a microphone array's geometry (Config.MIC_POSITIONS) travels in the checkpoint like the NIPD settings
     array = seld_augment.mic_positions(own.get("MIC_POSITIONS", getattr(trainer.config, "MIC_POSITIONS", None)))
     patterns = seld_augment.tta_patterns(getattr(trainer.config, "SELD_TTA_PATTERNS", ()) if args.tta is None else args.tta,
@@ -109,6 +117,9 @@ def main(argv=None):
         saved_nipd = {k: getattr(dataset.config, k) for k in nipd}
         for k, v in nipd.items():
             setattr(dataset.config, k, v)
+        saved_pcen = {k: vars(dataset.config)[k] for k in pcen if k in vars(dataset.config)}
+        for k, v in pcen.items():
+            setattr(dataset.config, k, v)
         own_array = "MIC_POSITIONS" in vars(dataset.config)      # (restored below without leaving an instance attribute)
         saved_array = vars(dataset.config).get("MIC_POSITIONS")
         dataset.config.MIC_POSITIONS = array
@@ -119,10 +130,16 @@ def main(argv=None):
             dataset.config.RESAMPLE_INPUT = saved
             for k, v in saved_nipd.items():
                 setattr(dataset.config, k, v)
+            for k in pcen:                                       # likewise: no instance attribute is left behind
+                if k in saved_pcen:
+                    setattr(dataset.config, k, saved_pcen[k])
+                else:
+                    delattr(dataset.config, k)
             if own_array:
                 dataset.config.MIC_POSITIONS = saved_array
             else:
                 del dataset.config.MIC_POSITIONS
+        trainer.check_dataset_pcen(trainer.checkpoint_pcen_settings(checkpoint), ds, "the checkpoint records")
         seld_augment.check_tta(patterns, getattr(trainer.config, "FEATURE_SET", "logmel"), ds.n_channels, array=array)
         # a checkpoint trained on standardised features carries their statistics: the recording's gathers apply them
         # (Config.STANDARDISE_FEATURES on and none in the checkpoint: an error, as in evaluate_seld)

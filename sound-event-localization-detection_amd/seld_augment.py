@@ -332,12 +332,47 @@ def enabled(cfg) -> bool:
             or spectral_enabled(cfg))
 
 
-def check_settings(cfg, feature_set: str | None = None, n_channels: int | None = None, array=None):
+PCEN_SETTINGS = ("PCEN", "PCEN_TIME_CONSTANT", "PCEN_GAIN", "PCEN_BIAS", "PCEN_POWER", "PCEN_EPS")
+# the switches that are defined on dB or power values and so have no meaning on PCEN values, with how each counts as on
+PCEN_EXCLUDES = (("AUGMENT_MIX_PROB", "mix_prob"), ("AUGMENT_ROTATE", "rotate"), ("AUGMENT_LEVEL_DB", "level_db"),
+                 ("AUGMENT_FILTER_PROB", "filter_prob"))
+
+
+def pcen_settings(cfg):
+    """The per-channel energy normalisation a Config asks for: None with Config.PCEN off, else
+    {'PCEN_TIME_CONSTANT', 'PCEN_GAIN', 'PCEN_BIAS', 'PCEN_POWER', 'PCEN_EPS': float}, checked against the ranges the
+    kernel takes (ValueError)."""
+    if not bool(getattr(cfg, "PCEN", False)):
+        return None
+    p = {name: float(getattr(cfg, name)) for name in PCEN_SETTINGS[1:]}
+    if not all(np.isfinite(v) for v in p.values()):
+        raise ValueError(f"the PCEN settings must be finite, got {p}")
+    if not p["PCEN_TIME_CONSTANT"] > 0:
+        raise ValueError(f"PCEN_TIME_CONSTANT must be a positive time in seconds, got {p['PCEN_TIME_CONSTANT']}")
+    if not 0.0 <= p["PCEN_GAIN"] <= 1.0:
+        raise ValueError(f"PCEN_GAIN must be in [0, 1], got {p['PCEN_GAIN']}")
+    if not 0.0 < p["PCEN_POWER"] <= 1.0:
+        raise ValueError(f"PCEN_POWER must be in (0, 1], got {p['PCEN_POWER']}")
+    if not (p["PCEN_BIAS"] > 0 and p["PCEN_EPS"] > 0):
+        raise ValueError(f"PCEN_BIAS and PCEN_EPS must be positive, got {p['PCEN_BIAS']} and {p['PCEN_EPS']}")
+    return p
+
+
+def check_settings(cfg, feature_set: str | None = None, n_channels: int | None = None, array=None, pcen: bool | None = None):
     """Raise ValueError for switches outside their range or a spatial swap the feature set does not define.  ``array``:
     microphone positions (``mic_positions``; None reads Config.MIC_POSITIONS) -- with them the spatial rules are those of
-    the array in place of the FOA ones."""
+    the array in place of the FOA ones.  ``pcen``: the features hold PCEN values (None reads
+    Config.PCEN) -- the switches defined on dB or power values are then refused."""
     s = settings(cfg)
     array = _array_of(cfg, array)
+    if bool(getattr(cfg, "PCEN", False)) if pcen is None else pcen:
+        for name, key in PCEN_EXCLUDES:
+            if s[key]:
+                raise ValueError(
+                    f"{name} cannot be combined with PCEN: it is defined on the log-mel channels' dB or power values (powers "
+                    f"add, a level is a dB offset, the rotation terms are mel powers), and with PCEN on those channels hold "
+                    f"normalised values.  Switch one of them off (channel swaps, masks, cutout, frequency shift, "
+                    f"standardisation and balanced sampling commute with a per-channel transform and stay allowed)")
     for key in ("time_masks", "freq_masks"):
         if not 0 <= s[key] <= 2:
             raise ValueError(f"AUGMENT_{key.upper()} must be 0, 1 or 2, got {s[key]}")

@@ -211,6 +211,9 @@ def _declare(lib):
         fn.argtypes = [_ptr, _i64, _i64, _i64, _ptr, _int, _int, _int, _int, _ptr, _i64, _ptr]
     lib.seld_frame_class_mask.argtypes = [_ptr, _i64, _int, _ptr, _ptr]
     lib.seld_window_class_frames.argtypes = [_ptr, _i64, _i64, _i64, _i64, _int, _ptr, _ptr]
+    lib.seld_pcen_workspace.restype = _i64
+    lib.seld_pcen_workspace.argtypes = [_i64, _i64, _int, _int]
+    lib.seld_pcen.argtypes = [_ptr, _ptr, _i64, _i64, _int, _int, _f, _f, _f, _f, _f, _ptr, _i64, _ptr]
     return lib
 
 
@@ -619,7 +622,55 @@ def feature_moments(spec_tm: torch.Tensor) -> torch.Tensor:
     return moments
 
 
-BALANCE_COLUMNS = 16              # SELD_BALANCE_COLUMNS: classes 0..13, frames with any class, frames inside the timeline
+PCEN_CHUNK_FRAMES = 256           # SELD_PCEN_CHUNK_FRAMES
+PCEN_FRAME_RATE = 50.0            # feature frames per second: hop 480 at 24 kHz
+
+
+def pcen_coefficient(tau: float) -> float:
+    """The smoother's coefficient s of a time constant ``tau`` in seconds at 50 frames per second, in float64:
+    T_f = 50 tau, s = (sqrt(1 + 4 T_f^2) - 1) / (2 T_f^2) -- evaluated as 2 / (1 + sqrt(1 + 4 T_f^2)), the same number
+    without the cancellation at small tau (tau -> 0 gives s -> 1, a smoother that follows the input)."""
+    import math
+    tau = float(tau)
+    if not (math.isfinite(tau) and tau > 0.0):
+        raise ValueError(f"pcen_coefficient: the time constant must be finite and positive, got {tau}")
+    tf = PCEN_FRAME_RATE * tau
+    return 2.0 / (1.0 + math.sqrt(1.0 + 4.0 * tf * tf))
+
+
+def pcen(features: torch.Tensor, c_log: int, s: float, alpha: float, delta: float, r: float, eps: float,
+         out: torch.Tensor | None = None) -> torch.Tensor:
+    """Per-channel energy normalisation of the first ``c_log`` (log-mel, dB) channels of time-major features
+    [T, C, 64] (one clip) or [N, T, C, 64] (float32, on the GPU; csrc/pcen.hip):
+    y = (E (eps + M)^-alpha + delta)^r - delta^r with E the mel power behind the stored dB value and M its first-order
+    average along time with coefficient ``s`` (``pcen_coefficient``), restarted in every clip.  ``out``: None (a new tensor:
+    the other channels are copied from ``features``), ``features`` itself (in place) or a tensor of its shape whose other
+    channels are left as they are.  The chunk carries live in a workspace from the caching allocator, freed on return
+    (stream-ordered: the allocator reuses it only behind this stream's work).  Out-of-range parameters are refused by the
+    library (SeldNativeError) before any launch."""
+    if not (isinstance(features, torch.Tensor) and features.is_cuda and features.dtype == torch.float32
+            and features.dim() in (3, 4) and features.shape[-1] == N_MELS and features.is_contiguous()):
+        raise SeldNativeError("pcen: features must be a contiguous float32 GPU tensor [T, C, 64] or [N, T, C, 64]")
+    if features.numel() == 0:
+        raise ValueError("pcen: empty features")
+    if out is None:
+        out = features.clone()
+    elif not (isinstance(out, torch.Tensor) and out.device == features.device and out.dtype == torch.float32
+              and out.shape == features.shape and out.is_contiguous()):
+        raise SeldNativeError("pcen: out must be a contiguous float32 tensor of the features' shape on their device")
+    index = ensure_init(features.device)
+    lib = load_library()
+    clips = int(features.shape[0]) if features.dim() == 4 else 1
+    frames, channels = int(features.shape[-3]), int(features.shape[-2])
+    nbytes = int(lib.seld_pcen_workspace(clips, frames, channels, int(c_log)))
+    with _device_guard(index):
+        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=features.device)
+        check(lib.seld_pcen(_p(features), _p(out), clips, frames, channels, int(c_log), float(s), float(alpha), float(delta),
+                            float(r), float(eps), _p(workspace), nbytes, _stream_ptr(features.device)), "seld_pcen")
+    return out
+
+
+BALANCE_COLUMNS = 16             # SELD_BALANCE_COLUMNS: classes 0..13, frames with any class, frames inside the timeline
 BALANCE_MAX_CLASSES = 14          # SELD_BALANCE_MAX_CLASSES
 
 

@@ -267,6 +267,11 @@ class LoaderFeed:
             raise RuntimeError("BALANCED_SAMPLING: the windows' class statistics are reduced from the device-resident label mask "
                                "and need the device feed (DEVICE_FEED = True, a ROCm GPU, a SELDDataset kept on the device); "
                                "the host DataLoader path has no CPU implementation of it.  Switch it off to use this path")
+        if getattr(config, "PCEN", False):
+            # likewise: the recurrence along time is a device kernel (csrc/pcen.hip)
+            raise RuntimeError("PCEN: the per-channel energy normalisation runs on the device-resident features and needs the "
+                               "device feed (DEVICE_FEED = True, a ROCm GPU, a SELDDataset kept on the device); the host "
+                               "DataLoader path has no CPU implementation of it.  Switch it off to use this path")
         self.loader, self.device = loader, device
         self.rank, self.world, self.seed = rank, world, seed
         sampler = getattr(loader, "sampler", None)
@@ -329,8 +334,12 @@ class DeviceFeed:
             if (self.array is None) != (now is None) or (now is not None and not np.array_equal(self.array, now)):
                 raise ValueError("Config.MIC_POSITIONS differs from the positions this dataset was constructed with "
                                  "(SELDDataset.mic_array): construct the dataset under the setting the training runs with")
+            # (a dataset whose timeline holds PCEN values refuses the switches defined on dB or power values, whatever
+            # Config.PCEN says by now)
             seld_augment.check_settings(config, getattr(config, "FEATURE_SET", "logmel"), self.dataset.n_channels,
-                                        array=self.array)
+                                        array=self.array,
+                                        pcen=bool(getattr(config, "PCEN", False))
+                                        or getattr(self.dataset, "pcen_settings", None) is not None)
             if seld_augment.settings(config)["rotate"] and getattr(self.dataset, "rot_tm", None) is None:
                 raise ValueError("AUGMENT_ROTATE needs a dataset constructed with the switch on and kept on the device: the "
                                  "rotating gather reads three extra mel rows per frame of the timeline (SELDDataset.rot_tm)")
@@ -882,6 +891,26 @@ def apply_checkpoint_statistics(checkpoint, dataset):
 
 
 NIPD_SETTINGS = ("NIPD_MIN_HZ", "NIPD_MAX_HZ", "SOUND_SPEED")
+PCEN_SETTINGS = seld_augment.PCEN_SETTINGS     # Config.PCEN and its five settings
+
+
+def checkpoint_pcen_settings(checkpoint):
+    """The PCEN settings a checkpoint's config records (``checkpoint_payload`` pins them with the switch on), in the form
+    of ``SELDDataset.pcen_settings``; None when it records none or the switch off."""
+    own = getattr(checkpoint.get("config"), "__dict__", {})
+    if not own.get("PCEN", False):
+        return None
+    return {name: float(own.get(name, getattr(Config, name))) for name in PCEN_SETTINGS[1:]}
+
+
+def check_dataset_pcen(expected, dataset, who):
+    """Raise ValueError when ``dataset`` was built with other PCEN settings than ``expected`` (``who`` says whose they
+    are): the weights would see other input values than they were trained on."""
+    built = getattr(dataset, "pcen_settings", None)
+    if built != expected:
+        say = lambda p: "PCEN off" if p is None else "PCEN on with " + ", ".join(f"{k} = {v:g}" for k, v in p.items())
+        raise ValueError(f"the dataset was built with {say(built)}, {who} with {say(expected)}: construct the dataset under "
+                         f"the same Config.PCEN settings (infer.py adopts a checkpoint's by itself)")
 
 
 def checkpoint_payload(epoch, model, optimizer, train_loss, test_loss, feature_statistics=None):
@@ -907,6 +936,10 @@ def checkpoint_payload(epoch, model, optimizer, train_loss, test_loss, feature_s
         # a pickled instance carries its OWN attributes only: pin what the NIPD channels were computed with, so that
         # infer.py reads them from the file and not from whatever the class says on the day it runs
         for name in NIPD_SETTINGS:
+            setattr(config, name, getattr(config, name))
+    if getattr(config, "PCEN", False):
+        # likewise what the log-mel channels were normalised with; with the switch off no key appears
+        for name in PCEN_SETTINGS:
             setattr(config, name, getattr(config, name))
     if getattr(config, "MIC_POSITIONS", None) is not None:
         # likewise the array's geometry: infer.py --tta swaps channels by the positions in the file
@@ -981,6 +1014,9 @@ def train_model(train_loader, test_loader, num_epochs=None, batch_size=None, lea
     # the timeline in the same fixed order: the same bits without a collective); None with the switch off
     feature_statistics = standardise_datasets(train_dataset, test_dataset)
     log_balanced_sampling(train_feed)
+    # Config.PCEN: the checkpoints will record this Config's settings, so both datasets must have been built with them
+    for ds in (train_dataset, test_dataset):
+        check_dataset_pcen(seld_augment.pcen_settings(config), ds, "this run's Config says")
 
     train_losses, test_losses = [], []
     best_train_loss = best_test_loss = float("inf")
@@ -1153,6 +1189,7 @@ def test_model(test_loader, model_path=None, batch_size=None, device=None, num_v
                                      device)
     model.load_state_dict(select_state_dict(checkpoint, use_ema))
     apply_checkpoint_statistics(checkpoint, test_dataset)      # the checkpoint decides (Config.STANDARDISE_FEATURES)
+    check_dataset_pcen(checkpoint_pcen_settings(checkpoint), test_dataset, "the checkpoint records")   # (Config.PCEN)
     model.eval()
     logger.info(f"Model loaded (epoch {checkpoint['epoch']}, test loss {checkpoint['test_loss']:.6f})")
     criterion = SMRSELDLoss(loss_type=config.LOSS_TYPE, w_class=config.W_CLASS, w_aiur=config.W_AIUR,
@@ -1325,6 +1362,7 @@ def evaluate_seld(test_loader, model_path=None, batch_size=None, device=None, th
                                                  n_channels=getattr(test_dataset, "n_channels", None)), device)
     model.load_state_dict(select_state_dict(checkpoint, use_ema))
     apply_checkpoint_statistics(checkpoint, test_dataset)      # the checkpoint decides (Config.STANDARDISE_FEATURES)
+    check_dataset_pcen(checkpoint_pcen_settings(checkpoint), test_dataset, "the checkpoint records")   # (Config.PCEN)
     model.eval()
     logger.info(f"SELD evaluation: {len(test_dataset)} windows, checkpoint epoch {checkpoint['epoch']}")
     if patterns:
