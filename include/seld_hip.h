@@ -31,6 +31,12 @@ int seld_shutdown(void);
 int seld_version(void);
 const char* seld_last_error(void);
 
+/* The compute-unit count the current device's grids, workspace queries and plans are sized from (>= 1), -3 before
+ * seld_init.  It is the device's own count unless the developer switch SELD_CUS=n (an integer >= 1, read once by
+ * seld_init; anything else makes seld_init return -1) lowered it to min(n, device count): a test seam that makes every
+ * CU-capped kernel walk its grid-stride laps at small shapes, never a tuning knob. */
+int seld_num_cus(void);
+
 /* Override the default HTK mel filterbank with a host table fb[481][64] (fp32), e.g. the one
  * torchaudio.functional.melscale_fbanks would build.  Replaces the constant inside
  * torchaudio.transforms.MelScale used at dataset.py:38-43. */

@@ -1,5 +1,7 @@
 // libseld_hip.so -- library state, constant tables, error reporting.  C ABI: include/seld_hip.h
+#include <errno.h>
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <map>
@@ -82,6 +84,17 @@ int seld_init(int device) {
   hipDeviceProp_t prop;
   SELD_HIP_TRY(hipGetDeviceProperties(&prop, device));
   st.num_cus = prop.multiProcessorCount;
+  // SELD_CUS=n: developer/test seam, read here only (st.ready latches): every CU-capped grid, workspace query and plan
+  // of this process sees min(n, device CUs), so the grid-stride laps run at unit-test shapes.  It can only lower the count.
+  const char* cus = getenv("SELD_CUS");
+  if (cus && *cus) {
+    char* end = nullptr;
+    errno = 0;
+    const long n = strtol(cus, &end, 10);
+    if (errno != 0 || end == cus || *end != '\0' || n < 1)
+      return fail(kErrInvalidArgument, std::string("seld_init: SELD_CUS=\"") + cus + "\" is not an integer >= 1");
+    if (n < st.num_cus) st.num_cus = static_cast<int>(n);
+  }
 
   std::vector<float> window, twiddle;
   hann_window(window);
@@ -102,6 +115,12 @@ int seld_init(int device) {
   if (rc_gcc != kOk) return rc_gcc;
   st.ready = true;
   return kOk;
+}
+
+int seld_num_cus(void) {
+  using namespace seld;
+  DeviceState* st = current_state();
+  return st ? st->num_cus : kErrNotInitialised;
 }
 
 int seld_shutdown(void) {

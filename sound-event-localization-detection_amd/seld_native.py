@@ -48,6 +48,8 @@ def _declare(lib):
     lib.seld_version.argtypes = []
     lib.seld_init.argtypes = [_int]
     lib.seld_shutdown.argtypes = []
+    lib.seld_num_cus.restype = _int
+    lib.seld_num_cus.argtypes = []
     lib.seld_set_mel_filterbank.argtypes = [_ptr]
     lib.seld_set_window.argtypes = [_ptr]
     lib.seld_default_tables.argtypes = [_ptr] * 5
@@ -290,6 +292,17 @@ def ensure_init(device) -> int:
     with _lock:
         _initialised_devices.add(index)
     return index
+
+
+def num_cus(device=None) -> int:
+    """The compute-unit count the library sizes its grids, workspaces and plans from on ``device`` (default: the current
+    one): the device's own, or the lower one the developer switch SELD_CUS set when seld_init ran."""
+    index = ensure_init(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
+    with _device_guard(index):
+        n = int(load_library().seld_num_cus())
+    if n < 1:
+        check(n, "seld_num_cus")
+    return n
 
 
 class _NoGuard:
